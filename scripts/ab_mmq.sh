@@ -6,6 +6,6 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_verify.py tests/test_gpu_de
 tail -2 $OUT/t.log
 shift
 for v in "$@"; do
-  env $v timeout -k 10 200 python -u bench.py --no-cpu --steps 8 --warmup 2 > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 1; }
+  env $v timeout -k 10 200 python -u bench.py --full --no-cpu --steps 8 --warmup 2 > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/b.json'));print('$v','decode',d['value'],'prefill ms',d['prefill']['ms'])"
 done

@@ -17,7 +17,7 @@ for rep in 1 2; do
   i=0
   for v in "$@"; do
     i=$((i+1)); [ "$v" = "-" ] && v=""
-    env $v timeout -k 10 200 python -u bench.py --no-cpu --prefill 0 --verify 0 --steps 256 > $OUT/b_$i.json 2> $OUT/b_$i.err || { tail $OUT/b_$i.err; exit 1; }
+    env $v timeout -k 10 200 python -u bench.py --full --no-cpu --prefill 0 --verify 0 --steps 256 > $OUT/b_$i.json 2> $OUT/b_$i.err || { tail $OUT/b_$i.err; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/b_$i.json'));print('[$v]',d['value'],d['roofline']['avg_launch_us'])"
   done
 done

@@ -24,13 +24,13 @@ if [ -n "$SWEEP" ]; then
   cat $OUT/sweep.txt
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 300 python -u bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
   ok $? bench
   cat $OUT/bench.json
 fi
 if [ -z "$SKIP_PROF" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-      python -u bench.py --no-cpu --steps 32 --warmup 4 ${PROF_ARGS} > $OUT/prof_bench.json 2> $OUT/prof.err
+      python -u bench.py --full --no-cpu --steps 32 --warmup 4 ${PROF_ARGS} > $OUT/prof_bench.json 2> $OUT/prof.err
   ok $? rocprof
   find $OUT/prof -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
   head -20 $OUT/kernel_stats.csv

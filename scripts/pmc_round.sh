@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 MI_NO_GRAPH=1 timeout -s KILL 170 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof -o run -- \
-    python -u bench.py --no-cpu --prefill 0 --verify 0 --steps 8 --warmup 2 > $OUT/pmc_bench.json 2> $OUT/pmc.err || { tail -5 $OUT/pmc.err; exit 1; }
+    python -u bench.py --full --no-cpu --prefill 0 --verify 0 --steps 8 --warmup 2 > $OUT/pmc_bench.json 2> $OUT/pmc.err || { tail -5 $OUT/pmc.err; exit 1; }
 CSV=$(find $OUT/prof -name '*counter_collection.csv' | head -1)
 [ -n "$CSV" ] || { echo "no counter_collection.csv"; exit 1; }
 cp $CSV $OUT/counter_collection.csv

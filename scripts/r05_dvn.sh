@@ -8,7 +8,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_decode.py tests/test_gpu_fu
 rc=$?; echo "pytest rc $rc"; grep -E "FAIL|Error" $OUT/pytest.log | head -10; tail -2 $OUT/pytest.log
 [ $rc -eq 0 ] || exit 1
 for mode in 1 0 1 0 1 0; do
-  MI_DV_NORM=$mode timeout -k 10 150 python -u bench.py --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/bench_n$mode.json 2> $OUT/bench_n$mode.err || { tail -5 $OUT/bench_n$mode.err; exit 1; }
+  MI_DV_NORM=$mode timeout -k 10 150 python -u bench.py --full --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/bench_n$mode.json 2> $OUT/bench_n$mode.err || { tail -5 $OUT/bench_n$mode.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_n$mode.json'));print('dv_norm=$mode', d['value'], d['roofline']['avg_launch_us'])"
 done
 exit 0

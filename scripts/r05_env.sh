@@ -5,7 +5,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() {   # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 150 python -u bench.py --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/b_$name.json 2> $OUT/b_$name.err || { echo "$name failed"; tail -3 $OUT/b_$name.err; return 1; }
+  env "$@" timeout -k 10 150 python -u bench.py --full --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/b_$name.json 2> $OUT/b_$name.err || { echo "$name failed"; tail -3 $OUT/b_$name.err; return 1; }
   python3 -c "import json;d=json.load(open('$OUT/b_$name.json'));print('$name', d['value'], d['roofline']['avg_launch_us'])"
 }
 for r in 1 2; do

@@ -8,7 +8,7 @@ MI_MMQS1_LEAN=1 timeout -k 10 300 python -u -m pytest tests/test_gpu_batch_ops.p
 tail -1 $OUT/ops.log
 for cfg in llama2-7b-q4_k_m mixtral-8x7b-q5_k_m; do
   for lean in 0 1 0 1; do
-    MI_MMQS1_LEAN=$lean timeout -k 10 300 python -u bench.py --config $cfg --no-cpu --steps 8 --warmup 2 > $OUT/b_${cfg}_$lean.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
+    MI_MMQS1_LEAN=$lean timeout -k 10 300 python -u bench.py --full --config $cfg --no-cpu --steps 8 --warmup 2 > $OUT/b_${cfg}_$lean.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/b_${cfg}_$lean.json'));p=d['prefill'];print('$cfg lean $lean','short',[v['ms'] for v in p['verify_short']])"
   done
 done

@@ -12,7 +12,7 @@ rc=$?; echo "fulldepth rc $rc"; grep -E "passed|failed|score|assert" $OUT/t_fd.l
 [ $rc -eq 0 ] || exit 1
 for mode in on off; do
   if [ $mode = off ]; then export MI_MOE_SHORT_OFF=1; fi
-  timeout -k 10 300 python -u bench.py --config mixtral-8x7b-q5_k_m --no-cpu --steps 16 --warmup 4 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { tail -5 $OUT/bench_$mode.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config mixtral-8x7b-q5_k_m --no-cpu --steps 16 --warmup 4 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { tail -5 $OUT/bench_$mode.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_$mode.json'));p=d['prefill'];print('$mode decode',d['value'],'prefill',p['ms'],'verify',p['verify']['ms'],'short',[v['ms'] for v in p['verify_short']])"
 done
 exit 0

@@ -12,7 +12,7 @@ rc=$?; echo "pytest rc $rc"; tail -5 $OUT/pytest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit 1; fi
 for mode in new old; do
   if [ $mode = old ]; then export MI_DECODE_OLD=1; fi
-  timeout -k 10 200 python -u bench.py --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { echo "bench $mode failed"; tail -5 $OUT/bench_$mode.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --no-cpu --prefill 0 --verify 0 --steps 128 --warmup 16 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { echo "bench $mode failed"; tail -5 $OUT/bench_$mode.err; exit 1; }
   python -c "import json;d=json.load(open('$OUT/bench_$mode.json'));print('$mode', d['value'], d['roofline']['avg_launch_us'])"
 done
 unset MI_DECODE_OLD

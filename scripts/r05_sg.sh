@@ -9,7 +9,7 @@ rc=$?; echo "pytest rc $rc"; grep -E "FAIL|Error" $OUT/pytest.log | head -10; ta
 [ $rc -eq 0 ] || exit 1
 for mode in graph eager graph eager; do
   if [ $mode = eager ]; then export MI_NO_GRAPH=1; else unset MI_NO_GRAPH; fi
-  timeout -k 10 200 python -u bench.py --no-cpu --steps 8 --warmup 2 --verify 0 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { tail -5 $OUT/bench_$mode.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --no-cpu --steps 8 --warmup 2 --verify 0 > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err || { tail -5 $OUT/bench_$mode.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_$mode.json'));p=d['prefill'];print('$mode short',[v['ms'] for v in p.get('verify_short',[])])"
 done
 exit 0

@@ -7,7 +7,7 @@ MI_SHORT_DEC=1 timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeo
 rc=$?; tail -2 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
 for i in 1 2 3; do
   for f in 1 0; do
-    MI_SHORT_DEC=$f timeout -k 10 300 python -u bench.py --no-cpu --steps 16 --warmup 4 --prof-layer -1 \
+    MI_SHORT_DEC=$f timeout -k 10 300 python -u bench.py --full --no-cpu --steps 16 --warmup 4 --prof-layer -1 \
         > $OUT/bench_d${f}_$i.json 2> $OUT/bench_d${f}_$i.err || { tail -3 $OUT/bench_d${f}_$i.err; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/bench_d${f}_$i.json'));p=d['prefill'];print('short_dec=$f verify256',p['verify']['ms'],'short',[v['ms'] for v in p['verify_short']])"
   done
