@@ -564,12 +564,7 @@ GemvParams single_gemv(const QMat& m, const float* x, float* y) {
     p.x[0] = x;
     p.K = m.K;
     p.nseg = 1;
-    p.seg[0].A = m;
-    p.seg[0].B = m;
-    p.seg[0].pair = PAIR_ADJ;
-    p.seg[0].epi = EPI_STORE;
-    p.seg[0].expA = p.seg[0].expB = -1;
-    p.seg[0].out = y;
+    p.seg[0] = seg_of(m, PAIR_ADJ, EPI_STORE, y);
     return p;
 }
 
@@ -642,12 +637,8 @@ int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw,
         const int epi[4] = {EPI_QKV, EPI_ADD, EPI_SWIGLU, EPI_STORE};
         for (int s = 0; s < p.nseg; ++s) {
             GemvSeg& g = p.seg[s];
-            g.A = s == 0 ? a : b;
-            g.B = role == 2 ? b : g.A;
-            g.pair = role == 2 ? PAIR_AB : PAIR_ADJ;
-            g.epi = epi[role];
-            g.expA = g.expB = -1;
-            g.out = dy.as<float>() + (s == 0 ? 0 : rows);
+            g = seg_of(s == 0 ? a : b, role == 2 ? PAIR_AB : PAIR_ADJ, epi[role], dy.as<float>() + (s == 0 ? 0 : rows));
+            if (role == 2) g.B = b;
             g.nq = g.A.rows;   // Q/K/V: every row a Q row, n_rot 0 (no rotation)
             g.resid = role == 1 ? dr.as<float>() : nullptr;
         }

@@ -424,7 +424,6 @@ bool dgemv_supported(const GemvParams& p) {
     const int role = dv_role(p);
     if (role < 0 || g.bias || g.expA >= 0 || g.expB >= 0) return false;
     if (p.nseg == 2 && (dv_base(role) != DV_QKV || p.seg[1].epi != EPI_QKV)) return false;
-    if ((role == DV_QKVN || role == DV_SWIGLUN) && p.K > 4 * 256 * 2 * dv_chunks(p.K)) return false;
     return dv_fn(role, g.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K)) != nullptr;
 }
 

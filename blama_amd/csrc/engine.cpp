@@ -1,8 +1,7 @@
-// Engine host code: GGUF parsing, weight residency and the batch-1 decode
-// schedule captured into HIP graphs.
+// Engine host code: the decode context -- its buffers, the batch-1 decode schedule captured
+// into HIP graphs, prompt batches, sampling reads and the KV cache (the model: model.cpp).
 //
 // Reference anchors (the llama.h functions this replaces):
-//   llama_model_load_from_file  /root/reference/inference/code/llama/Model.cpp:52
 //   llama_init_from_model       /root/reference/inference/code/llama/Instance.cpp:36
 //   llama_decode                /root/reference/inference/code/llama/Session.cpp:388
 //   llama_get_logits_ith        /root/reference/inference/code/llama/Session.cpp:24
@@ -19,524 +18,10 @@
 
 namespace mi {
 
-static thread_local std::string g_last_error;
-void set_last_error(const std::string& s) { g_last_error = s; }
-const char* last_error() { return g_last_error.c_str(); }
-
-// ================================================================== GGUF ===
-namespace {
-struct Reader {
-    const uint8_t* p;
-    size_t n, pos = 0;
-    void need(size_t k) {
-        if (pos + k > n) throw Error("GGUF: truncated header");
-    }
-    template <class T> T rd() {
-        need(sizeof(T));
-        T v;
-        std::memcpy(&v, p + pos, sizeof(T));
-        pos += sizeof(T);
-        return v;
-    }
-    std::string str() {
-        const uint64_t len = rd<uint64_t>();
-        need(len);
-        std::string s(reinterpret_cast<const char*>(p + pos), len);
-        pos += len;
-        return s;
-    }
-};
-
-enum { G_U8 = 0, G_I8, G_U16, G_I16, G_U32, G_I32, G_F32, G_BOOL, G_STR, G_ARR, G_U64, G_I64, G_F64 };
-
-double read_num(Reader& r, int t, bool* is_float) {
-    *is_float = false;
-    switch (t) {
-    case G_U8: return r.rd<uint8_t>();
-    case G_I8: return r.rd<int8_t>();
-    case G_U16: return r.rd<uint16_t>();
-    case G_I16: return r.rd<int16_t>();
-    case G_U32: return r.rd<uint32_t>();
-    case G_I32: return r.rd<int32_t>();
-    case G_F32: *is_float = true; return r.rd<float>();
-    case G_BOOL: return r.rd<uint8_t>();
-    case G_U64: return (double)r.rd<uint64_t>();
-    case G_I64: return (double)r.rd<int64_t>();
-    case G_F64: *is_float = true; return r.rd<double>();
-    default: throw Error("GGUF: bad value type");
-    }
-}
-}  // namespace
-
-void Gguf::parse(const uint8_t* data, size_t size) {
-    Reader r{data, size};
-    if (size < 24 || std::memcmp(data, "GGUF", 4) != 0) throw Error("not a GGUF file");
-    r.pos = 4;
-    const uint32_t ver = r.rd<uint32_t>();
-    if (ver != 2 && ver != 3) throw Error("unsupported GGUF version " + std::to_string(ver));
-    const uint64_t nt = r.rd<uint64_t>(), nkv = r.rd<uint64_t>();
-    for (uint64_t i = 0; i < nkv; ++i) {
-        std::string key = r.str();
-        GgufValue v;
-        v.type = (int)r.rd<uint32_t>();
-        if (v.type == G_STR) {
-            v.s = r.str();
-        } else if (v.type == G_ARR) {
-            v.arr_type = (int)r.rd<uint32_t>();
-            v.arr_n = (long long)r.rd<uint64_t>();
-            if (v.arr_type == G_STR) {
-                v.arr_s.reserve(v.arr_n);
-                for (long long k = 0; k < v.arr_n; ++k) v.arr_s.push_back(r.str());
-            } else {
-                v.arr_num.reserve(v.arr_n);
-                bool fl;
-                for (long long k = 0; k < v.arr_n; ++k) v.arr_num.push_back(read_num(r, v.arr_type, &fl));
-            }
-        } else {
-            bool fl;
-            const double d = read_num(r, v.type, &fl);
-            v.f = d;
-            v.i = (long long)d;
-        }
-        kv.emplace(std::move(key), std::move(v));
-    }
-    for (uint64_t i = 0; i < nt; ++i) {
-        GgufTensor t;
-        t.name = r.str();
-        t.n_dims = (int)r.rd<uint32_t>();
-        if (t.n_dims < 1 || t.n_dims > 4) throw Error("GGUF: bad n_dims for " + t.name);
-        long long n = 1;
-        for (int d = 0; d < t.n_dims; ++d) { t.ne[d] = (long long)r.rd<uint64_t>(); n *= t.ne[d]; }
-        t.type = (int)r.rd<uint32_t>();
-        t.offset = r.rd<uint64_t>();
-        const int be = block_elems(t.type), bb = block_bytes(t.type);
-        if (bb == 0) {
-            t.nbytes = 0;   // unsupported type: only an error if the tensor is used
-        } else {
-            if (n % be) throw Error("GGUF: tensor " + t.name + " not a whole number of blocks");
-            t.nbytes = (size_t)(n / be) * bb;
-        }
-        tensors.push_back(t);
-    }
-    const long long align = get_int("general.alignment", 32);
-    data_offset = (r.pos + align - 1) / align * align;
-}
-
-long long Gguf::get_int(const std::string& k, long long def) const {
-    const GgufValue* v = get(k);
-    return (v && v->type != G_STR && v->type != G_ARR) ? v->i : def;
-}
-double Gguf::get_float(const std::string& k, double def) const {
-    const GgufValue* v = get(k);
-    return (v && v->type != G_STR && v->type != G_ARR) ? v->f : def;
-}
-std::string Gguf::get_str(const std::string& k, const std::string& def) const {
-    const GgufValue* v = get(k);
-    return (v && v->type == G_STR) ? v->s : def;
-}
-const GgufTensor* Gguf::tensor(const std::string& name) const {
-    for (const auto& t : tensors)
-        if (t.name == name) return &t;
-    return nullptr;
-}
-
-// ================================================================= model ===
-Model::~Model() {
-    if (arena || mmq_arena || gelu_tab) hipSetDevice(device);
-    if (arena) hipFree(arena);
-    if (mmq_arena) hipFree(mmq_arena);
-    if (gelu_tab) hipFree(gelu_tab);
-}
-
-namespace {
-// ggml_table_gelu_f16 (ggml-cpu.c init with GGML_GELU_FP16): fp16(ggml_gelu_f32(fp32(h))) for
-// every f16 bit pattern h, ggml_gelu_f32(x) = 0.5f*x*(1.0f + tanhf(SQRT_2_OVER_PI*x*(1.0f +
-// GELU_COEF_A*x*x))), evaluated on the host with the C library's tanhf (no FMA contraction:
-// -ffp-contract=off), as the reference's CPU build evaluates it.
-std::vector<unsigned short> gelu_table_host() {
-    std::vector<unsigned short> t(65536);
-    const float A = 0.044715f, K = 0.79788456080286535587989211986876f;
-    for (int i = 0; i < 65536; ++i) {
-        const unsigned short h = (unsigned short)i;
-        _Float16 hf;
-        std::memcpy(&hf, &h, 2);
-        const float x = (float)hf;
-        const float g = 0.5f * x * (1.0f + tanhf(K * x * (1.0f + A * x * x)));
-        const _Float16 r = (_Float16)g;
-        std::memcpy(&t[i], &r, 2);
-    }
-    return t;
-}
-}  // namespace
-
-// Expert e of a MoE tensor as a matrix of its own (planes and MFMA-order copy offset).
-QMat expert_view(const QMat& q, int e) {
-    QMat v = q;
-    for (int k = 0; k < 4; ++k)
-        if (v.p[k]) v.p[k] += e * q.expert_stride[k];
-    if (v.sw) v.sw += e * q.sw_expert_stride;
-    return v;
-}
-
-bool Model::ensure_mmq_copies() {
-    std::lock_guard<std::mutex> lk(mmq_mu);
-    if (mmq_arena) return true;
-    MI_HIP(hipSetDevice(device));
-    // every mmq32-capable projection (gate and up as one pair copy; MoE: one copy per expert,
-    // expert e at sw + e * sw_expert_stride) and the output head
-    std::vector<std::pair<QMat*, QMat*>> todo;
-    for (Layer& L : layers) {
-        for (QMat* q : {&L.wq, &L.wk, &L.wv, &L.wo, &L.down})
-            if (mmq32_supported(q->type)) todo.push_back({q, nullptr});
-        if (mmq32_supported(L.gate.type) && L.up.type == L.gate.type) todo.push_back({&L.gate, &L.up});
-    }
-    if (mmq32_supported(output.type)) todo.push_back({&output, nullptr});
-    auto experts = [](const QMat& q) { return std::max(1, q.n_exp); };
-    size_t total = 0;
-    std::vector<size_t> offs;
-    for (auto& t : todo) {
-        offs.push_back(total);
-        const size_t one = mmq32_copy_bytes(*t.first, t.second != nullptr);
-        total = (total + one * experts(*t.first) + 255) & ~size_t(255);
-    }
-    if (!total) return true;
-    if (hipMalloc(&mmq_arena, total) != hipSuccess) {
-        (void)hipGetLastError();   // clear the sticky error; the caller falls back
-        mmq_arena = nullptr;
-        return false;
-    }
-    mmq_bytes = total;
-    for (size_t i = 0; i < todo.size(); ++i) {
-        QMat& A = *todo[i].first;
-        const size_t one = mmq32_copy_bytes(A, todo[i].second != nullptr);
-        for (int e = 0; e < experts(A); ++e) {   // expert e's planes -> its own copy
-            QMat a = expert_view(A, e), b = todo[i].second ? expert_view(*todo[i].second, e) : QMat{};
-            launch_mmq32_swizzle(a, todo[i].second ? &b : nullptr, mmq_arena + offs[i] + one * e, nullptr);
-        }
-        A.sw = mmq_arena + offs[i];
-        A.sw_expert_stride = (long long)one;
-    }
-    MI_HIP(hipDeviceSynchronize());
-    return true;
-}
-
-const QMat* Model::find_qmat(const std::string&) const { return nullptr; }
-
-namespace {
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-struct Planned {
-    const GgufTensor* t;
-    size_t off[4];     // arena offsets of the planes (quant) or of the raw copy (p0)
-    long long rows;    // rows across all experts
-    int K;
-    int experts;
-};
-}  // namespace
-
-void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
-    device = p.device_ordinal;
-    vocab_only = p.vocab_only != 0;
-    gguf.parse(data, size);
-    const std::string arch = gguf.get_str("general.architecture", "");
-    if (arch != "llama" && arch != "gpt2")
-        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama and gpt2 graphs)");
-    hp.arch = arch == "gpt2" ? ARCH_GPT2 : ARCH_LLAMA;
-    auto key = [&](const char* k) { return arch + "." + k; };
-    hp.n_embd = (int)gguf.get_int(key("embedding_length"), 0);
-    hp.n_layer = (int)gguf.get_int(key("block_count"), 0);
-    hp.n_ff = (int)gguf.get_int(key("feed_forward_length"), 0);
-    hp.n_head = (int)gguf.get_int(key("attention.head_count"), 0);
-    hp.n_head_kv = (int)gguf.get_int(key("attention.head_count_kv"), hp.n_head);
-    hp.n_ctx_train = (int)gguf.get_int(key("context_length"), 2048);
-    hp.eps = (float)gguf.get_float(key(hp.arch == ARCH_GPT2 ? "attention.layer_norm_epsilon"
-                                                             : "attention.layer_norm_rms_epsilon"), 1e-5);
-    hp.rope_base = (float)gguf.get_float(key("rope.freq_base"), 10000.0);
-    const double fs = gguf.get_float(key("rope.scale_linear"), 0.0);
-    hp.freq_scale = fs > 0.0 ? (float)(1.0 / fs) : 1.0f;
-    hp.n_expert = (int)gguf.get_int(key("expert_count"), 0);
-    hp.n_expert_used = (int)gguf.get_int(key("expert_used_count"), 0);
-    if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0) throw Error("GGUF: missing llama hparams");
-    hp.head_dim = hp.n_embd / hp.n_head;
-    hp.n_rot = hp.arch == ARCH_GPT2 ? 0 : (int)gguf.get_int(key("rope.dimension_count"), hp.head_dim);
-    if (hp.arch == ARCH_GPT2 && hp.n_expert) throw Error("gpt2: no MoE");
-
-    if (const GgufValue* tv = gguf.get("tokenizer.ggml.tokens")) tokens = tv->arr_s;
-    if (const GgufValue* tt = gguf.get("tokenizer.ggml.token_type"))
-        for (double d : tt->arr_num) token_type.push_back((int)d);
-    if (const GgufValue* ts = gguf.get("tokenizer.ggml.scores"))
-        for (double d : ts->arr_num) token_score.push_back((float)d);
-    tok_model = gguf.get_str("tokenizer.ggml.model", "llama");
-    if (const GgufValue* mv = gguf.get("tokenizer.ggml.merges")) merges = mv->arr_s;
-    hp.n_vocab = (int)tokens.size();
-    if (const GgufTensor* te = gguf.tensor("token_embd.weight")) hp.n_vocab = (int)te->ne[1];
-    bos = (int)gguf.get_int("tokenizer.ggml.bos_token_id", 1);
-    eos = (int)gguf.get_int("tokenizer.ggml.eos_token_id", 2);
-    eot = (int)gguf.get_int("tokenizer.ggml.eot_token_id", -1);
-    add_bos = gguf.get_int("tokenizer.ggml.add_bos_token", 1) != 0;
-    if (vocab_only) return;
-    if (p.cpu_only) throw Error("cpu_only models are served by the CPU reference path, not this engine");
-
-    // ---- plan the arena ----
-    std::vector<Planned> plan;
-    size_t off = 0;
-    auto add = [&](const std::string& name, bool required, int experts) -> int {
-        const GgufTensor* t = gguf.tensor(name);
-        if (!t) {
-            if (required) throw Error("GGUF: missing tensor " + name);
-            return -1;
-        }
-        Planned pl{};
-        pl.t = t;
-        pl.K = (int)t->ne[0];
-        pl.experts = experts;
-        pl.rows = t->ne[1] * (t->n_dims > 2 ? t->ne[2] : 1);
-        if (is_quant(t->type)) {
-            if (pl.K % 256) throw Error("tensor " + name + ": K not a multiple of 256");
-            const long long nsb = pl.rows * (pl.K / 256);
-            for (int k = 0; k < plane_count(t->type); ++k) {
-                pl.off[k] = off;   // + 8 superblocks of tail padding read by idle GEMV lanes
-                off = align256(off + (size_t)(nsb + kPlanePadSb) * plane_sb_bytes(t->type, k));
-            }
-        } else if (t->type == T_F32 || t->type == T_F16) {
-            pl.off[0] = off;
-            off = align256(off + t->nbytes);
-        } else {
-            throw Error("tensor " + name + ": unsupported ggml type " + std::to_string(t->type));
-        }
-        plan.push_back(pl);
-        return (int)plan.size() - 1;
-    };
-    // Q/K/V of one layer as groups of adjacent same-type tensors whose planes are stored back to
-    // back (plane k of the group = plane k of each tensor in order): one decode-GEMV matrix each
-    auto add_group = [&](const std::vector<std::string>& names, std::vector<int>& idx) {
-        std::vector<const GgufTensor*> ts;
-        for (const auto& n : names) {
-            const GgufTensor* t = gguf.tensor(n);
-            if (!t) throw Error("GGUF: missing tensor " + n);
-            ts.push_back(t);
-        }
-        const int type = ts[0]->type;
-        const int K = (int)ts[0]->ne[0];
-        if (!is_quant(type) || K % 256) throw Error("tensor " + names[0] + ": not a quantised matrix with K % 256 == 0");
-        const size_t first = plan.size();
-        for (const GgufTensor* t : ts) {
-            if (t->type != type || (int)t->ne[0] != K) throw Error("add_group: mixed tensors");
-            Planned pl{};
-            pl.t = t;
-            pl.K = K;
-            pl.experts = 1;
-            pl.rows = t->ne[1];
-            plan.push_back(pl);
-            idx.push_back((int)plan.size() - 1);
-        }
-        for (int k = 0; k < plane_count(type); ++k) {
-            for (size_t i = first; i < plan.size(); ++i) {
-                plan[i].off[k] = off;
-                off += (size_t)plan[i].rows * (K / 256) * plane_sb_bytes(type, k);
-            }
-            off = align256(off + (size_t)kPlanePadSb * plane_sb_bytes(type, k));
-        }
-    };
-    struct LayerIdx {
-        int an, fn, q, k, v, o, g, u, d, r;
-        std::vector<std::vector<int>> qkv_groups;
-        int anb = -1, fnb = -1, bqkv = -1, bo = -1, bu = -1, bd = -1;   // GPT-2 biases
-    };
-    const bool gpt2 = hp.arch == ARCH_GPT2;
-    const int i_te = add("token_embd.weight", true, 1);
-    const int i_pe = gpt2 ? add("position_embd.weight", true, 1) : -1;
-    const int i_on = add("output_norm.weight", true, 1);
-    const int i_onb = gpt2 ? add("output_norm.bias", true, 1) : -1;
-    int i_out = add("output.weight", false, 1);
-    const int i_rf = add("rope_freqs.weight", false, 1);
-    std::vector<LayerIdx> li(hp.n_layer);
-    const int E = hp.n_expert > 0 ? hp.n_expert : 1;
-    for (int l = 0; l < hp.n_layer && gpt2; ++l) {   // llm_build_gpt2's tensors (LLM_ARCH_GPT2)
-        const std::string b = "blk." + std::to_string(l) + ".";
-        LayerIdx& x = li[l];
-        x.an = add(b + "attn_norm.weight", true, 1);
-        x.anb = add(b + "attn_norm.bias", true, 1);
-        x.fn = add(b + "ffn_norm.weight", true, 1);
-        x.fnb = add(b + "ffn_norm.bias", true, 1);
-        std::vector<int> idx;
-        add_group({b + "attn_qkv.weight"}, idx);   // one fused [3 n_embd] x n_embd matrix
-        x.qkv_groups.push_back(idx);
-        x.q = x.k = x.v = idx[0];
-        x.bqkv = add(b + "attn_qkv.bias", true, 1);
-        x.o = add(b + "attn_output.weight", true, 1);
-        x.bo = add(b + "attn_output.bias", true, 1);
-        x.r = -1;
-        x.g = x.u = add(b + "ffn_up.weight", true, 1);
-        x.bu = add(b + "ffn_up.bias", true, 1);
-        x.d = add(b + "ffn_down.weight", true, 1);
-        x.bd = add(b + "ffn_down.bias", true, 1);
-    }
-    for (int l = 0; l < hp.n_layer && !gpt2; ++l) {
-        const std::string b = "blk." + std::to_string(l) + ".";
-        LayerIdx& x = li[l];
-        x.an = add(b + "attn_norm.weight", true, 1);
-        x.fn = add(b + "ffn_norm.weight", true, 1);
-        {
-            const std::string nq = b + "attn_q.weight", nk = b + "attn_k.weight", nv = b + "attn_v.weight";
-            const GgufTensor *tq = gguf.tensor(nq), *tk = gguf.tensor(nk), *tv = gguf.tensor(nv);
-            if (!tq || !tk || !tv) throw Error("GGUF: missing attention tensors in " + b);
-            std::vector<std::vector<std::string>> groups;
-            if (tq->type == tk->type && tk->type == tv->type) groups = {{nq, nk, nv}};
-            else if (tq->type == tk->type) groups = {{nq, nk}, {nv}};
-            else if (tk->type == tv->type) groups = {{nq}, {nk, nv}};
-            else groups = {{nq}, {nk}, {nv}};
-            std::vector<int> all;
-            for (const auto& g : groups) {
-                std::vector<int> idx;
-                add_group(g, idx);
-                x.qkv_groups.push_back(idx);
-                all.insert(all.end(), idx.begin(), idx.end());
-            }
-            x.q = all[0];
-            x.k = all[1];
-            x.v = all[2];
-        }
-        x.o = add(b + "attn_output.weight", true, 1);
-        if (hp.n_expert > 0) {
-            x.r = add(b + "ffn_gate_inp.weight", true, 1);
-            x.g = add(b + "ffn_gate_exps.weight", true, E);
-            x.u = add(b + "ffn_up_exps.weight", true, E);
-            x.d = add(b + "ffn_down_exps.weight", true, E);
-        } else {
-            x.r = -1;
-            x.g = add(b + "ffn_gate.weight", true, 1);
-            x.u = add(b + "ffn_up.weight", true, 1);
-            x.d = add(b + "ffn_down.weight", true, 1);
-        }
-    }
-    if (hp.n_expert > 0 && hp.n_expert_used != 2)
-        throw Error("MoE: this build serves top-2 routing (expert_used_count=2)");
-    arena_bytes = off;
-    for (const auto& pl : plan) {
-        // bytes one decode step streams: an expert tensor contributes the n_expert_used experts
-        // the router picks (build_moe_ffn reads only those), not all n_expert of them
-        if (pl.t->name != "token_embd.weight" && pl.t->name != "position_embd.weight")
-            weight_bytes += pl.experts > 1 ? (long long)pl.t->nbytes / pl.experts * hp.n_expert_used
-                                           : (long long)pl.t->nbytes;
-        if (pl.t->type >= 0 && pl.t->type < 32) type_bytes[pl.t->type] += (long long)pl.t->nbytes;
-    }
-    if (i_out < 0) weight_bytes += (long long)plan[i_te].t->nbytes;   // tied output head
-
-    MI_HIP(hipSetDevice(device));
-    MI_HIP(hipMalloc(&arena, arena_bytes));
-
-    // ---- upload + repack ----
-    if (!p.no_upload) {
-        size_t max_raw = 0;
-        for (const auto& pl : plan)
-            if (is_quant(pl.t->type)) max_raw = std::max(max_raw, pl.t->nbytes);
-        uint8_t* staging = nullptr;
-        if (max_raw) MI_HIP(hipMalloc(&staging, max_raw));
-        for (const auto& pl : plan) {
-            const size_t src = gguf.data_offset + pl.t->offset;
-            if (src + pl.t->nbytes > size) {
-                if (staging) hipFree(staging);
-                throw Error("GGUF: tensor data of " + pl.t->name + " beyond the end of the image");
-            }
-            if (is_quant(pl.t->type)) {
-                MI_HIP(hipMemcpy(staging, data + src, pl.t->nbytes, hipMemcpyHostToDevice));
-                uint8_t* planes[4] = {arena + pl.off[0], arena + pl.off[1], arena + pl.off[2], arena + pl.off[3]};
-                launch_repack(staging, pl.t->type, pl.rows, pl.K, planes, nullptr);
-            } else {
-                MI_HIP(hipMemcpy(arena + pl.off[0], data + src, pl.t->nbytes, hipMemcpyHostToDevice));
-            }
-        }
-        MI_HIP(hipDeviceSynchronize());
-        if (staging) hipFree(staging);
-    }
-
-    // ---- device views ----
-    auto qm = [&](int idx) -> QMat {
-        QMat m{};
-        const Planned& pl = plan[idx];
-        m.type = pl.t->type;
-        m.K = pl.K;
-        m.nb = pl.K / 256;
-        m.rows = (int)(pl.rows / pl.experts);
-        m.n_exp = pl.experts;
-        if (is_quant(m.type)) {
-            for (int k = 0; k < plane_count(m.type); ++k) {
-                m.p[k] = arena + pl.off[k];
-                m.expert_stride[k] = (long long)m.rows * m.nb * plane_sb_bytes(m.type, k);
-            }
-        } else {
-            m.p[0] = arena + pl.off[0];
-        }
-        return m;
-    };
-    auto f32p = [&](int idx) -> float* {
-        if (idx < 0) return nullptr;
-        if (plan[idx].t->type != T_F32) throw Error("tensor " + plan[idx].t->name + " must be F32");
-        return reinterpret_cast<float*>(arena + plan[idx].off[0]);
-    };
-    tok_embd = qm(i_te);
-    if (i_pe >= 0) pos_embd = qm(i_pe);
-    output_norm_b = f32p(i_onb);
-    output = i_out >= 0 ? qm(i_out) : qm(i_te);
-    if (!is_quant(output.type)) throw Error("output head must be a quantised tensor in this build");
-    output_norm = f32p(i_on);
-    rope_freqs = f32p(i_rf);
-    layers.resize(hp.n_layer);
-    for (int l = 0; l < hp.n_layer; ++l) {
-        Layer& L = layers[l];
-        const LayerIdx& x = li[l];
-        L.attn_norm = f32p(x.an);
-        L.ffn_norm = f32p(x.fn);
-        L.wq = qm(x.q); L.wk = qm(x.k); L.wv = qm(x.v); L.wo = qm(x.o);
-        L.gate = qm(x.g); L.up = qm(x.u); L.down = qm(x.d);
-        L.router = f32p(x.r);
-        L.attn_norm_b = f32p(x.anb);
-        L.ffn_norm_b = f32p(x.fnb);
-        L.bqkv = f32p(x.bqkv);
-        L.bo = f32p(x.bo);
-        L.bup = f32p(x.bu);
-        L.bdown = f32p(x.bd);
-        for (const QMat* m : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down})
-            if (!is_quant(m->type)) throw Error("layer weights must be quantised (Q4_K/Q5_K/Q6_K/Q8_0)");
-        if (gpt2) {   // the fused QKV rows: n_embd Q rows, n_embd K rows, n_embd V rows
-            L.n_qkv = 1;
-            L.qkv[0] = qm(x.qkv_groups[0][0]);
-            L.qkv_nq[0] = hp.n_embd;
-            L.qkv_nk[0] = hp.n_head_kv * hp.head_dim;
-            if (L.qkv[0].rows != L.qkv_nq[0] + 2 * L.qkv_nk[0]) throw Error("gpt2: attn_qkv must have 3 n_embd rows");
-            continue;
-        }
-        L.n_qkv = (int)x.qkv_groups.size();
-        int seen = 0;   // Q rows, then K rows, then V rows across the groups
-        for (int g = 0; g < L.n_qkv; ++g) {
-            QMat m = qm(x.qkv_groups[g][0]);
-            int nq = 0, nk = 0, rows = 0;
-            for (int i : x.qkv_groups[g]) {
-                const int r = (int)plan[i].rows;
-                if (seen == 0) nq += r;
-                else if (seen == 1) nk += r;
-                rows += r;
-                ++seen;
-            }
-            m.rows = rows;
-            L.qkv[g] = m;
-            L.qkv_nq[g] = nq;
-            L.qkv_nk[g] = nk;
-        }
-    }
-    if (gpt2) {
-        const std::vector<unsigned short> t = gelu_table_host();
-        MI_HIP(hipMalloc(&gelu_tab, t.size() * sizeof(unsigned short)));
-        MI_HIP(hipMemcpy(gelu_tab, t.data(), t.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    }
-}
-
 // =============================================================== context ===
 namespace {
 std::vector<int> g_attr_done(64, 0);
 
-namespace {
 struct DevChain {
     std::mutex mu;
     std::atomic<int> nctx{0};  // live contexts on the device (attention co-residency budget)
@@ -549,7 +34,14 @@ DevChain& dev_chain(int device) {
     if (!c) c.reset(new DevChain());
     return *c;
 }
+// activation formats a set of matrices reads: bit 0 Q8_K (k-quants), bit 1 Q8_0
+int act_fmt(std::initializer_list<int> types) {
+    int f = 0;
+    for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
+    return f;
+}
 }  // namespace
+int dev_chain_contexts(int device) { return dev_chain(device).nctx.load(); }
 
 GemvSeg seg_of(const QMat& A, int pair, int epi, float* out) {
     GemvSeg g;
@@ -562,8 +54,53 @@ GemvSeg seg_of(const QMat& A, int pair, int epi, float* out) {
     g.out = out;
     return g;
 }
-}  // namespace
-int dev_chain_contexts(int device) { return dev_chain(device).nctx.load(); }
+
+// ---- CtxMem ----
+void* CtxMem::dev_bytes(size_t bytes, bool zero) {
+    dev_ptrs.reserve(dev_ptrs.size() + 1);   // (no throw between the allocation and its record)
+    void* p = nullptr;
+    MI_HIP(hipMalloc(&p, bytes));
+    dev_ptrs.push_back(p);
+    if (zero) MI_HIP(hipMemset(p, 0, bytes));
+    return p;
+}
+void* CtxMem::host_bytes(size_t bytes, unsigned flags) {
+    host_ptrs.reserve(host_ptrs.size() + 1);
+    void* p = nullptr;
+    MI_HIP(hipHostMalloc(&p, bytes, flags));
+    host_ptrs.push_back(p);
+    return p;
+}
+void CtxMem::free_one(void* p) {
+    if (!p) return;
+    auto d = std::find(dev_ptrs.begin(), dev_ptrs.end(), p);
+    if (d != dev_ptrs.end()) {
+        dev_ptrs.erase(d);
+        hipFree(p);
+        return;
+    }
+    auto h = std::find(host_ptrs.begin(), host_ptrs.end(), p);
+    if (h == host_ptrs.end()) throw Error("CtxMem: not a buffer of this context");
+    host_ptrs.erase(h);
+    hipHostFree(p);
+}
+hipStream_t CtxMem::stream() {
+    if (!stream_) MI_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    return stream_;
+}
+hipEvent_t CtxMem::event() {
+    events.reserve(events.size() + 1);
+    hipEvent_t e = nullptr;
+    MI_HIP(hipEventCreate(&e));
+    events.push_back(e);
+    return e;
+}
+CtxMem::~CtxMem() {
+    for (hipEvent_t e : events) hipEventDestroy(e);
+    for (void* p : dev_ptrs) hipFree(p);
+    for (void* p : host_ptrs) hipHostFree(p);
+    if (stream_) hipStreamDestroy(stream_);
+}
 
 Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(model) {
     if (m->vocab_only) throw Error("cannot create a context on a vocab-only model");
@@ -578,28 +115,25 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         init_kernel_attributes();
         g_attr_done[device] = 1;
     }
-    MI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const size_t kvb = (size_t)hp.n_layer * n_ctx * kv_dim * sizeof(__half);
-    MI_HIP(hipMalloc(&kcache, kvb));
-    MI_HIP(hipMalloc(&vcache, kvb));
-    MI_HIP(hipMemset(kcache, 0, kvb));
-    MI_HIP(hipMemset(vcache, 0, kvb));
-    MI_HIP(hipMalloc(&cell_pos, n_ctx * sizeof(int)));
-    MI_HIP(hipMemset(cell_pos, 0, n_ctx * sizeof(int)));
-    MI_HIP(hipMalloc(&tokpos, 4 * sizeof(int)));
-    MI_HIP(hipMemset(tokpos, 0, 4 * sizeof(int)));
+    stream = mem.stream();
+    const size_t kvn = (size_t)hp.n_layer * n_ctx * kv_dim;
+    kcache = mem.dev<__half>(kvn);
+    vcache = mem.dev<__half>(kvn);
+    MI_HIP(hipMemset(kcache, 0, kvn * sizeof(__half)));
+    MI_HIP(hipMemset(vcache, 0, kvn * sizeof(__half)));
+    cell_pos = mem.dev<int>(n_ctx, true);
+    tokpos = mem.dev<int>(4, true);
     const int big = std::max(hp.n_embd, hp.n_ff);
-    MI_HIP(hipMalloc(&x, hp.n_embd * sizeof(float)));
-    MI_HIP(hipMalloc(&q, hp.n_embd * sizeof(float)));
-    MI_HIP(hipMalloc(&attn, hp.n_embd * sizeof(float)));
-    MI_HIP(hipMalloc(&h, big * sizeof(float)));
-    MI_HIP(hipMalloc(&h2, big * sizeof(float)));
-    MI_HIP(hipMalloc(&logits, (size_t)hp.n_vocab * sizeof(float)));
-    MI_HIP(hipMalloc(&cand, (size_t)topk_blocks(hp.n_vocab) * TOPK_MAX * sizeof(unsigned long long)));
-    MI_HIP(hipMalloc(&part_o, (size_t)ATTN_SMAX * hp.n_head * hp.head_dim * sizeof(float)));
+    x = mem.dev<float>(hp.n_embd);
+    q = mem.dev<float>(hp.n_embd);
+    attn = mem.dev<float>(hp.n_embd);
+    h = mem.dev<float>(big);
+    h2 = mem.dev<float>(big);
+    logits = mem.dev<float>(hp.n_vocab);
+    cand = mem.dev<unsigned long long>((size_t)topk_blocks(hp.n_vocab) * TOPK_MAX);
+    part_o = mem.dev<float>((size_t)ATTN_SMAX * hp.n_head * hp.head_dim);
 #ifdef MI_STAMPS
-    MI_HIP(hipMalloc(&stamps, (size_t)kStampLaunches * kStampWgs * 8 * sizeof(unsigned long long)));
-    MI_HIP(hipMemset(stamps, 0, (size_t)kStampLaunches * kStampWgs * 8 * sizeof(unsigned long long)));
+    stamps = mem.dev<unsigned long long>((size_t)kStampLaunches * kStampWgs * 8, true);
 #endif
     // GPT-2 prompts run token by token (one decode graph each): its batch kernels (LayerNorm,
     // biases, GELU) are not built
@@ -621,12 +155,12 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         const int NB = kBatchRows;
         // MoE: a row per (token, slot), each expert's rows padded to whole 32-row tiles
         const int hrows = hp.n_expert > 0 ? moe_rows_cap(NB * hp.n_expert_used, hp.n_expert) : NB;
-        MI_HIP(hipMalloc(&xb, (size_t)NB * hp.n_embd * sizeof(float)));
-        MI_HIP(hipMalloc(&qb, (size_t)NB * hp.n_embd * sizeof(float)));
-        MI_HIP(hipMalloc(&attnb, (size_t)NB * hp.n_embd * sizeof(float)));
-        MI_HIP(hipMalloc(&hb, (size_t)hrows * hp.n_ff * sizeof(float)));
-        MI_HIP(hipMalloc(&tokpos_b, (size_t)NB * 4 * sizeof(int)));
-        MI_HIP(hipHostMalloc(&h_tokpos_b, (size_t)kTokbRing * NB * 4 * sizeof(int)));
+        xb = mem.dev<float>((size_t)NB * hp.n_embd);
+        qb = mem.dev<float>((size_t)NB * hp.n_embd);
+        attnb = mem.dev<float>((size_t)NB * hp.n_embd);
+        hb = mem.dev<float>((size_t)hrows * hp.n_ff);
+        tokpos_b = mem.dev<int>((size_t)NB * 4);
+        h_tokpos_b = mem.host<int>((size_t)kTokbRing * NB * 4);
         const int kmax = std::max(hp.n_embd, hp.n_ff);
         if (mmq_ok) {
             // ub_q / ub_dT / ub_bsb: the k-quant (Q8_K) activations, or the Q8_0 ones when every
@@ -637,32 +171,31 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
             mmq_ok = m->ensure_mmq_copies();
             out_mmq = mmq_ok && mmq32_supported(m->output.type);
             attn_mfma = attn_mfma_supported(hp.head_dim);
-            MI_HIP(hipMalloc(&ub_q, (size_t)UB_MAX * kmax));
-            MI_HIP(hipMalloc(&ub_dT, (size_t)UB_MAX * (kmax / 32) * sizeof(float)));   // Q8_0: per 32
-            MI_HIP(hipMalloc(&ub_bsb, (size_t)UB_MAX * (kmax / 256) * 16));
+            ub_q = mem.dev<int8_t>((size_t)UB_MAX * kmax);
+            ub_dT = mem.dev<float>((size_t)UB_MAX * (kmax / 32));   // Q8_0: per 32
+            ub_bsb = mem.dev<int8_t>((size_t)UB_MAX * (kmax / 256) * 16);
             if (any_k && any_0) {
-                MI_HIP(hipMalloc(&ub_q0, (size_t)UB_MAX * kmax));
-                MI_HIP(hipMalloc(&ub_dT0, (size_t)UB_MAX * (kmax / 32) * sizeof(float)));
+                ub_q0 = mem.dev<int8_t>((size_t)UB_MAX * kmax);
+                ub_dT0 = mem.dev<float>((size_t)UB_MAX * (kmax / 32));
             }
             if (hp.n_expert > 0) {   // routing of a physical batch, grouped rows, expert down outputs
                 if (hp.n_expert > MOE_GROUP_MAXE) throw Error("MoE prompt batches: at most 16 experts");
                 const int ns = NB * hp.n_expert_used;
                 const int cap = moe_rows_cap(ns, hp.n_expert);
-                MI_HIP(hipMalloc(&yb, (size_t)cap * hp.n_embd * sizeof(float)));
-                MI_HIP(hipMalloc(&sel_b, (size_t)ns * sizeof(int)));
-                MI_HIP(hipMalloc(&selw_b, (size_t)ns * sizeof(float)));
-                MI_HIP(hipMalloc(&moe_rows, (size_t)cap * sizeof(int)));
-                MI_HIP(hipMalloc(&moe_rowsel, (size_t)cap * sizeof(int)));
-                MI_HIP(hipMalloc(&moe_pos, (size_t)ns * sizeof(int)));
-                MI_HIP(hipMalloc(&moe_grp, (size_t)(2 * MOE_GROUP_MAXE + 1) * sizeof(int)));
-                MI_HIP(hipMalloc(&moe_q, (size_t)cap * kmax));
-                MI_HIP(hipMalloc(&moe_dT, (size_t)cap * (kmax / 32) * sizeof(float)));
-                MI_HIP(hipMalloc(&moe_bsb, (size_t)cap * (kmax / 256) * 16));
+                yb = mem.dev<float>((size_t)cap * hp.n_embd);
+                sel_b = mem.dev<int>(ns);
+                selw_b = mem.dev<float>(ns);
+                moe_rows = mem.dev<int>(cap);
+                moe_rowsel = mem.dev<int>(cap);
+                moe_pos = mem.dev<int>(ns);
+                moe_grp = mem.dev<int>(2 * MOE_GROUP_MAXE + 1);
+                moe_q = mem.dev<int8_t>((size_t)cap * kmax);
+                moe_dT = mem.dev<float>((size_t)cap * (kmax / 32));
+                moe_bsb = mem.dev<int8_t>((size_t)cap * (kmax / 256) * 16);
             }
-            MI_HIP(hipMalloc(&ub_rope, (size_t)UB_MAX * std::max(1, hp.n_rot / 2) * sizeof(float2)));
+            ub_rope = mem.dev<float2>((size_t)UB_MAX * std::max(1, hp.n_rot / 2));
             // split-K partials of the residual GEMMs (WO, FFN down) of dense models
-            if (mmq2_active())
-                MI_HIP(hipMalloc(&ub_part, (size_t)2 * UB_MAX * hp.n_embd * sizeof(float)));
+            if (mmq2_active()) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
             mmqs_max = getenv("MI_MMQS_MAX") ? std::min(MMQS_MAX, std::max(0, atoi(getenv("MI_MMQS_MAX")))) : MMQS_MAX;
             // MoE: short batches when every expert matrix has the grouped form (k-quants)
             moe_short = hp.n_expert > 0;
@@ -678,7 +211,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
                 if (moe_short)   // the experts' parts over the MoE rows of MMQS_MAX tokens
                     tot = std::max(tot, std::max((size_t)mmqs_parts(hp.n_embd) * 2 * hp.n_ff, (size_t)mmqs_parts(hp.n_ff) * hp.n_embd) *
                                             (size_t)moe_rows_cap(MMQS_MAX * hp.n_expert_used, hp.n_expert));
-                MI_HIP(hipMalloc(&ub_spart, tot * sizeof(float)));
+                ub_spart = mem.dev<float>(tot);
             } else {
                 moe_short = false;
                 mmqs_max = 0;
@@ -687,38 +220,35 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         // MoE prompts need the MFMA path (the v_dot4 GEMM has no routed-expert form)
         if (hp.n_expert > 0 && !mmq_ok) batch_ok = false;
     }
-    MI_HIP(hipMalloc(&attn_smax, (size_t)ATTN_SMAX * hp.n_head * sizeof(float)));
-    MI_HIP(hipMalloc(&attn_scores, (size_t)hp.n_head * n_ctx * sizeof(float)));
-    MI_HIP(hipMalloc(&attn_xflags, (size_t)hp.n_head * ATTN_SMAX * 32 * sizeof(unsigned)));
-    MI_HIP(hipMemset(attn_xflags, 0, (size_t)hp.n_head * ATTN_SMAX * 32 * sizeof(unsigned)));
-    MI_HIP(hipMalloc(&attn_xmax, (size_t)hp.n_head * ATTN_SMAX * sizeof(float)));
-    MI_HIP(hipMalloc(&attn_xsum, (size_t)hp.n_head * ATTN_SMAX * sizeof(double)));
-    MI_HIP(hipMalloc(&step_ctr, 16));
-    MI_HIP(hipMemset(step_ctr, 0, 16));
-    MI_HIP(hipHostMalloc(&h_attn_xerr, 16, hipHostMallocMapped | hipHostMallocCoherent));
+    attn_smax = mem.dev<float>((size_t)ATTN_SMAX * hp.n_head);
+    attn_scores = mem.dev<float>((size_t)hp.n_head * n_ctx);
+    attn_xflags = mem.dev<unsigned>((size_t)hp.n_head * ATTN_SMAX * 32, true);
+    attn_xmax = mem.dev<float>((size_t)hp.n_head * ATTN_SMAX);
+    attn_xsum = mem.dev<double>((size_t)hp.n_head * ATTN_SMAX);
+    step_ctr = mem.dev<unsigned>(4, true);
+    const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+    h_attn_xerr = mem.host<unsigned>(4, mapped);
     *h_attn_xerr = 0;
     MI_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_attn_xerr), h_attn_xerr, 0));
-    MI_HIP(hipMalloc(&topk_ids, TOPK_MAX * sizeof(int)));
-    MI_HIP(hipMalloc(&topk_vals, TOPK_MAX * sizeof(float)));
-    MI_HIP(hipMalloc(&sel, 64 * sizeof(int)));
-    MI_HIP(hipMalloc(&selw, 64 * sizeof(float)));
-    MI_HIP(hipMemset(sel, 0, 64 * sizeof(int)));
-    MI_HIP(hipMemset(selw, 0, 64 * sizeof(float)));
-    MI_HIP(hipMalloc(&gather_ids, 4096 * sizeof(int)));
-    MI_HIP(hipMalloc(&gather_out, 4096 * sizeof(float)));
-    MI_HIP(hipMalloc(&cell_delta, n_ctx * sizeof(int)));
-    MI_HIP(hipMalloc(&move_src, n_ctx * sizeof(int)));
-    MI_HIP(hipHostMalloc(&h_tokpos, kTokRing * 4 * sizeof(int)));
+    topk_ids = mem.dev<int>(TOPK_MAX);
+    topk_vals = mem.dev<float>(TOPK_MAX);
+    sel = mem.dev<int>(64, true);
+    selw = mem.dev<float>(64, true);
+    gather_ids = mem.dev<int>(4096);
+    gather_out = mem.dev<float>(4096);
+    cell_delta = mem.dev<int>(n_ctx);
+    move_src = mem.dev<int>(n_ctx);
+    h_tokpos = mem.host<int>(kTokRing * 4);
     // the top-k kernel writes its result straight into these (coherent, mapped)
-    MI_HIP(hipHostMalloc(&h_topk_ids, TOPK_MAX * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    MI_HIP(hipHostMalloc(&h_topk_vals, TOPK_MAX * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    h_topk_ids = mem.host<int>(TOPK_MAX, mapped);
+    h_topk_vals = mem.host<float>(TOPK_MAX, mapped);
     MI_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_h_topk_ids), h_topk_ids, 0));
     MI_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_h_topk_vals), h_topk_vals, 0));
-    MI_HIP(hipHostMalloc(&h_logits, (size_t)hp.n_vocab * sizeof(float)));
-    MI_HIP(hipHostMalloc(&h_gather, 4096 * sizeof(float)));
+    h_logits = mem.host<float>(hp.n_vocab);
+    h_gather = mem.host<float>(4096);
     h_cell_pos.assign(n_ctx, 0);
     sp_ok = sp_setup();
-    dev_chain(device).nctx++;
+    dev_chain(device).nctx++;   // last: a constructor that throws leaves the count as it was
 }
 
 Ctx::~Ctx() {
@@ -726,22 +256,7 @@ Ctx::~Ctx() {
     hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
     invalidate_graphs();
-    for (auto e : prof_ev) if (e) hipEventDestroy(e);
-    for (void* p : {(void*)kcache, (void*)vcache, (void*)kv_scratch, (void*)cell_pos, (void*)tokpos, (void*)x,
-                    (void*)q, (void*)attn, (void*)h, (void*)h2, (void*)logits, (void*)cand, (void*)topk_ids,
-                    (void*)topk_vals, (void*)sel, (void*)selw, (void*)gather_ids, (void*)gather_out,
-                    (void*)cell_delta, (void*)move_src, (void*)part_o, (void*)attn_smax, (void*)attn_scores, (void*)stamps,
-                    (void*)attn_xflags, (void*)attn_xmax, (void*)attn_xsum, (void*)step_ctr,
-                    (void*)xb, (void*)qb, (void*)attnb, (void*)hb, (void*)tokpos_b, (void*)ub_q, (void*)ub_dT, (void*)ub_bsb, (void*)ub_rope, (void*)ub_part, (void*)ub_spart,
-                    (void*)ub_q0, (void*)ub_dT0, (void*)yb, (void*)sel_b, (void*)selw_b, (void*)moe_rows, (void*)moe_pos,
-                    (void*)moe_rowsel, (void*)moe_grp, (void*)moe_q, (void*)moe_dT, (void*)moe_bsb,
-                    (void*)logits_all, (void*)grows_ids, (void*)grows_out, (void*)sp_mem})
-        if (p) hipFree(p);
-    for (void* p : {(void*)h_tokpos, (void*)h_topk_ids, (void*)h_topk_vals, (void*)h_logits, (void*)h_gather, (void*)h_grows,
-                    (void*)h_tokpos_b, (void*)h_attn_xerr})
-        if (p) hipHostFree(p);
-    if (stream) hipStreamDestroy(stream);
-}
+}   // (mem releases the events, the buffers and the stream)
 
 void Ctx::invalidate_graphs() {
     for (int m = 0; m < 2; ++m) {
@@ -763,57 +278,92 @@ long long Ctx::ffn_bytes() const {
     return w + act;   // weights + x and norm weight read + h written
 }
 
-// The ops of one llm_build_llama layer for the token in tokpos, as launch parameters handed to
-// `gemv` (role: 0 QKV, 1 WO, 2 FFN gate/up, 3 FFN down), `attn` and `router` (the residual
-// updated in place).
-void Ctx::layer_ops(int l, const LayerBufs& B, const std::function<void(const GemvParams&, int)>& gemv,
-                    const std::function<void(const AttnParams&)>& attn,
-                    const std::function<void(const RouterParams&)>& router) {
+// ======================================================== decode launches ===
+// The parameter block of every launch of a batch-1 decode step for the token in tokpos.  Both
+// steps (the streaming one on dgemv_kernel, the r04 one on gemv_kernel), both architectures and
+// sp_setup's dry check build their launches here; a GPT-2 layer (llm_build_gpt2) is the LLaMA one
+// with LayerNorm for RMSNorm, projection biases, no RoPE and up -> GELU for the gate/up pair.
+GemvParams Ctx::gemv_base() const {
+    GemvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tokpos = tokpos;
+    p.cell_pos = cell_pos;
+    p.head_dim = m->hp.head_dim;
+    p.kv_dim = kv_dim;
+    p.eps = m->hp.eps;
+    p.nslots = 1;
+    return p;
+}
+
+ActOut Ctx::act_out(int role, int fmt, int K, const float* norm_w) const {
+    return ActOut{K, fmt & 1, fmt >> 1, sp_act[role], norm_w, m->hp.eps};
+}
+
+// How p's activation arrives: quantised at sp_act[role], or the fp32 row xin (normed with norm_w /
+// norm_b when set) through gemv_kernel's prologue or quantised in the dgemv launch itself.  fmt:
+// the formats the launch's matrices read (dgemv).
+void Ctx::set_act(GemvParams& p, ActSrc src, int role, int fmt, const float* xin, const float* norm_w,
+                  const float* norm_b) const {
+    if (src == ACT_QUANT) {
+        p.act_in = sp_act[role];
+    } else {
+        p.x[0] = xin;
+        p.norm_w = norm_w;
+    }
+    if (src == ACT_PRO) {
+        p.pro = !norm_w ? PRO_PLAIN : m->hp.arch == ARCH_GPT2 ? PRO_LAYERNORM : PRO_RMSNORM;
+        p.norm_b = norm_b;
+    } else {
+        p.act_q8k = fmt & 1;
+        p.act_q80 = fmt >> 1;
+    }
+}
+
+// Q/K/V projections + RoPE + KV append: one launch per pair of row groups a kernel variant can carry
+int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
     const HParams& hp = m->hp;
     const Layer& L = m->layers[l];
-    __half* kl = kcache + (size_t)l * n_ctx * kv_dim;
-    __half* vl = vcache + (size_t)l * n_ctx * kv_dim;
-    const float theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    GemvParams base;
-    std::memset(&base, 0, sizeof(base));
-    base.tokpos = tokpos;
-    base.cell_pos = cell_pos;
-    base.head_dim = hp.head_dim;
-    base.kv_dim = kv_dim;
-    base.eps = hp.eps;
-    base.nslots = 1;
-    // ---- Q/K/V projections + RoPE + KV append: one launch per pair of row groups ----
-    {
-        GemvParams p = base;
-        p.pro = PRO_RMSNORM;
-        p.x[0] = B.x_in;
-        p.norm_w = L.attn_norm;
-        p.K = hp.n_embd;
-        p.theta_scale = theta_scale;
+    GemvParams p = gemv_base();
+    p.K = hp.n_embd;
+    set_act(p, src, 0, src == ACT_PRO ? 0 : sp[l].fA, x, L.attn_norm, L.attn_norm_b);
+    if (hp.arch == ARCH_LLAMA) {   // (GPT-2: learned positions, n_rot 0)
+        p.theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
         p.freq_scale = hp.freq_scale;
         p.n_rot = hp.n_rot;
         p.freq_factors = m->rope_freqs;
-        p.kcache = kl;
-        p.vcache = vl;
-        for (int g = 0; g < L.n_qkv;) {
-            p.nseg = 0;
-            for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
-                if (p.nseg == 1 && !gemv_pair_supported(p.seg[0].A.type, L.qkv[g].type)) break;
-                GemvSeg& sg = p.seg[p.nseg++];
-                sg = seg_of(L.qkv[g], PAIR_ADJ, EPI_QKV, B.q);
-                sg.nq = L.qkv_nq[g];
-                sg.nk = L.qkv_nk[g];
-            }
-            gemv(p, 0);
-        }
     }
-    // ---- attention ----
-    {
-        AttnParams a{B.q, kl, vl, tokpos, cell_pos, attn_scores, attn_smax, B.po, hp.n_head, hp.n_head_kv, hp.head_dim,
-                     kv_dim, (int)n_ctx, kq_scale};
-        a.fused = attn_fused;
-        a.xflags = attn_xflags;   // contexts past ATTN_SHORT: one launch (attn_long_kernel)
+    p.kcache = kcache + (size_t)l * n_ctx * kv_dim;
+    p.vcache = vcache + (size_t)l * n_ctx * kv_dim;
+    int n = 0;
+    for (int g = 0; g < L.n_qkv; ++n) {
+        p.nseg = 0;
+        for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
+            if (p.nseg == 1 && !gemv_pair_supported(p.seg[0].A.type, L.qkv[g].type)) break;
+            GemvSeg& sg = p.seg[p.nseg++];
+            sg = seg_of(L.qkv[g], PAIR_ADJ, EPI_QKV, q);
+            sg.nq = L.qkv_nq[g];
+            sg.nk = L.qkv_nk[g];
+            sg.bias = L.bqkv;   // GPT-2 (its one fused group)
+        }
+        out[n] = p;
+    }
+    return n;
+}
+
+// Attention over the layer's cache.  Up to ATTN_SHORT cells one fused launch, which for the
+// streaming step (quant_out) also quantises its output for WO; past that the split kernels --
+// LLaMA: with the exchange of the single-launch attn_long_kernel -- whose partials the WO prologue
+// (r04 step) or attn_combine_quant (streaming step) adds in split order.
+AttnParams Ctx::attn_params(int l, bool quant_out) const {
+    const HParams& hp = m->hp;
+    AttnParams a{q, kcache + (size_t)l * n_ctx * kv_dim, vcache + (size_t)l * n_ctx * kv_dim, tokpos, cell_pos,
+                 attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv, hp.head_dim, kv_dim, (int)n_ctx,
+                 1.0f / std::sqrt((float)hp.head_dim)};
+    a.fused = attn_fused;
+    if (attn_fused) {
+        if (quant_out) a.act_out = act_out(1, sp[l].fB, hp.n_embd, nullptr);
+    } else if (hp.arch == ARCH_LLAMA) {
+        a.xflags = attn_xflags;
         a.xmax = attn_xmax;
         a.xsum = attn_xsum;
         a.step = step_ctr;
@@ -822,79 +372,131 @@ void Ctx::layer_ops(int l, const LayerBufs& B, const std::function<void(const Ge
         a.xerr = d_attn_xerr;
         a.long_share = dev_chain(device).nctx.load();
         a.long_off = attn_long_off ? 1 : 0;
-        attn(a);
     }
-    // ---- output projection + residual (prologue: the attention splits combined) ----
-    {
-        GemvParams p = base;
+    return a;
+}
+
+// output projection + residual, in place (ACT_PRO: the prologue adds the attention splits)
+GemvParams Ctx::wo_params(int l, ActSrc src) const {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    GemvParams p = gemv_base();
+    p.K = hp.n_embd;
+    if (src == ACT_PRO) {
         p.pro = PRO_ATTN;
-        p.attn = AttnPartials{B.po, hp.n_head, hp.head_dim};
+        p.attn = AttnPartials{part_o, hp.n_head, hp.head_dim};
         p.attn_nsplit = attn_fused ? 1 : 0;   // the split graph reads the count from the cell count
-        p.K = hp.n_embd;
-        p.nseg = 1;
-        p.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, B.xa);
-        p.seg[0].resid = B.x_in;
-        gemv(p, 1);
+    } else {
+        set_act(p, ACT_QUANT, 1, sp[l].fB, nullptr, nullptr, nullptr);
     }
+    p.nseg = 1;
+    p.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, x);
+    p.seg[0].resid = x;
+    p.seg[0].bias = L.bo;
+    return p;
+}
+
+// FFN gate/up + SwiGLU into h (MoE, ACT_PRO only: the two routed experts into h and h2; GPT-2:
+// up + bias + GELU)
+GemvParams Ctx::gate_up_params(int l, ActSrc src) const {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    GemvParams p = gemv_base();
+    p.K = hp.n_embd;
+    set_act(p, src, 2, src == ACT_PRO ? 0 : sp[l].fC, x, L.ffn_norm, L.ffn_norm_b);
+    if (hp.arch == ARCH_GPT2) {
+        p.gelu_tab = m->gelu_tab;
+        p.nseg = 1;
+        p.seg[0] = seg_of(L.up, PAIR_ADJ, EPI_GELU, h);
+        p.seg[0].bias = L.bup;
+        return p;
+    }
+    const bool moe = hp.n_expert > 0;
+    if (moe) {   // expert ids/weights: only MoE launches wait for them
+        p.sel = sel;
+        p.selw = selw;
+    }
+    p.nseg = moe ? 2 : 1;
+    for (int k = 0; k < p.nseg; ++k) {
+        p.seg[k] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
+        p.seg[k].B = L.up;
+        if (moe) p.seg[k].expA = p.seg[k].expB = k;
+    }
+    return p;
+}
+
+// FFN down + residual, in place (MoE, ACT_PRO only: the two experts' rows weighted and added)
+GemvParams Ctx::down_params(int l, ActSrc src) const {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    GemvParams p = gemv_base();
+    p.K = hp.n_ff;
+    set_act(p, src, 3, src == ACT_PRO ? 0 : sp[l].fD, h, nullptr, nullptr);
+    p.nseg = 1;
     if (hp.n_expert > 0) {
-        RouterParams rp{B.xa, L.ffn_norm, hp.eps, L.router, hp.n_embd, hp.n_expert, hp.n_expert_used, sel, selw, 0};
-        router(rp);
+        p.sel = sel;
+        p.selw = selw;
+        p.nslots = 2;
+        p.x[1] = h2;
+        p.seg[0] = seg_of(L.down, PAIR_AB, EPI_MOE_DOWN, x);
+        p.seg[0].expA = 0;
+        p.seg[0].expB = 1;
+        p.seg[0].actB = 1;
+    } else {
+        p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
+        p.seg[0].bias = L.bdown;
     }
-    // ---- FFN gate/up + SwiGLU ----
-    {
-        GemvParams p = base;
-        p.pro = PRO_RMSNORM;
-        p.x[0] = B.xa;
-        p.norm_w = L.ffn_norm;
-        p.K = hp.n_embd;
-        const int nsl = hp.n_expert > 0 ? 2 : 1;
-        if (hp.n_expert > 0) {   // expert ids/weights: only MoE launches wait for them
-            p.sel = sel;
-            p.selw = selw;
-        }
-        p.nseg = nsl;
-        for (int k = 0; k < nsl; ++k) {
-            p.seg[k] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, k == 0 ? B.h : B.h2);
-            p.seg[k].B = L.up;
-            if (hp.n_expert > 0) p.seg[k].expA = p.seg[k].expB = k;
-        }
-        gemv(p, 2);
-    }
-    // ---- FFN down + residual ----
-    {
-        GemvParams p = base;
-        p.pro = PRO_PLAIN;
-        p.x[0] = B.h;
-        p.K = hp.n_ff;
-        p.nseg = 1;
-        if (hp.n_expert > 0) {
-            p.sel = sel;
-            p.selw = selw;
-            p.nslots = 2;
-            p.x[1] = B.h2;
-            p.seg[0] = seg_of(L.down, PAIR_AB, EPI_MOE_DOWN, B.xf);
-            p.seg[0].expA = 0;
-            p.seg[0].expB = 1;
-            p.seg[0].actB = 1;
-        } else {
-            p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, B.xf);
-        }
-        p.seg[0].resid = B.xa;
-        gemv(p, 3);
-    }
+    p.seg[0].resid = x;
+    return p;
 }
 
-namespace {
-// activation formats a set of matrices reads: bit 0 Q8_K (k-quants), bit 1 Q8_0
-int act_fmt(std::initializer_list<int> types) {
-    int f = 0;
-    for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
-    return f;
+// final norm + output head of one residual row
+GemvParams Ctx::head_params(ActSrc src, const float* xrow) const {
+    GemvParams p = gemv_base();
+    p.K = m->hp.n_embd;
+    set_act(p, src, 4, sp_fH, xrow, m->output_norm, m->output_norm_b);
+    p.nseg = 1;
+    p.seg[0] = seg_of(m->output, PAIR_ADJ, EPI_STORE, logits);
+    return p;
 }
-}  // namespace
 
-// The streaming decode step's buffers (dense LLaMA; DESIGN.md §4 "dgemv"), and whether every
-// launch of the step has a compiled variant (GPT-2 keeps the gemv_kernel graph; MoE experts run on it).
+// ---- the profiling gate ----
+unsigned long long* Ctx::next_stamp() {   // (the r04 step's launches only)
+    if (!stamps || sp_ok || enq_launch >= kStampLaunches) return nullptr;
+    return stamps + (size_t)(enq_launch++) * kStampWgs * 8;
+}
+
+// One GEMV launch of the step being enqueued, on the kernel its activation form selects.  The
+// gate/up launch of prof_layer is segment 1 on its own (always eager) and carries the event pair.
+void Ctx::run_gemv(GemvParams p, int l, bool gate_up) {
+    const bool prof = gate_up && l == prof_layer;
+    if (prof) enq_seg = 1;
+    const bool timed = prof && seg_filter == 1;
+    const bool streaming = p.act_q8k || p.act_q80;
+    if (!streaming) p.stamps = next_stamp();
+    if (seg_on())
+        (streaming ? launch_dgemv : launch_gemv)(p, stream, timed ? prof_ev[0] : nullptr, timed ? prof_ev[1] : nullptr);
+    if (prof) enq_seg = 2;
+}
+
+void Ctx::run_attn(AttnParams a) {
+    a.stamps = next_stamp();
+    a.stamps2 = next_stamp();
+    if (seg_on()) launch_attn(a, stream);
+}
+
+// The routed experts of layer l on gemv_kernel (both steps), x in place
+void Ctx::enqueue_moe_ffn(int l) {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    RouterParams rp{x, L.ffn_norm, hp.eps, L.router, hp.n_embd, hp.n_expert, hp.n_expert_used, sel, selw, 0};
+    if (seg_on()) launch_router(rp, stream);
+    run_gemv(gate_up_params(l, ACT_PRO), l, true);
+    run_gemv(down_params(l, ACT_PRO));
+}
+
+// The streaming decode step's buffers (LLaMA; DESIGN.md §4 "dgemv"), and whether every launch of
+// the step has a compiled variant (GPT-2 keeps the gemv_kernel graph; MoE experts run on it).
 bool Ctx::sp_setup() {
     const HParams& hp = m->hp;
     if (hp.arch != ARCH_LLAMA) return false;
@@ -904,7 +506,7 @@ bool Ctx::sp_setup() {
     const int nl = hp.n_layer;
     sp.assign(nl, SpLayer{});
     sp_fH = act_fmt({m->output.type});
-    size_t act_max = 0;
+    size_t act_n = dv_act_bytes(hp.n_embd, sp_fH & 1, sp_fH >> 1), act_f = 0;
     for (int l = 0; l < nl; ++l) {
         const Layer& L = m->layers[l];
         SpLayer& b = sp[l];
@@ -913,442 +515,124 @@ bool Ctx::sp_setup() {
         b.fB = act_fmt({L.wo.type});
         b.fC = act_fmt({L.gate.type, L.up.type});
         b.fD = act_fmt({L.down.type});
-        act_max = std::max(act_max, dv_act_bytes(hp.n_embd, b.fB & 1, b.fB >> 1));
-    }
-    // every launch must have a variant: the step's parameter checks, dry
-    bool ok = true;
-    for (int l = 0; l < nl && ok; ++l) {
-        const Layer& L = m->layers[l];
-        GemvParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.K = hp.n_embd;
-        p.act_in = reinterpret_cast<const char*>(x);   // (any non-null pointer: the checks only)
-        p.act_q8k = sp[l].fA & 1;
-        p.act_q80 = sp[l].fA >> 1;
-        for (int g = 0; g < L.n_qkv && ok;) {
-            p.nseg = 0;
-            for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
-                if (p.nseg == 1 && !gemv_pair_supported(p.seg[0].A.type, L.qkv[g].type)) break;
-                p.seg[p.nseg++] = seg_of(L.qkv[g], PAIR_ADJ, EPI_QKV, q);
-            }
-            ok = dgemv_supported(p);
-        }
-        GemvParams w = p;
-        w.nseg = 1;
-        w.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, x);
-        w.act_q8k = sp[l].fB & 1;
-        w.act_q80 = sp[l].fB >> 1;
-        ok = ok && dgemv_supported(w);
-        if (moe) continue;
-        GemvParams gu = p;
-        gu.nseg = 1;
-        gu.seg[0] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, h);
-        gu.seg[0].B = L.up;
-        gu.act_q8k = sp[l].fC & 1;
-        gu.act_q80 = sp[l].fC >> 1;
-        ok = ok && L.gate.type == L.up.type && dgemv_supported(gu);
-        GemvParams d = p;
-        d.K = hp.n_ff;
-        d.nseg = 1;
-        d.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
-        d.act_q8k = sp[l].fD & 1;
-        d.act_q80 = sp[l].fD >> 1;
-        ok = ok && dgemv_supported(d);
-    }
-    GemvParams hd;
-    std::memset(&hd, 0, sizeof(hd));
-    hd.K = hp.n_embd;
-    hd.act_in = reinterpret_cast<const char*>(x);
-    hd.nseg = 1;
-    hd.seg[0] = seg_of(m->output, PAIR_ADJ, EPI_STORE, logits);
-    hd.act_q8k = sp_fH & 1;
-    hd.act_q80 = sp_fH >> 1;
-    ok = ok && dgemv_supported(hd);
-    if (!ok) {
-        sp.clear();
-        return false;
-    }
-    size_t act_n = 0, act_f = 0;
-    for (int l = 0; l < nl; ++l) {
-        const SpLayer& b = sp[l];
         for (int f : {b.fA, b.fB, b.fC}) act_n = std::max(act_n, dv_act_bytes(hp.n_embd, f & 1, f >> 1));
         act_f = std::max(act_f, dv_act_bytes(hp.n_ff, b.fD & 1, b.fD >> 1));
     }
-    act_n = std::max(act_n, dv_act_bytes(hp.n_embd, sp_fH & 1, sp_fH >> 1));
+    // The FFN down launch quantises h in every workgroup itself (no dv_quant launch before it) when
+    // that redundant work -- n_ff elements in each of n_embd / 8 workgroups -- is small: one launch
+    // fewer per layer wins for TinyLlama (1398-1409 vs 1341-1342 tok/s), loses 1 % for 7B
+    // (profiles/r06_hq_ab.txt).
+    sp_hq_down = (long long)hp.n_ff * hp.n_embd <= (1LL << 24);
+    // The same rule for the normed inputs of Q/K/V and gate/up (dense models): their workgroups
+    // build rms_norm(x) * norm_w and quantise it themselves, bit-identical to dv_quant_kernel. That
+    // removes two more launches per layer: TinyLlama 1407-1412 -> 1639-1653 tok/s, but 7B 637-643 ->
+    // 579-589 and Llama-3-8B 511 -> 470-480 (profiles/r06_nq_ab.txt).
+    sp_nq_in = sp_hq_down && !moe && hp.n_embd <= 8192;
     act_n = (act_n + 255) / 256 * 256;
     act_f = (act_f + 255) / 256 * 256;
-    MI_HIP(hipSetDevice(device));
-    MI_HIP(hipMalloc(&sp_mem, 4 * act_n + act_f));
-    MI_HIP(hipMemset(sp_mem, 0, 4 * act_n + act_f));
+    sp_mem = mem.dev<char>(4 * act_n + act_f, true);
     sp_act[0] = sp_mem;
     sp_act[1] = sp_mem + act_n;
     sp_act[2] = sp_mem + 2 * act_n;
     sp_act[4] = sp_mem + 3 * act_n;
     sp_act[3] = sp_mem + 4 * act_n;
-    return true;
+    // every launch must have a variant: the parameter blocks enqueue_step_sp will launch, dry
+    const ActSrc in = sp_nq_in ? ACT_RAW : ACT_QUANT;
+    bool ok = dgemv_supported(head_params(ACT_QUANT, nullptr));
+    for (int l = 0; l < nl && ok; ++l) {
+        const Layer& L = m->layers[l];
+        GemvParams qkv[3];
+        const int n = qkv_params(l, in, qkv);
+        for (int i = 0; i < n; ++i) ok = ok && dgemv_supported(qkv[i]);
+        ok = ok && dgemv_supported(wo_params(l, ACT_QUANT));
+        if (moe) continue;
+        ok = ok && L.gate.type == L.up.type && dgemv_supported(gate_up_params(l, in)) &&
+             dgemv_supported(down_params(l, sp_hq_down ? ACT_RAW : ACT_QUANT));
+    }
+    if (!ok) {   // the r04 step serves this model
+        mem.release(sp_mem);
+        for (char*& a : sp_act) a = nullptr;
+        sp.clear();
+    }
+    return ok;
 }
 
-// One batch-1 decode step on the streaming kernels (any context length): the embedding, per layer
+// The layers of one batch-1 decode step on the streaming kernels (any context length): per layer
 // dv_quant(rms_norm(x) * attn_norm) -> QKV -> attention (its output also quantised; past ATTN_SHORT
 // cells the split attention + attn_combine_quant) -> WO + residual -> dv_quant(rms_norm
-// * ffn_norm) -> gate/up -> dv_quant(h) (small models: inside the down launch) -> down + residual,
-// then the output head and the top-k.
-// Profiling segments as enqueue_step's (the gate/up launch of prof_layer carries the event pair).
+// * ffn_norm) -> gate/up -> dv_quant(h) -> down + residual; small models quantise inside the
+// consuming launch instead (sp_nq_in, sp_hq_down).
 void Ctx::enqueue_step_sp(bool with_logits) {
-    // The FFN down launch quantises h in every workgroup itself (no dv_quant launch before it) when
-    // that redundant work -- n_ff elements in each of n_embd / 8 workgroups -- is small: one launch
-    // fewer per layer wins for TinyLlama (1398-1409 vs 1341-1342 tok/s), loses 1 % for 7B
-    // (profiles/r06_hq_ab.txt).
     const HParams& hp = m->hp;
-    const bool hq_down = (long long)hp.n_ff * hp.n_embd <= (1LL << 24);
-    // The same rule for the normed inputs of Q/K/V and gate/up (dense models): their workgroups
-    // build rms_norm(x) * norm_w and quantise it themselves, bit-identical to dv_quant_kernel. That
-    // removes two more launches per layer: TinyLlama 1407-1412 -> 1639-1653 tok/s, but 7B 637-643 ->
-    // 579-589 and Llama-3-8B 511 -> 470-480 (profiles/r06_nq_ab.txt).
-    const bool nq_in = hq_down && hp.n_expert == 0 && hp.n_embd <= 8192;
     const bool moe = hp.n_expert > 0;
-    int seg = 0;
-    auto on = [&]() { return seg_filter < 0 || seg_filter == seg; };
-    const float theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    auto act = [&](int role, int fmt, int K, const float* norm_w) {
-        return ActOut{K, fmt & 1, fmt >> 1, sp_act[role], norm_w, hp.eps};
+    const ActSrc in = sp_nq_in ? ACT_RAW : ACT_QUANT;
+    auto quant = [&](const float* src, const ActOut& t) {
+        if (seg_on()) launch_dv_quant(src, t, stream);
     };
-    if (on()) {
-        EmbedParams ep{m->tok_embd, tokpos, x, hp.n_embd, m->pos_embd, 0, step_ctr};
-        launch_embed(ep, stream);
-        if (!nq_in) launch_dv_quant(x, act(0, sp[0].fA, hp.n_embd, m->layers[0].attn_norm), stream);
-    }
+    // the residual quantised for its next reader: layer l's Q/K/V, or (l == n_layer) the output head
+    auto quant_x_for = [&](int l) {
+        if (l == hp.n_layer) {
+            if (with_logits) quant(x, act_out(4, sp_fH, hp.n_embd, m->output_norm));
+        } else if (!sp_nq_in) {
+            quant(x, act_out(0, sp[l].fA, hp.n_embd, m->layers[l].attn_norm));
+        }
+    };
+    quant_x_for(0);
     for (int l = 0; l < hp.n_layer; ++l) {
-        const Layer& L = m->layers[l];
-        const SpLayer& b = sp[l];
-        __half* kl = kcache + (size_t)l * n_ctx * kv_dim;
-        __half* vl = vcache + (size_t)l * n_ctx * kv_dim;
-        GemvParams base;
-        std::memset(&base, 0, sizeof(base));
-        base.tokpos = tokpos;
-        base.cell_pos = cell_pos;
-        base.head_dim = hp.head_dim;
-        base.kv_dim = kv_dim;
-        base.nslots = 1;
-        base.K = hp.n_embd;
-        {   // Q/K/V + RoPE + KV append
-            GemvParams p = base;
-            p.act_in = nq_in ? nullptr : sp_act[0];
-            p.x[0] = nq_in ? x : nullptr;
-            p.norm_w = nq_in ? L.attn_norm : nullptr;
-            p.eps = hp.eps;
-            p.act_q8k = b.fA & 1;
-            p.act_q80 = b.fA >> 1;
-            p.theta_scale = theta_scale;
-            p.freq_scale = hp.freq_scale;
-            p.n_rot = hp.n_rot;
-            p.freq_factors = m->rope_freqs;
-            p.kcache = kl;
-            p.vcache = vl;
-            for (int g = 0; g < L.n_qkv;) {
-                p.nseg = 0;
-                for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
-                    if (p.nseg == 1 && !gemv_pair_supported(p.seg[0].A.type, L.qkv[g].type)) break;
-                    GemvSeg& sg = p.seg[p.nseg++];
-                    sg = seg_of(L.qkv[g], PAIR_ADJ, EPI_QKV, q);
-                    sg.nq = L.qkv_nq[g];
-                    sg.nk = L.qkv_nk[g];
-                }
-                if (on()) launch_dgemv(p, stream);
-            }
+        GemvParams qkv[3];
+        const int n = qkv_params(l, in, qkv);
+        for (int i = 0; i < n; ++i) run_gemv(qkv[i]);
+        run_attn(attn_params(l, true));
+        if (!attn_fused && seg_on())
+            launch_attn_combine_quant(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos,
+                                      act_out(1, sp[l].fB, hp.n_embd, nullptr), stream);
+        run_gemv(wo_params(l, ACT_QUANT));
+        if (moe) {
+            enqueue_moe_ffn(l);
+        } else {
+            if (!sp_nq_in) quant(x, act_out(2, sp[l].fC, hp.n_embd, m->layers[l].ffn_norm));
+            run_gemv(gate_up_params(l, in), l, true);
+            if (!sp_hq_down) quant(h, act_out(3, sp[l].fD, hp.n_ff, nullptr));
+            run_gemv(down_params(l, sp_hq_down ? ACT_RAW : ACT_QUANT));
         }
-        {   // attention, its output quantised for WO: <= ATTN_SHORT cells one fused launch (which
-            // quantises); past that the split launch(es) of the r04 step, then the splits summed in
-            // split order and quantised (attn_combine_quant_kernel)
-            AttnParams a{q, kl, vl, tokpos, cell_pos, attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv,
-                         hp.head_dim, kv_dim, (int)n_ctx, kq_scale};
-            if (attn_fused) {
-                a.fused = 1;
-                a.act_out = act(1, b.fB, hp.n_embd, nullptr);
-                if (on()) launch_attn(a, stream);
-            } else {
-                a.fused = 0;
-                a.xflags = attn_xflags;
-                a.xmax = attn_xmax;
-                a.xsum = attn_xsum;
-                a.step = step_ctr;
-                a.layer = l;
-                a.n_layer = hp.n_layer;
-                a.xerr = d_attn_xerr;
-                a.long_share = dev_chain(device).nctx.load();
-                a.long_off = attn_long_off ? 1 : 0;
-                if (on()) {
-                    launch_attn(a, stream);
-                    launch_attn_combine_quant(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos,
-                                              act(1, b.fB, hp.n_embd, nullptr), stream);
-                }
-            }
-        }
-        {   // output projection + residual (in place), then rms_norm(x) * ffn_norm quantised
-            GemvParams p = base;
-            p.act_in = sp_act[1];
-            p.act_q8k = b.fB & 1;
-            p.act_q80 = b.fB >> 1;
-            p.nseg = 1;
-            p.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, x);
-            p.seg[0].resid = x;
-            if (on()) {
-                launch_dgemv(p, stream);
-                if (!moe && !nq_in) launch_dv_quant(x, act(2, b.fC, hp.n_embd, L.ffn_norm), stream);
-            }
-        }
-        if (moe) {   // the routed experts on the r04 step's kernels (layer_ops' MoE FFN), x in place
-            GemvParams gb = base;
-            gb.eps = hp.eps;
-            RouterParams rp{x, L.ffn_norm, hp.eps, L.router, hp.n_embd, hp.n_expert, hp.n_expert_used, sel, selw, 0};
-            if (on()) launch_router(rp, stream);
-            GemvParams p = gb;
-            p.pro = PRO_RMSNORM;
-            p.x[0] = x;
-            p.norm_w = L.ffn_norm;
-            p.sel = sel;
-            p.selw = selw;
-            p.nseg = 2;
-            for (int k = 0; k < 2; ++k) {
-                p.seg[k] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
-                p.seg[k].B = L.up;
-                p.seg[k].expA = p.seg[k].expB = k;
-            }
-            if (l == prof_layer) seg = 1;
-            const bool timed = l == prof_layer && seg_filter == 1;
-            if (on()) launch_gemv(p, stream, timed ? prof_ev[0] : nullptr, timed ? prof_ev[1] : nullptr);
-            if (l == prof_layer) seg = 2;
-            GemvParams d = gb;
-            d.pro = PRO_PLAIN;
-            d.x[0] = h;
-            d.x[1] = h2;
-            d.nslots = 2;
-            d.K = hp.n_ff;
-            d.sel = sel;
-            d.selw = selw;
-            d.nseg = 1;
-            d.seg[0] = seg_of(L.down, PAIR_AB, EPI_MOE_DOWN, x);
-            d.seg[0].expA = 0;
-            d.seg[0].expB = 1;
-            d.seg[0].actB = 1;
-            d.seg[0].resid = x;
-            if (on()) {
-                launch_gemv(d, stream);
-                if (l + 1 < hp.n_layer)
-                    launch_dv_quant(x, act(0, sp[l + 1].fA, hp.n_embd, m->layers[l + 1].attn_norm), stream);
-                else if (with_logits)
-                    launch_dv_quant(x, act(4, sp_fH, hp.n_embd, m->output_norm), stream);
-            }
-            continue;
-        }
-        {   // FFN gate/up + SwiGLU, then h quantised
-            GemvParams p = base;
-            p.act_in = nq_in ? nullptr : sp_act[2];
-            p.x[0] = nq_in ? x : nullptr;
-            p.norm_w = nq_in ? L.ffn_norm : nullptr;
-            p.eps = hp.eps;
-            p.act_q8k = b.fC & 1;
-            p.act_q80 = b.fC >> 1;
-            p.nseg = 1;
-            p.seg[0] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, h);
-            p.seg[0].B = L.up;
-            if (l == prof_layer) seg = 1;
-            const bool timed = l == prof_layer && seg_filter == 1;
-            if (on()) launch_dgemv(p, stream, timed ? prof_ev[0] : nullptr, timed ? prof_ev[1] : nullptr);
-            if (l == prof_layer) seg = 2;
-            if (on() && !hq_down) launch_dv_quant(h, act(3, b.fD, hp.n_ff, nullptr), stream);
-        }
-        {   // FFN down + residual (in place), then the next layer's (or the output head's) input quantised
-            GemvParams p = base;
-            p.act_in = hq_down ? nullptr : sp_act[3];
-            p.x[0] = h;
-            p.K = hp.n_ff;
-            p.act_q8k = b.fD & 1;
-            p.act_q80 = b.fD >> 1;
-            p.nseg = 1;
-            p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
-            p.seg[0].resid = x;
-            const bool next = (l + 1 < hp.n_layer && !nq_in) || (l + 1 == hp.n_layer && with_logits);
-            const ActOut nx = l + 1 < hp.n_layer ? act(0, sp[l + 1].fA, hp.n_embd, m->layers[l + 1].attn_norm)
-                                                 : act(4, sp_fH, hp.n_embd, m->output_norm);
-            if (on()) {
-                launch_dgemv(p, stream);
-                if (next) launch_dv_quant(x, nx, stream);
-            }
-        }
-    }
-    if (with_logits && on()) {   // the output head, the top-k
-        GemvParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.K = hp.n_embd;
-        p.act_in = sp_act[4];
-        p.act_q8k = sp_fH & 1;
-        p.act_q80 = sp_fH >> 1;
-        p.nseg = 1;
-        p.seg[0] = seg_of(m->output, PAIR_ADJ, EPI_STORE, logits);
-        launch_dgemv(p, stream);
-        TopkParams tp{logits, hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
-        launch_topk(tp, stream);
+        quant_x_for(l + 1);
     }
 }
 
-// One decode step for the token in tokpos (batch 1): the llm_build_llama graph.
-// With seg_filter >= 0 only the ops of that profiling segment are enqueued
-// (0: up to layer prof_layer's FFN gate/up, 1: that launch, 2: the rest).
+// One decode step for the token in tokpos (batch 1): the llm_build_llama / llm_build_gpt2 graph,
+// on the streaming kernels (sp_ok) or on gemv_kernel.
 void Ctx::enqueue_step(bool with_logits) {
     const HParams& hp = m->hp;
-    if (sp_ok) {   // dense LLaMA at any context (past 512 cells: 474-481 vs 429-435 tok/s at 3968, r06)
-        enqueue_step_sp(with_logits);
-        return;
-    }
-    int seg = 0;
-    int n_launch = 0;   // diagnostic stamps (MI_STAMPS builds only): one slab per launch
-    auto stamp = [&]() -> unsigned long long* {
-        if (!stamps || n_launch >= kStampLaunches) return nullptr;
-        return stamps + (size_t)(n_launch++) * kStampWgs * 8;
-    };
-    auto on = [&]() { return seg_filter < 0 || seg_filter == seg; };
+    enq_seg = 0;
+    enq_launch = 0;
     EmbedParams ep{m->tok_embd, tokpos, x, hp.n_embd, m->pos_embd, hp.arch == ARCH_GPT2 ? 1 : 0, step_ctr};
-    if (on()) launch_embed(ep, stream);
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    for (int l = 0; l < hp.n_layer; ++l) {
-        if (hp.arch == ARCH_GPT2) {   // llm_build_gpt2: LayerNorm, biases, no RoPE, GELU MLP
-            GemvParams base;
-            std::memset(&base, 0, sizeof(base));
-            base.tokpos = tokpos;
-            base.cell_pos = cell_pos;
-            base.head_dim = hp.head_dim;
-            base.kv_dim = kv_dim;
-            base.eps = hp.eps;
-            base.nslots = 1;
-            enqueue_layer_gpt2(l, base, kcache + (size_t)l * n_ctx * kv_dim, vcache + (size_t)l * n_ctx * kv_dim,
-                               kq_scale, stamp);
-            continue;
+    if (seg_on()) launch_embed(ep, stream);
+    if (sp_ok) {
+        enqueue_step_sp(with_logits);
+    } else {
+        for (int l = 0; l < hp.n_layer; ++l) {
+            GemvParams qkv[3];
+            const int n = qkv_params(l, ACT_PRO, qkv);
+            for (int i = 0; i < n; ++i) run_gemv(qkv[i]);
+            run_attn(attn_params(l, false));
+            run_gemv(wo_params(l, ACT_PRO));
+            if (hp.n_expert > 0) {
+                enqueue_moe_ffn(l);
+            } else {
+                run_gemv(gate_up_params(l, ACT_PRO), l, true);
+                run_gemv(down_params(l, ACT_PRO));
+            }
         }
-        const LayerBufs B{x, q, part_o, x, h, h2, x};
-        layer_ops(
-            l, B,
-            [&](const GemvParams& p0, int role) {
-                GemvParams p = p0;
-                p.stamps = stamp();
-                if (role != 2) {
-                    if (on()) launch_gemv(p, stream);
-                    return;
-                }
-                if (l == prof_layer) seg = 1;
-                // the profiled launch (segment 1, always eager) carries the event pair
-                const bool timed = l == prof_layer && seg_filter == 1;
-                if (on()) launch_gemv(p, stream, timed ? prof_ev[0] : nullptr, timed ? prof_ev[1] : nullptr);
-                if (l == prof_layer) seg = 2;
-            },
-            [&](const AttnParams& a0) {
-                AttnParams a = a0;
-                a.stamps = stamp();
-                a.stamps2 = stamp();
-                if (on()) launch_attn(a, stream);
-            },
-            [&](const RouterParams& rp) {
-                if (on()) launch_router(rp, stream);
-            });
     }
-    if (with_logits && on()) enqueue_output(x, stamp());
+    if (with_logits && seg_on()) enqueue_output(sp_ok ? ACT_QUANT : ACT_PRO, x, next_stamp());
 }
 
-// One GPT-2 block (llm_build_gpt2, src/llama-model.cpp b5187) of the decode step:
-//   cur = LayerNorm(x)*attn_norm + attn_norm_b -> wqkv + bqkv -> Q / K / V (no RoPE) -> KV append
-//   attention -> wo + bo + x (residual);  LayerNorm(x)*ffn_norm + ffn_norm_b -> up + bup -> GELU
-//   -> down + bdown + x
-void Ctx::enqueue_layer_gpt2(int l, const GemvParams& base, __half* kl, __half* vl, float kq_scale,
-                             const std::function<unsigned long long*()>& stamp) {
-    const HParams& hp = m->hp;
-    const Layer& L = m->layers[l];
-    auto on = [&]() { return seg_filter < 0; };
-    {
-        GemvParams p = base;
-        p.pro = PRO_LAYERNORM;
-        p.x[0] = x;
-        p.norm_w = L.attn_norm;
-        p.norm_b = L.attn_norm_b;
-        p.K = hp.n_embd;
-        p.n_rot = 0;
-        p.kcache = kl;
-        p.vcache = vl;
-        p.nseg = 1;
-        p.seg[0] = seg_of(L.qkv[0], PAIR_ADJ, EPI_QKV, q);
-        p.seg[0].nq = L.qkv_nq[0];
-        p.seg[0].nk = L.qkv_nk[0];
-        p.seg[0].bias = L.bqkv;
-        p.stamps = stamp();
-        if (on()) launch_gemv(p, stream);
-    }
-    {
-        AttnParams a{q, kl, vl, tokpos, cell_pos, attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv, hp.head_dim,
-                     kv_dim, (int)n_ctx, kq_scale};
-        a.fused = attn_fused;
-        a.stamps = stamp();
-        a.stamps2 = stamp();
-        if (on()) launch_attn(a, stream);
-    }
-    {
-        GemvParams p = base;
-        p.pro = PRO_ATTN;
-        p.attn = AttnPartials{part_o, hp.n_head, hp.head_dim};
-        p.attn_nsplit = attn_fused ? 1 : 0;
-        p.K = hp.n_embd;
-        p.nseg = 1;
-        p.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, x);
-        p.seg[0].resid = x;
-        p.seg[0].bias = L.bo;
-        p.stamps = stamp();
-        if (on()) launch_gemv(p, stream);
-    }
-    {
-        GemvParams p = base;
-        p.pro = PRO_LAYERNORM;
-        p.x[0] = x;
-        p.norm_w = L.ffn_norm;
-        p.norm_b = L.ffn_norm_b;
-        p.K = hp.n_embd;
-        p.gelu_tab = m->gelu_tab;
-        p.nseg = 1;
-        p.seg[0] = seg_of(L.up, PAIR_ADJ, EPI_GELU, h);
-        p.seg[0].bias = L.bup;
-        p.stamps = stamp();
-        if (on()) launch_gemv(p, stream);
-    }
-    {
-        GemvParams p = base;
-        p.pro = PRO_PLAIN;
-        p.x[0] = h;
-        p.K = hp.n_ff;
-        p.nseg = 1;
-        p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
-        p.seg[0].resid = x;
-        p.seg[0].bias = L.bdown;
-        p.stamps = stamp();
-        if (on()) launch_gemv(p, stream);
-    }
-}
-
-// final RMSNorm (GPT-2: LayerNorm) + output head GEMV of one residual row, then the top-k
-void Ctx::enqueue_output(const float* xrow, unsigned long long* stamps_slab) {
-    const HParams& hp = m->hp;
-    GemvParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.pro = hp.arch == ARCH_GPT2 ? PRO_LAYERNORM : PRO_RMSNORM;
-    p.norm_b = m->output_norm_b;
-    p.nslots = 1;
-    p.x[0] = xrow;
-    p.norm_w = m->output_norm;
-    p.eps = hp.eps;
-    p.K = hp.n_embd;
-    p.tokpos = tokpos;
-    p.nseg = 1;
-    p.seg[0] = seg_of(m->output, PAIR_ADJ, EPI_STORE, logits);
+// the output head of one residual row (ACT_QUANT: quantised at sp_act[4] already), then the top-k
+void Ctx::enqueue_output(ActSrc src, const float* xrow, unsigned long long* stamps_slab) {
+    GemvParams p = head_params(src, xrow);
     p.stamps = stamps_slab;
-    launch_gemv(p, stream);
-    TopkParams tp{logits, hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
+    (src == ACT_PRO ? launch_gemv : launch_dgemv)(p, stream, nullptr, nullptr);
+    TopkParams tp{logits, m->hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
     launch_topk(tp, stream);
 }
 
@@ -1478,7 +762,7 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
                 proj(p, hb, hp.n_ff, nullptr, true);
             }
         }
-        if (c0 + nt == n) enqueue_output(xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+        if (c0 + nt == n) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
     logits_valid = true;
 }
@@ -1754,7 +1038,7 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                 launch_topk(tp, stream);
             }
         } else if (c0 + nt == n) {
-            enqueue_output(xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+            enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
         }
     }
     logits_valid = true;
@@ -1788,7 +1072,7 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
     } else {
         // the last residual parts into xb (the next chunk, or the output, reads it)
         if (pend_k) launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream);
-        if (last) enqueue_output(xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+        if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
 }
 
@@ -1897,9 +1181,8 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     out_rows = 0;
     topk_row = -1;
     if (all && logits_all_cap < n) {   // every token's logits: [n_batch][n_vocab], allocated once
-        if (logits_all) MI_HIP(hipFree(logits_all));
-        logits_all = nullptr;
-        MI_HIP(hipMalloc(&logits_all, (size_t)n_batch * m->hp.n_vocab * sizeof(float)));
+        mem.release(logits_all);
+        logits_all = mem.dev<float>((size_t)n_batch * m->hp.n_vocab);
         logits_all_cap = (int)n_batch;
     }
     // prompt ingestion through the batched GEMM when the context stays within the fused
@@ -1930,7 +1213,7 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
         MI_HIP(hipMemcpyAsync(tokpos, hp, 4 * sizeof(int), hipMemcpyHostToDevice, stream));
         if (last && prof_layer >= 0 && prof_layer < m->hp.n_layer) {
             for (int k = 0; k < 2; ++k)
-                if (!prof_ev[k]) MI_HIP(hipEventCreate(&prof_ev[k]));
+                if (!prof_ev[k]) prof_ev[k] = mem.event();
             // graph up to the profiled launch, the launch itself eagerly with
             // hipExtLaunchKernel start/stop events, graph for the rest
             for (int k = 0; k < 3; ++k) {
@@ -2040,13 +1323,13 @@ int Ctx::gather_rows(int row0, int nrows, const int32_t* ids, int k, float* out)
         if (ids[i] < 0 || ids[i] >= m->hp.n_vocab) throw Error("gather_rows: id out of range");
     MI_HIP(hipSetDevice(device));
     if (n > grows_cap) {
-        if (grows_ids) hipFree(grows_ids);
-        if (grows_out) hipFree(grows_out);
-        if (h_grows) hipHostFree(h_grows);
-        grows_ids = nullptr; grows_out = nullptr; h_grows = nullptr; grows_cap = 0;
-        MI_HIP(hipMalloc(&grows_ids, n * sizeof(int)));
-        MI_HIP(hipMalloc(&grows_out, n * sizeof(float)));
-        MI_HIP(hipHostMalloc(&h_grows, n * sizeof(float)));
+        mem.release(grows_ids);
+        mem.release(grows_out);
+        mem.release(h_grows);
+        grows_cap = 0;
+        grows_ids = mem.dev<int>(n);
+        grows_out = mem.dev<float>(n);
+        h_grows = mem.host<float>(n);
         grows_cap = n;
     }
     const float* base = out_rows > 0 ? logits_all + (size_t)row0 * m->hp.n_vocab : logits;
@@ -2089,7 +1372,7 @@ int Ctx::kv_seq_rm(int p0, int p1) {
     if (!prefix) {
         MI_HIP(hipSetDevice(device));
         const HParams& hp = m->hp;
-        if (!kv_scratch) MI_HIP(hipMalloc(&kv_scratch, (size_t)hp.n_layer * n_ctx * kv_dim * sizeof(__half)));
+        if (!kv_scratch) kv_scratch = mem.dev<__half>((size_t)hp.n_layer * n_ctx * kv_dim);
         MI_HIP(hipMemcpyAsync(move_src, keep.data(), keep.size() * sizeof(int), hipMemcpyHostToDevice, stream));
         launch_kv_move(kcache, hp.n_layer, n_ctx, kv_dim, move_src, (int)keep.size(), kv_scratch, stream);
         launch_kv_move(vcache, hp.n_layer, n_ctx, kv_dim, move_src, (int)keep.size(), kv_scratch, stream);

@@ -1,5 +1,5 @@
-// Engine internals: GGUF parsing, the device-resident model and the decode
-// context.  The public surface is the C ABI in include/mi_engine.h.
+// Engine internals: GGUF parsing and the device-resident model (model.cpp), the decode
+// context (engine.cpp).  The public surface is the C ABI in include/mi_engine.h.
 #pragma once
 #include <mutex>
 #include <cstdlib>
@@ -7,7 +7,6 @@
 #include "kernels.h"
 #include "mi_engine.h"
 
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -124,12 +123,44 @@ struct Model {
 // ------------------------------------------------------------- context ----
 int dev_chain_contexts(int device);   // live contexts on the device
 
+// A decode launch's segment of one matrix (dense: no experts, no bias, no residual yet)
+GemvSeg seg_of(const QMat& A, int pair, int epi, float* out);
+
+// Owner of a context's device buffers, pinned host buffers, stream and events: one hipMalloc /
+// hipHostMalloc per buffer, every one recorded and released by the destructor -- which, as Ctx's
+// first member, also runs when Ctx's constructor throws part-way.
+struct CtxMem {
+    std::vector<void*> dev_ptrs, host_ptrs;
+    std::vector<hipEvent_t> events;
+    hipStream_t stream_ = nullptr;
+    CtxMem() = default;
+    CtxMem(const CtxMem&) = delete;
+    CtxMem& operator=(const CtxMem&) = delete;
+    ~CtxMem();
+    void* dev_bytes(size_t bytes, bool zero);
+    void* host_bytes(size_t bytes, unsigned flags);
+    template <class T> T* dev(size_t n, bool zero = false) { return static_cast<T*>(dev_bytes(n * sizeof(T), zero)); }
+    // pinned host memory (flags: hipHostMallocMapped | hipHostMallocCoherent for kernel-written buffers)
+    template <class T> T* host(size_t n, unsigned flags = hipHostMallocDefault) {
+        return static_cast<T*>(host_bytes(n * sizeof(T), flags));
+    }
+    // frees one buffer of either kind now and nulls p (null: nothing); for buffers that grow
+    template <class T> void release(T*& p) {
+        free_one(p);
+        p = nullptr;
+    }
+    void free_one(void* p);
+    hipStream_t stream();    // the context's stream, created on the first call
+    hipEvent_t event();
+};
+
 struct Ctx {
+    CtxMem mem;                         // first: released last, and on a throwing constructor
     Model* m = nullptr;
     int device = 0;
     uint32_t n_ctx = 0, n_batch = 0, n_ubatch = 0;
     int kv_dim = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;       // mem's
 
     // device buffers
     __half* kcache = nullptr;           // [n_layer][n_ctx][kv_dim]
@@ -171,14 +202,14 @@ struct Ctx {
     float* ub_dT = nullptr;             // [kmax/256][UB_MAX]
     int8_t* ub_bsb = nullptr;           // [UB_MAX][kmax/256][16]
     float2* ub_rope = nullptr;          // [UB_MAX][n_rot/2]
-    float* ub_part = nullptr;           // [2][UB_MAX][n_embd] split-K partials (dense models; MI_MMQ_KSPLIT=0: off)
+    float* ub_part = nullptr;           // [2][UB_MAX][n_embd] split-K partials (dense models)
     // short batches (<= mmqs_max tokens, dense models): the split-K streaming GEMM's partial sums
     // [kp][ntok][rows] of every launch (mmq.hip mmqs; MI_MMQS_MAX=0: off)
     float* ub_spart = nullptr;
     int mmqs_max = 0;
     bool out_mmq = false;               // the output head is mmq32-capable (batched logits of every token)
     bool ub_q80 = false;                // the layer matrices are Q8_0: Q8_0 batch activations
-    bool attn_mfma = false;             // batch attention on f16 MFMA (attn_mfma.hip); MI_ATTN_VALU=1: VALU kernel
+    bool attn_mfma = false;             // batch attention on f16 MFMA (attn_mfma.hip)
     // MI_OUT_ALL: logits of every token of the last decode call, [out_rows][n_vocab]
     float* logits_all = nullptr;
     int logits_all_cap = 0;
@@ -227,33 +258,54 @@ struct Ctx {
 
     static constexpr int kTokRing = 8192;
 
-    // streaming decode step (dgemv.hip) for dense LLaMA contexts within ATTN_SHORT cells: every GEMV
-    // reads its activation quantised -- WO's from the attention kernel, the others' from a
-    // dv_quant launch (rms_norm'd x, or h) -- from sp_act[role]
+    // streaming decode step (dgemv.hip) for LLaMA contexts of any length whose every launch has a
+    // compiled variant (MoE: the attention half; the experts keep gemv_kernel): a GEMV reads its
+    // activation quantised from sp_act[role] -- WO's written by the attention kernel (past
+    // ATTN_SHORT cells by attn_combine_quant), the others' by a dv_quant launch (rms_norm'd x, or
+    // h) -- or, in small models, quantises the fp32 row itself (sp_hq_down, sp_nq_in)
     struct SpLayer {
         int fA, fB, fC, fD;             // activation formats of QKV, WO, gate/up, down: bit 0 Q8_K, bit 1 Q8_0
     };
-    bool sp_ok = false;                 // false: the gemv_kernel graph (GPT-2)
+    bool sp_ok = false;                 // false: the r04 step on gemv_kernel (GPT-2, geometries sp_setup rejects)
     std::vector<SpLayer> sp;
     int sp_fH = 0;                      // the output head's activation formats
+    bool sp_hq_down = false;            // FFN down quantises h in-launch (no dv_quant launch before it)
+    bool sp_nq_in = false;              // Q/K/V and gate/up norm and quantise x in-launch
     char* sp_mem = nullptr;
     char* sp_act[5] = {};               // QKV, WO, gate/up, down, head inputs
     bool sp_setup();
     void enqueue_step_sp(bool with_logits);
-    struct LayerBufs {
-        const float* x_in;              // residual stream into the layer
-        float *q, *po, *xa, *h, *h2, *xf;   // q, attention output, residual after WO, FFN (2nd expert), after down
+
+    // ---- the parameter block of each decode launch, built in one place (engine.cpp) ----
+    // How a GEMV's activation arrives:
+    enum ActSrc {
+        ACT_PRO,                        // fp32 row through gemv_kernel's prologue (the r04 step)
+        ACT_QUANT,                      // quantised at sp_act[role] (dgemv)
+        ACT_RAW,                        // fp32 row, normed and quantised inside the dgemv launch
     };
-    void layer_ops(int l, const LayerBufs& B, const std::function<void(const GemvParams&, int)>& gemv,
-                   const std::function<void(const AttnParams&)>& attn,
-                   const std::function<void(const RouterParams&)>& router);
+    GemvParams gemv_base() const;
+    int qkv_params(int l, ActSrc src, GemvParams out[3]) const;   // 1-3 launches of the layer's row groups
+    GemvParams wo_params(int l, ActSrc src) const;
+    GemvParams gate_up_params(int l, ActSrc src) const;
+    GemvParams down_params(int l, ActSrc src) const;
+    GemvParams head_params(ActSrc src, const float* xrow) const;
+    AttnParams attn_params(int l, bool quant_out) const;
+    ActOut act_out(int role, int fmt, int K, const float* norm_w) const;
+    void set_act(GemvParams& p, ActSrc src, int role, int fmt, const float* xin, const float* norm_w,
+                 const float* norm_b) const;
+    // ---- the profiling gate of the step being enqueued: with seg_filter >= 0 only the launches of
+    // that segment go out (0: up to layer prof_layer's FFN gate/up, 1: that launch, 2: the rest)
+    int enq_seg = 0, enq_launch = 0;
+    bool seg_on() const { return seg_filter < 0 || seg_filter == enq_seg; }
+    unsigned long long* next_stamp();   // MI_STAMPS builds: one slab per gemv_kernel / attention launch
+    void run_gemv(GemvParams p, int l = -1, bool gate_up = false);
+    void run_attn(AttnParams a);
+    void enqueue_moe_ffn(int l);
 
     Ctx(Model* model, uint32_t n_ctx, uint32_t n_batch, uint32_t n_ubatch);
     ~Ctx();
     void enqueue_step(bool with_logits);
-    void enqueue_output(const float* xrow, unsigned long long* stamps_slab);
-    void enqueue_layer_gpt2(int l, const GemvParams& base, __half* kl, __half* vl, float kq_scale,
-                            const std::function<unsigned long long*()>& stamp);
+    void enqueue_output(ActSrc src, const float* xrow, unsigned long long* stamps_slab);
     void decode_batch(const int32_t* tokens, int n);
     void decode_ubatch(const int32_t* tokens, int n, bool all);
     // the layers of one short physical batch on mmqs; returns the residual parts still to add

@@ -1290,12 +1290,13 @@ static AttnQuantPick attn_quant_pick(int n_head, int n_head_kv, int head_dim) {
 
 static AttnFn attn_dec_pick(const AttnQuantPick& k, int r, int head_dim, int& nwv) {
     nwv = 4;
-    if (!(k.hg > 1 || k.qsplit || r == 1)) return nullptr;
+    if (!(k.qsplit || r == 1)) {   // a group of R > 1 q heads: the fused kernel, one group per workgroup
+        if (k.hg > 1) throw Error("attn: the decode kernel's groups serve one q head each");
+        return nullptr;
+    }
+    // (one q head per group: hg = 256 / head_dim)
     switch (head_dim * 8 + k.hg) {
-    case 128 * 8 + 1: nwv = 16; return attn_dec_kernel<16, 1, 16>;
     case 128 * 8 + 2: nwv = 8; return attn_dec_kernel<16, 2, 8>;
-    case 64 * 8 + 1: nwv = 16; return attn_dec_kernel<8, 1, 16>;
-    case 64 * 8 + 2: nwv = 8; return attn_dec_kernel<8, 2, 8>;
     case 64 * 8 + 4: nwv = 4; return attn_dec_kernel<8, 4, 4>;
     default: return nullptr;
     }

@@ -3,7 +3,7 @@
 Blama serves concurrent verification sessions; batch-1 decode does not shard,
 so every GPU holds a full replica and runs its own sessions.  What is shared is
 the load: rank 0 parses the GGUF and repacks the weights into its device arena
-(engine.cpp Model::load), every other rank allocates an identical arena from
+(model.cpp Model::load), every other rank allocates an identical arena from
 the GGUF header alone (mi_model_params.no_upload) and receives the bytes with
 one RCCL broadcast over xGMI (torch.distributed "nccl" == RCCL on ROCm) --
 a device-to-device copy instead of N host->device uploads and N repacks.

@@ -308,3 +308,32 @@ def test_gqa16_layout_decode_and_short_batch(gpu_lib):
         a.close()
         b.close()
         m.close()
+
+
+# The decode step each tiny config takes: 1 = the streaming step (dgemv), 0 = the gemv_kernel step.
+# The oracle-tolerance tests pass on either step, so a model silently moving to the other one would
+# go unnoticed without this table.  tiny-gqa16 and tiny-q8_0 (head_dim 32) have no quantising
+# attention kernel for their head geometry; GPT-2 has no streaming step.
+DECODE_PATH = {
+    "tiny-q4_k_m": 1,
+    "tiny-q5_k_m": 1,
+    "tiny-q6_k": 1,
+    "tiny-q8_0": 0,
+    "tiny1-q4_k_m": 1,
+    "tiny-moe-q5_k_m": 1,
+    "tiny-gqa16-q4_k_m": 0,
+    "tiny-gpt2-q6_k": 0,
+    "tiny-gpt2-q8_0": 0,
+}
+
+
+@pytest.mark.parametrize("cfg_name", sorted(n for n in synthetic.CONFIGS if n.startswith(("tiny-", "tiny1-"))))
+def test_decode_path_per_config(gpu_lib, cfg_name):
+    assert cfg_name in DECODE_PATH, "a new tiny config: add its decode step to the table"
+    m = engine.Model(synthetic.build_gguf(synthetic.CONFIGS[cfg_name], seed=5))
+    ctx = engine.Context(m, n_ctx=64)
+    try:
+        assert ctx.decode_path() == DECODE_PATH[cfg_name]
+    finally:
+        ctx.close()
+        m.close()
