@@ -190,6 +190,7 @@ int32_t mi_model_n_head(const mi_model* m) { return m ? m->impl.hp.n_head : -1; 
 int32_t mi_model_n_head_kv(const mi_model* m) { return m ? m->impl.hp.n_head_kv : -1; }
 int32_t mi_model_n_ff(const mi_model* m) { return m ? m->impl.hp.n_ff : -1; }
 int32_t mi_model_n_expert(const mi_model* m) { return m ? m->impl.hp.n_expert : -1; }
+float mi_model_rope_freq_scale(const mi_model* m) { return m ? m->impl.hp.freq_scale : 0.0f; }
 int32_t mi_model_token_bos(const mi_model* m) { return m ? m->impl.bos : -1; }
 int32_t mi_model_token_eos(const mi_model* m) { return m ? m->impl.eos : -1; }
 int32_t mi_model_add_bos(const mi_model* m) { return m ? (m->impl.add_bos ? 1 : 0) : -1; }

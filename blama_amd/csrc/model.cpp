@@ -245,8 +245,15 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     hp.eps = (float)gguf.get_float(key(hp.arch == ARCH_GPT2 ? "attention.layer_norm_epsilon"
                                                              : "attention.layer_norm_rms_epsilon"), 1e-5);
     hp.rope_base = (float)gguf.get_float(key("rope.freq_base"), 10000.0);
-    const double fs = gguf.get_float(key("rope.scale_linear"), 0.0);
-    hp.freq_scale = fs > 0.0 ? (float)(1.0 / fs) : 1.0f;
+    // llama.cpp b5187 (llama-model.cpp load_hparams): the factor is rope.scaling.factor, else the
+    // older rope.scale_linear; rope.scaling.type (default linear) picks the mode.  The kernels
+    // implement ggml_rope_ext with ext_factor 0 and mscale 1 only: linear scaling or none.
+    const double fs = gguf.get_float(key("rope.scaling.factor"), gguf.get_float(key("rope.scale_linear"), 0.0));
+    const std::string rope_type = gguf.get_str(key("rope.scaling.type"), "linear");
+    if (rope_type != "linear" && rope_type != "none")
+        throw Error("unsupported " + key("rope.scaling.type") + " '" + rope_type +
+                    "' (this backend implements linear RoPE scaling only)");
+    hp.freq_scale = (rope_type == "linear" && fs > 0.0) ? (float)(1.0 / fs) : 1.0f;
     hp.n_expert = (int)gguf.get_int(key("expert_count"), 0);
     hp.n_expert_used = (int)gguf.get_int(key("expert_used_count"), 0);
     if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0) throw Error("GGUF: missing llama hparams");

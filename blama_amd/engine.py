@@ -46,6 +46,7 @@ _SIGS = {
     "mi_model_n_head_kv": (C.c_int32, [_P]),
     "mi_model_n_ff": (C.c_int32, [_P]),
     "mi_model_n_expert": (C.c_int32, [_P]),
+    "mi_model_rope_freq_scale": (C.c_float, [_P]),
     "mi_model_token_bos": (C.c_int32, [_P]),
     "mi_model_token_eos": (C.c_int32, [_P]),
     "mi_model_add_bos": (C.c_int32, [_P]),
@@ -163,6 +164,7 @@ class Model:
         self.n_head_kv = L.mi_model_n_head_kv(h)
         self.n_ff = L.mi_model_n_ff(h)
         self.n_expert = L.mi_model_n_expert(h)
+        self.rope_freq_scale = float(L.mi_model_rope_freq_scale(h))
 
     def close(self):
         if getattr(self, "h", None):

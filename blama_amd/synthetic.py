@@ -41,10 +41,21 @@ class LlamaConfig:
     n_expert: int = 0
     n_expert_used: int = 0
     arch: str = "llama"   # "llama" or "gpt2" (llm_build_gpt2)
+    # RoPE variants, all off by default (an existing config's image stays byte-identical)
+    n_rot: int = 0                    # rope.dimension_count; 0 = head_dim (partial rotary when smaller)
+    rope_scale: float = 0.0           # > 0: linear RoPE scaling, rope.scaling.type "linear" + rope.scaling.factor
+    rope_scale_legacy: bool = False   # write the factor as rope.scale_linear instead, with no type key
+    rope_scaling_type: str = "linear"  # the rope.scaling.type written beside rope.scaling.factor
+    rope_freqs: bool = False          # an F32 rope_freqs.weight of n_rot/2 frequency factors (Llama-3.1)
+    init: str = ""                    # _init_params overrides of this config, "key=value,..." as BLAMA_SYNTH_INIT
 
     @property
     def head_dim(self):
         return self.n_embd // self.n_head
+
+    @property
+    def rot_dim(self):
+        return self.n_rot or self.head_dim
 
 
 CONFIGS = {
@@ -65,6 +76,18 @@ CONFIGS = {
     "tiny1-q4_k_m": LlamaConfig("tiny1", 512, 256, 1, 4, 2, 512, 256, 10000.0, 1e-5, "Q4_K_M"),
     "tiny-moe-q5_k_m": LlamaConfig("tiny-moe", 512, 256, 2, 4, 2, 512, 256, 1e6, 1e-5,
                                     "Q5_K_M", n_expert=4, n_expert_used=2),
+    # RoPE variants (tests/test_gpu_rope.py): frequency factors, linear scaling under both key
+    # spellings, partial rotary -- on the streaming step (hd 64), the gemv_kernel step (hd 32), MoE.
+    # Q/K weights 30 x the default scale: with the default's near-uniform softmax a wrong rotation
+    # barely reaches the logits (test_rope_fault_would_be_detected measures that it does here)
+    "tiny-rf-q4_k_m": LlamaConfig("tiny-rf", 512, 256, 2, 4, 2, 512, 256, 10000.0, 1e-5, "Q4_K_M",
+                                   rope_scale=4.0, rope_freqs=True, init="qk=0.3"),
+    "tiny-prot-q4_k_m": LlamaConfig("tiny-prot", 512, 256, 2, 4, 2, 512, 256, 10000.0, 1e-5, "Q4_K_M",
+                                     n_rot=32, rope_scale=2.0, rope_scale_legacy=True, init="qk=0.3"),
+    "tiny-rf-q8_0": LlamaConfig("tiny-rf", 512, 256, 2, 8, 4, 768, 256, 10000.0, 1e-6, "Q8_0",
+                                 n_rot=16, rope_scale=4.0, rope_freqs=True, init="qk=0.3"),
+    "tiny-rf-moe-q5_k_m": LlamaConfig("tiny-rf-moe", 512, 256, 2, 4, 2, 512, 256, 1e6, 1e-5, "Q5_K_M",
+                                       n_expert=4, n_expert_used=2, rope_scale=2.0, rope_freqs=True, init="qk=0.3"),
     # GQA ratio 2 with 16 kv heads of 64: the quantising decode attention has no
     # kernel for two kv heads per 256-block, so decode takes the gemv_kernel step and short
     # batches the plain fused attention + quant_act -- both must still run
@@ -131,6 +154,8 @@ def tensor_types(cfg: LlamaConfig) -> dict:
     mixed = cfg.ftype in ("Q4_K_M", "Q5_K_M")
     t = {"token_embd.weight": base, "output_norm.weight": F32,
          "output.weight": Q8_0 if base == Q8_0 else Q6_K}
+    if cfg.rope_freqs:
+        t["rope_freqs.weight"] = F32
     n = cfg.n_layer
     for i in range(n):
         p = f"blk.{i}."
@@ -167,6 +192,8 @@ def tensor_shapes(cfg: LlamaConfig) -> dict:
     d, kv = cfg.n_embd, cfg.n_head_kv * cfg.head_dim
     s = {"token_embd.weight": (d, cfg.n_vocab), "output_norm.weight": (d,),
          "output.weight": (d, cfg.n_vocab)}
+    if cfg.rope_freqs:
+        s["rope_freqs.weight"] = (cfg.rot_dim // 2,)
     for i in range(cfg.n_layer):
         p = f"blk.{i}."
         s[p + "attn_norm.weight"] = (d,)
@@ -375,7 +402,7 @@ def _token_dirs(seed: int, lo: int, hi: int, V: int, d: int) -> np.ndarray:
 
 
 def _init_params(cfg):
-    env = dict(kv.split("=") for kv in os.environ.get("BLAMA_SYNTH_INIT", "").split(",") if kv)
+    env = dict(kv.split("=") for kv in (cfg.init + "," + os.environ.get("BLAMA_SYNTH_INIT", "")).split(",") if kv)
     p = {"base": 0.03, "qk": 0.01, "resid": 0.03 / np.sqrt(2.0 * cfg.n_layer), "embd": 8.0,
          "alpha": 0.01, "nsucc": 10}
     if cfg.arch == "gpt2":
@@ -501,7 +528,12 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
         w.add_u32(f"{arch}.attention.head_count_kv", cfg.n_head_kv)
         w.add_f32(f"{arch}.attention.layer_norm_rms_epsilon", cfg.eps)
         w.add_f32(f"{arch}.rope.freq_base", cfg.rope_base)
-        w.add_u32(f"{arch}.rope.dimension_count", cfg.head_dim)
+        w.add_u32(f"{arch}.rope.dimension_count", cfg.rot_dim)
+        if cfg.rope_scale > 0 and cfg.rope_scale_legacy:
+            w.add_f32(f"{arch}.rope.scale_linear", cfg.rope_scale)
+        elif cfg.rope_scale > 0:
+            w.add_str(f"{arch}.rope.scaling.type", cfg.rope_scaling_type)
+            w.add_f32(f"{arch}.rope.scaling.factor", cfg.rope_scale)
     w.add_u32(f"{arch}.vocab_size", cfg.n_vocab)
     if cfg.n_expert:
         w.add_u32(f"{arch}.expert_count", cfg.n_expert)
@@ -541,7 +573,12 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
         if name in ("token_embd.weight", "output.weight"):
             _fill_structured(cfg, seed, name, t, view, P)
             return
-        if name.endswith("norm.weight"):
+        if name == "rope_freqs.weight":
+            # every pair, the fast ones included, gets a factor well away from 1 (not Llama-3.1's
+            # 1 .. 8 ramp): dropping or mis-indexing the factors then moves every angle
+            v = view.view(np.float32)
+            v[:] = rng.uniform(0.5, 4.0, v.size).astype(np.float32)
+        elif name.endswith("norm.weight"):
             v = view.view(np.float32)
             v[:] = rng.uniform(0.8, 1.2, v.size).astype(np.float32)
         elif name.endswith(".bias"):

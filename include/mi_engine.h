@@ -56,6 +56,8 @@ int32_t mi_model_n_head(const mi_model* model);
 int32_t mi_model_n_head_kv(const mi_model* model);
 int32_t mi_model_n_ff(const mi_model* model);
 int32_t mi_model_n_expert(const mi_model* model);
+/* llama_model_rope_freq_scale_train: 1 / the linear RoPE scaling factor (1 when unscaled) */
+float mi_model_rope_freq_scale(const mi_model* model);
 int32_t mi_model_token_bos(const mi_model* model);
 int32_t mi_model_token_eos(const mi_model* model);
 int32_t mi_model_add_bos(const mi_model* model);

@@ -70,6 +70,16 @@ class Model:
         rd = gguf.GGUFReader(gguf_image)
         kv = rd.kv
         a = kv["general.architecture"]
+        # orc rope() knows neither frequency factors nor a frequency scale: refuse, not ignore
+        if _HERE not in sys.path:
+            sys.path.insert(0, _HERE)
+        import ggml_ref
+        if "rope_freqs.weight" in rd.tensors:
+            raise NotImplementedError("the C oracle's rope() has no frequency factors: this image carries "
+                                      "rope_freqs.weight (use the numpy oracle, ggml_ref.LlamaOracle)")
+        if ggml_ref.rope_freq_scale(kv, a) != 1.0:
+            raise NotImplementedError("the C oracle's rope() has no freq_scale: this image asks for linear "
+                                      "RoPE scaling (use the numpy oracle, ggml_ref.LlamaOracle)")
         n_embd = int(kv[f"{a}.embedding_length"])
         n_head = int(kv[f"{a}.attention.head_count"])
         hp = HParams(int(rd.tensors["token_embd.weight"].shape[1]), n_embd, int(kv[f"{a}.block_count"]),

@@ -431,17 +431,33 @@ def rope_cache(pos: int, n_dims: int, freq_base: float, freq_scale: float = 1.0,
     return cos, sin
 
 
-def rope_norm(x: np.ndarray, pos: int, n_dims: int, freq_base: float, freq_factors=None):
-    """mode 0 (NORM): rotate adjacent pairs (x[2i], x[2i+1]) of each head.
-    x: (n_heads, head_dim)."""
+def rope_norm(x: np.ndarray, pos: int, n_dims: int, freq_base: float, freq_factors=None,
+              freq_scale: float = 1.0):
+    """mode 0 (NORM): rotate adjacent pairs (x[2i], x[2i+1]) of each head; elements from n_dims
+    on pass through.  x: (n_heads, head_dim)."""
     x = np.asarray(x, np.float32)
-    cos, sin = rope_cache(pos, n_dims, freq_base, freq_factors=freq_factors)
+    cos, sin = rope_cache(pos, n_dims, freq_base, freq_scale, freq_factors)
     y = x.copy()
     x0 = x[:, 0:n_dims:2]
     x1 = x[:, 1:n_dims:2]
     y[:, 0:n_dims:2] = (x0 * cos - x1 * sin).astype(np.float32)
     y[:, 1:n_dims:2] = (x0 * sin + x1 * cos).astype(np.float32)
     return y
+
+
+def rope_freq_scale(kv: dict, arch: str) -> float:
+    """freq_scale from a GGUF's metadata as llama.cpp b5187 derives it: the factor is
+    <arch>.rope.scaling.factor, else the older <arch>.rope.scale_linear; freq_scale = 1/factor
+    when factor > 0.  <arch>.rope.scaling.type (default "linear") picks the mode: "none" runs
+    unscaled; "yarn" / "longrope" need an ext_factor / per-layer factors that neither this
+    restatement nor the engine's kernels implement, so they are refused."""
+    typ = kv.get(f"{arch}.rope.scaling.type", "linear")
+    if typ == "none":
+        return 1.0
+    if typ != "linear":
+        raise NotImplementedError(f"rope.scaling.type '{typ}' is not implemented (linear / none only)")
+    f = float(kv.get(f"{arch}.rope.scaling.factor", kv.get(f"{arch}.rope.scale_linear", 0.0)))
+    return 1.0 / f if f > 0.0 else 1.0
 
 
 def soft_max(s: np.ndarray, scale: float) -> np.ndarray:
@@ -596,6 +612,7 @@ class HParams:
     n_expert: int = 0
     n_expert_used: int = 0
     arch: str = "llama"      # "llama" (llm_build_llama) or "gpt2" (llm_build_gpt2)
+    freq_scale: float = 1.0  # linear RoPE scaling: 1 / rope.scaling.factor
 
     @property
     def head_dim(self):
@@ -659,6 +676,13 @@ class LlamaOracle:
         raw = t.data.reshape(-1)[e * M * rb:(e + 1) * M * rb]
         return mul_mat_vec(raw, t.type, K, x)
 
+    def _rope(self, x, pos, ffv, which):
+        """ggml_rope_ext of Q ("q"), K ("k") or the cached K of a K-shift ("shift"): the same
+        n_rot, base, frequency factors and freq_scale for all three (a test's deliberately wrong
+        oracle overrides this per operand)."""
+        hp = self.hp
+        return rope_norm(x, pos, hp.n_rot, hp.rope_base, ffv, hp.freq_scale)
+
     # ---- KV cache cell operations (llama_kv_self_seq_rm / seq_add / seq_div) ----
     def kv_seq_rm(self, p0, p1):
         p1 = 1 << 30 if p1 < 0 else p1
@@ -686,8 +710,7 @@ class LlamaOracle:
                 if d:
                     for il in range(self.hp.n_layer):
                         k = self.kcache[il][c].astype(np.float32).reshape(self.hp.n_head_kv, hd)
-                        self.kcache[il][c] = f32_to_f16(rope_norm(k, d, self.hp.n_rot, self.hp.rope_base,
-                                                                  ffv).reshape(-1))
+                        self.kcache[il][c] = f32_to_f16(self._rope(k, d, ffv, "shift").reshape(-1))
         neg = [c for c in range(self.n_past) if self.cell_pos[c] < 0]
         if neg:
             self.kv_seq_rm(-(1 << 30), 0)
@@ -768,8 +791,8 @@ class LlamaOracle:
             q = self._mm(f"blk.{il}.attn_q.weight", cur).reshape(hp.n_head, hd)
             k = self._mm(f"blk.{il}.attn_k.weight", cur).reshape(hp.n_head_kv, hd)
             v = self._mm(f"blk.{il}.attn_v.weight", cur)
-            q = rope_norm(q, pos, hp.n_rot, hp.rope_base, ffv)
-            k = rope_norm(k, pos, hp.n_rot, hp.rope_base, ffv)
+            q = self._rope(q, pos, ffv, "q")
+            k = self._rope(k, pos, ffv, "k")
             self.kcache[il][cell] = f32_to_f16(k.reshape(-1))
             self.vcache[il][cell] = f32_to_f16(v)
             vis = [c for c in range(cell + 1) if c == cell or self.cell_pos[c] <= pos]

@@ -141,14 +141,16 @@ def test_context_shift_matches_oracle(gpu_lib, cfg_name):
         assert np.max(np.abs(got - ref)) <= LOGIT_TOL * rms
 
 
-def _kshift_ref(k16, deltas, hp):
-    """The K-shift applied to a cache snapshot: f16(rope(f32(K), delta)) per cell."""
+def _kshift_ref(k16, deltas, hp, freq_factors=None):
+    """The K-shift applied to a cache snapshot: f16(rope(f32(K), delta)) per cell, with the
+    model's freq_scale and frequency factors (rope_freqs.weight)."""
     out = k16.copy()
     for c, d in enumerate(deltas):
         if d:
             for il in range(k16.shape[0]):
                 k = k16[il, c].astype(np.float32).reshape(hp.n_head_kv, hp.head_dim)
-                out[il, c] = R.f32_to_f16(R.rope_norm(k, d, hp.n_rot, hp.rope_base).reshape(-1))
+                out[il, c] = R.f32_to_f16(R.rope_norm(k, d, hp.n_rot, hp.rope_base, freq_factors,
+                                                      hp.freq_scale).reshape(-1))
     return out
 
 
@@ -324,6 +326,11 @@ DECODE_PATH = {
     "tiny-gqa16-q4_k_m": 0,
     "tiny-gpt2-q6_k": 0,
     "tiny-gpt2-q8_0": 0,
+    # the RoPE variants (test_gpu_rope.py): the step of the geometry each is built on
+    "tiny-rf-q4_k_m": 1,
+    "tiny-prot-q4_k_m": 1,
+    "tiny-rf-q8_0": 0,
+    "tiny-rf-moe-q5_k_m": 1,
 }
 
 

@@ -32,7 +32,7 @@ def oracle_from_gguf(buf, n_ctx: int = 0) -> R.LlamaOracle:
         rope_base=float(kv.get(f"{a}.rope.freq_base", 10000.0)),
         n_rot=int(kv.get(f"{a}.rope.dimension_count", n_embd // n_head)),
         n_expert=int(kv.get(f"{a}.expert_count", 0)), n_expert_used=int(kv.get(f"{a}.expert_used_count", 0)),
-        arch=a)
+        arch=a, freq_scale=R.rope_freq_scale(kv, a))
     tens = {k: R.Tensor(v.type, v.shape, v.data) for k, v in rd.tensors.items()}
     return R.LlamaOracle(hp, tens, n_ctx=n_ctx)
 
