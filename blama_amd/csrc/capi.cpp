@@ -489,6 +489,76 @@ size_t mi_state_set(mi_ctx* c, const uint8_t* src, size_t size) {
     MI_TRY(0)
 }
 
+int32_t mi_ctx_apply_cvec(mi_ctx* c, const float* data, size_t len, int32_t n_embd, int32_t il_start, int32_t il_end) {
+    try {
+        if (!c) throw Error("null ctx");
+        c->impl->apply_cvec(data, len, n_embd, il_start, il_end);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// The loader of one control-vector GGUF: every tensor must be an F32, 1-D "direction.N" (N >= 1),
+// all of one length; data[n_embd * (N - 1) + j] += src[j] * strength.
+int64_t mi_cvec_load(const char* path, float strength, float* data, size_t cap, int32_t* n_embd_out) {
+    try {
+        if (!path) throw Error("null path");
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) throw Error(std::string("cannot open ") + path);
+        struct stat st;
+        if (fstat(fd, &st) != 0) { ::close(fd); throw Error("fstat failed"); }
+        const size_t size = (size_t)st.st_size;
+        std::vector<uint8_t> img(size);
+        size_t got = 0;
+        while (got < size) {
+            const ssize_t r = ::read(fd, img.data() + got, size - got);
+            if (r <= 0) break;
+            got += (size_t)r;
+        }
+        ::close(fd);
+        if (got != size) throw Error(std::string("cannot read ") + path);
+        Gguf g;
+        g.parse(img.data(), size);
+        long long n_embd = -1, max_n = 0;
+        std::vector<long long> layer(g.tensors.size());
+        for (size_t i = 0; i < g.tensors.size(); ++i) {
+            const GgufTensor& t = g.tensors[i];
+            long long n = -1;
+            if (t.name.compare(0, 10, "direction.") == 0 && t.name.size() > 10 && t.name.size() <= 19) {
+                // (std::stoi's reading: optional sign, digits, anything after them ignored)
+                const char* s = t.name.c_str() + 10;
+                char* end = nullptr;
+                const long long v = std::strtoll(s, &end, 10);
+                if (end != s) n = v;
+            }
+            if (n <= 0) throw Error("control vector: tensor '" + t.name + "' is not direction.N with N >= 1");
+            if (t.type != T_F32) throw Error("control vector: " + t.name + " is not F32");
+            if (t.n_dims != 1) throw Error("control vector: " + t.name + " is not 1-D");
+            if (n_embd < 0) n_embd = t.ne[0];
+            else if (t.ne[0] != n_embd) throw Error("control vector: " + t.name + " differs in length from the others");
+            if (g.data_offset + t.offset + (size_t)t.ne[0] * 4 > size) throw Error("control vector: tensor data beyond the end of the file");
+            layer[i] = n;
+            max_n = std::max(max_n, n);
+        }
+        if (n_embd <= 0 || n_embd > INT32_MAX) throw Error("control vector: no direction tensors");
+        if (n_embd_out) *n_embd_out = (int32_t)n_embd;
+        const long long need = n_embd * max_n;
+        if (data && cap >= (size_t)need) {
+            for (size_t i = 0; i < g.tensors.size(); ++i) {
+                const uint8_t* src = img.data() + g.data_offset + g.tensors[i].offset;
+                float* dst = data + n_embd * (layer[i] - 1);
+                for (long long j = 0; j < n_embd; ++j) {
+                    float v;
+                    std::memcpy(&v, src + 4 * j, 4);
+                    dst[j] += v * strength;
+                }
+            }
+        }
+        return need;
+    }
+    MI_TRY(-1)
+}
+
 int32_t mi_prof_enable(mi_ctx* c, int32_t layer) {
     if (!c) return -1;
     if (layer >= c->impl->m->hp.n_layer) layer = c->impl->m->hp.n_layer - 1;

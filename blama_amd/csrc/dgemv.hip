@@ -54,6 +54,7 @@ struct DvArgs {
     const char* act;            // this launch's activation, act_layout(K, q8k, q80)
     int act_bytes, K, q8k, q80;
     const float* resid;         // DV_ADD
+    const float* addend;        // DV_ADD, optional: out = (y + resid) + addend (GemvSeg::addend)
     const float* hraw;          // DV_ADDQ / _QKVN / _SWIGLUN: the fp32 activation (K floats)
     const float* norm_w;        // DV_QKVN / DV_SWIGLUN
     float eps;
@@ -259,7 +260,9 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     } else if (ROLE == DV_SWIGLU) {
         S.out[u] = silu_f(y[0]) * y[RW - 1];
     } else if (ADD) {
-        S.out[u] = y[0] + res;
+        float o = y[0] + res;
+        if (a.addend) o = o + gptr(a.addend)[u];   // (uniform: a launch without one is what it was)
+        S.out[u] = o;
     } else {
         S.out[u] = y[0];
     }
@@ -423,6 +426,7 @@ bool dgemv_supported(const GemvParams& p) {
     const GemvSeg& g = p.seg[0];
     const int role = dv_role(p);
     if (role < 0 || g.bias || g.expA >= 0 || g.expB >= 0) return false;
+    if (g.addend && dv_base(role) != DV_ADD) return false;
     if (p.nseg == 2 && (dv_base(role) != DV_QKV || p.seg[1].epi != EPI_QKV)) return false;
     return dv_fn(role, g.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K)) != nullptr;
 }
@@ -464,6 +468,7 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
     a.q80 = p.act_q80;
     a.act_bytes = (int)dv_act_bytes(p.K, p.act_q8k, p.act_q80);
     a.resid = g0.resid;
+    a.addend = role == DV_ADD ? g0.addend : nullptr;
     a.tokpos = p.tokpos;
     a.cell_pos = p.cell_pos;
     a.kcache = p.kcache;

@@ -7,6 +7,7 @@
 //   llama_get_logits_ith        /root/reference/inference/code/llama/Session.cpp:24
 //   llama_kv_self_*             /root/reference/inference/code/llama/Session.cpp:53,341-361
 //   llama_state_*               /root/reference/inference/code/llama/Session.cpp:291-304
+//   llama_apply_adapter_cvec    /root/reference/inference/code/llama/Instance.cpp:74
 #include "engine.h"
 
 #include <atomic>
@@ -267,6 +268,27 @@ void Ctx::invalidate_graphs() {
     }
 }
 
+void Ctx::apply_cvec(const float* data, size_t len, int n_embd, int il_start, int il_end) {
+    const HParams& hp = m->hp;
+    if (data && n_embd != hp.n_embd) throw Error("apply_cvec: the control vector's n_embd differs from the model's");
+    MI_HIP(hipSetDevice(device));
+    sync();                 // steps in flight still read the old rows
+    invalidate_graphs();    // the next step re-captures with the new arguments
+    cvec_on.clear();
+    if (!data) return;
+    std::vector<char> on(hp.n_layer, 0);
+    bool any = false;
+    for (int il = std::max(1, il_start); il < hp.n_layer && il <= il_end; ++il)
+        if ((size_t)il * hp.n_embd <= len) on[il] = 1, any = true;
+    if (!any) return;
+    if (!cvec) cvec = mem.dev<float>((size_t)hp.n_layer * hp.n_embd, true);
+    for (int il = 1; il < hp.n_layer; ++il)
+        if (on[il])
+            MI_HIP(hipMemcpy(cvec + (size_t)il * hp.n_embd, data + (size_t)(il - 1) * hp.n_embd,
+                             (size_t)hp.n_embd * sizeof(float), hipMemcpyHostToDevice));
+    cvec_on = std::move(on);
+}
+
 long long Ctx::ffn_bytes() const {
     const Layer& L = m->layers[0];
     auto mb = [](const QMat& q) { return (long long)q.rows * q.nb * ((long long)block_bytes(q.type) * 256 / block_elems(q.type)); };
@@ -447,6 +469,7 @@ GemvParams Ctx::down_params(int l, ActSrc src) const {
         p.seg[0].bias = L.bdown;
     }
     p.seg[0].resid = x;
+    p.seg[0].addend = cvec_for(l);   // build_cvec: after the FFN residual add
     return p;
 }
 
@@ -758,6 +781,7 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
                 p.K = hp.n_ff;
                 p.out = xb;
                 p.resid = xb;
+                p.addend = cvec_for(l);
                 p.out_stride = hp.n_embd;
                 proj(p, hb, hp.n_ff, nullptr, true);
             }
@@ -825,7 +849,7 @@ void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
     d.out_stride = hp.n_embd;
     d.grp_stride = L.down.sw_expert_stride;
     launch_mmq32(d, a2, ub_rope, stream);
-    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream);
+    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
 }
 
 // The same build_moe_ffn over a short batch (<= MMQS_MAX tokens; x already holds the residual) on
@@ -860,7 +884,7 @@ void Ctx::moe_ffn_short(int l, int nt) {
     launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel, ub_spart, kg, 1);
     const int kd = launch_mmqs_grouped(L.down, false, 0, a2, ub_spart, hp.n_embd, moe_grp, E, nt, stream);
     launch_part_sum(ub_spart, kd, cap, hp.n_embd, hp.n_embd, nullptr, 0, yb, hp.n_embd, stream);
-    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream);
+    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
 }
 
 ActQ8 Ctx::ub_act(int K, int ntok, int type) const {
@@ -910,6 +934,7 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
         launch_embed_multi(ep, nt, stream);
         launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale, hp.freq_scale, m->rope_freqs, ub_rope, stream);
         const float* pend = nullptr;   // split-K partials not yet added into xb (the next quant_act does)
+        const float* pend_add = nullptr;   // the control-vector row that goes in after them (FFN down's parts)
         // split-K parts of the residual GEMMs: 4 for short batches of dense models (verification
         // of tens of tokens: more workgroups, a quarter of the superblock steps each; 4 x nt rows
         // fit the 2 x UB_MAX partials buffer), else 2 (the MoE router adds 2)
@@ -939,7 +964,7 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                 for (const QMat* q : mats) need = need || (q->type == T_Q8_0) == (f == 1);
                 if (need) {
                     launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                     nullptr, pend, ks);
+                                     nullptr, pend, ks, 0, pend ? pend_add : nullptr);
                     pend = nullptr;
                 }
             }
@@ -1013,6 +1038,9 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                     p.ksplit = ks;
                     p.part = ub_part;
                     pend = ub_part;
+                    pend_add = cvec_for(l);
+                } else {
+                    p.addend = cvec_for(l);
                 }
                 launch_mmq32(p, act, ub_rope, stream);
             }
@@ -1054,10 +1082,13 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
     launch_embed_multi(ep, nt, stream);
     launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale, hp.freq_scale, m->rope_freqs, ub_rope, stream);
     const int pend_k = ubatch_layers_short(nt);
+    // (the parts pending are the last layer's FFN down's -- dense models; its control-vector row
+    // goes in with them)
+    const float* pend_add = pend_k ? cvec_for(hp.n_layer - 1) : nullptr;
     if (all) {   // final norm + output head on mmqs, its parts summed into the logits rows
         const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);
         launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream, nullptr, pend_k ? ub_spart : nullptr,
-                         pend_k ? pend_k : 2);
+                         pend_k ? pend_k : 2, 0, pend_add);
         const QMat* mo[1] = {&m->output};
         const int pr[1] = {0};
         const int kp = launch_mmqs(mo, pr, 1, false, 0, a_out, ub_spart, hp.n_vocab, stream);
@@ -1071,7 +1102,8 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
         }
     } else {
         // the last residual parts into xb (the next chunk, or the output, reads it)
-        if (pend_k) launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream);
+        if (pend_k)
+            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream, 0, pend_add);
         if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
 }
@@ -1097,8 +1129,10 @@ int Ctx::ubatch_layers_short(int nt) {
             bool need = false;
             for (const QMat* q : mats) need = need || (q->type == T_Q8_0) == (f == 1);
             if (need) {
+                // (parts pending here are the previous layer's FFN down's: its control-vector row with them)
                 launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                 nullptr, pend_k ? ub_spart : nullptr, pend_k ? pend_k : 2);
+                                 nullptr, pend_k ? ub_spart : nullptr, pend_k ? pend_k : 2, 0,
+                                 pend_k && l > 0 ? cvec_for(l - 1) : nullptr);
                 pend_k = 0;
             }
         }

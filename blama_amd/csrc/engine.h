@@ -215,6 +215,18 @@ struct Ctx {
     int logits_all_cap = 0;
     int out_rows = 0;                   // rows of logits_all valid (0: the last decode was MI_OUT_LAST)
     int topk_row = -1;                  // output row the mapped top-k buffers hold (-1: the last token)
+    // control vector (llama_adapter_cvec, b5187): row l is layer l's direction, added to the
+    // residual stream after the layer's FFN residual add (build_cvec) in every path.  A property
+    // of the context, not of its state (mi_state_get / mi_state_set leave it alone).
+    float* cvec = nullptr;              // [n_layer][n_embd], allocated by the first apply_cvec
+    std::vector<char> cvec_on;          // [n_layer]: the layer carries its row (empty: no vector)
+    const float* cvec_for(int l) const {
+        return !cvec_on.empty() && cvec_on[l] ? cvec + (size_t)l * m->hp.n_embd : nullptr;
+    }
+    // llama_adapter_cvec::apply: data == null clears; layer il in [max(1, il_start), min(il_end,
+    // n_layer - 1)] with il * n_embd <= len carries data[(il - 1) * n_embd ..).  Synchronises the
+    // stream and drops the captured decode graphs (their launches hold the old arguments).
+    void apply_cvec(const float* data, size_t len, int n_embd, int il_start, int il_end);
     // diagnostics (MI_STAMPS builds only): s_memrealtime stamps of every
     // workgroup of every launch of the last enqueued step [launch][wg][8]
     static constexpr int kStampLaunches = 320, kStampWgs = 512;

@@ -42,6 +42,7 @@ struct GvSeg {
     float* out;
     const float* resid;
     const float* bias;          // optional per-row bias (GPT-2 projections)
+    const float* addend;        // optional, EPI_ADD / EPI_MOE_DOWN: added after the residual
     int units, blk0, nblk, rows;
     int epi, nq, nk, expA, expB, actB;
 };
@@ -773,7 +774,11 @@ __device__ __forceinline__ void gv_body(const GvArgs& a, char* lds, Wait&& wait 
                 float* const out = S.out;
                 if (ab) {
                     if (epi == EPI_SWIGLU) gst<P>(out + u, silu_f(y[0]) * y[RW - 1]);
-                    else gst<P>(out + u, (y[0] * w0 + y[RW - 1] * w1) + s.res.x);   // EPI_MOE_DOWN
+                    else {   // EPI_MOE_DOWN
+                        float o = (y[0] * w0 + y[RW - 1] * w1) + s.res.x;
+                        if (S.addend) o = o + gptr(S.addend)[u];
+                        gst<P>(out + u, o);
+                    }
                 } else {
                     const long long r0 = u * RW;
                     if (epi == EPI_QKV) {
@@ -810,7 +815,10 @@ __device__ __forceinline__ void gv_body(const GvArgs& a, char* lds, Wait&& wait 
                             const float v = r == 0 ? y[0] : y[RW - 1];
                             const float rv = r == 0 ? s.res.x : s.res.y;
                             float o = v;
-                            if (epi == EPI_ADD) o = v + rv;
+                            if (epi == EPI_ADD) {
+                                o = v + rv;
+                                if (S.addend) o = o + gptr(S.addend)[r0 + r];
+                            }
                             if (GX && epi == EPI_GELU) {   // ggml_vec_gelu_f32 (GGML_GELU_FP16 table)
                                 const unsigned short hb = __half_as_ushort(__float2half_rn(v));
                                 const float t = __half2float(__ushort_as_half(gptr(a.gelu_tab)[hb]));
@@ -1000,6 +1008,7 @@ static void gv_prepare(const GemvParams& p, int cap, GvArgs& a, int& grid_out, G
         if ((g.epi == EPI_ADD || g.epi == EPI_MOE_DOWN) && !g.resid) throw Error("gemv: residual epilogue without resid");
         if (g.epi == EPI_GELU && (!p.gelu_tab || g.pair == PAIR_AB)) throw Error("gemv: GELU epilogue needs the table, one matrix");
         if (g.bias && g.pair == PAIR_AB) throw Error("gemv: no bias on a PAIR_AB segment");
+        if (g.addend && g.epi != EPI_ADD && g.epi != EPI_MOE_DOWN) throw Error("gemv: an addend goes with a residual epilogue");
     }
     if (p.nseg == 2 && !gemv_pair_supported(p.seg[0].A.type, p.seg[1].A.type))
         throw Error("gemv: unsupported pair of segment types");
@@ -1038,6 +1047,7 @@ static void gv_prepare(const GemvParams& p, int cap, GvArgs& a, int& grid_out, G
         o.out = g.out;
         o.resid = g.resid;
         o.bias = g.bias;
+        o.addend = g.addend;
         o.rows = g.A.rows;
         o.units = g.pair == PAIR_AB ? g.A.rows : (g.A.rows + key.rw - 1) / key.rw;
         o.epi = g.epi;

@@ -40,6 +40,9 @@ struct GemvSeg {
     float* out;
     const float* resid;   // EPI_ADD / EPI_MOE_DOWN (may alias out)
     const float* bias;    // optional per-row bias (GPT-2), added before the epilogue
+    // optional per-row addend of EPI_ADD / EPI_MOE_DOWN, added AFTER the residual: out[r] = (y +
+    // resid[r]) + addend[r] (a control vector's layer direction, build_cvec after the FFN residual)
+    const float* addend;
 };
 
 // Attention split over cells: split s of q head h holds the partial sum
@@ -158,6 +161,7 @@ struct GemmParams {
     float* out;                // [ntok][out_stride]
     int out_stride;
     const float* resid;        // EPI_ADD: [ntok][out_stride] (may alias out)
+    const float* addend;       // EPI_ADD, optional: [rows], out = (y + resid) + addend[row] for every token
     const int* tokpos;         // [ntok][4] {token, pos, cell, 0}
     int* cell_pos;
     float theta_scale, freq_scale;
@@ -286,7 +290,8 @@ void launch_router(const RouterParams& p, hipStream_t s);
 void launch_router_multi(const RouterParams& p, int ntok, hipStream_t s);
 // build_moe_ffn's aggregation over a physical batch: x[t] = (y[pos[t][0]]*w[t][0] + y[pos[t][1]]*w[t][1])
 // + x[t] (ggml_mul by the weights, ggml_add of the slots in slot order, then the residual add);
-// y holds the experts' down outputs in compact rows (grouped by expert)
+// y holds the experts' down outputs in compact rows (grouped by expert); addend (optional): [n_embd]
+// added to every token's row after the residual
 // Groups the n (token, slot) picks of a physical batch (sel[t*U + k] = expert) by expert on the
 // device: expert e's rows are [grp[e], grp[e] + cnt_e) with grp[e] a multiple of 32 (whole MFMA
 // token tiles), tokens ascending within an expert; grp = {off[0..E], cnt[0..E-1]}.  rows[r] = the
@@ -296,7 +301,7 @@ inline int moe_rows_cap(int n, int E) { return (n + E * 31 + 31) / 32 * 32; }
 void launch_moe_group(const int* sel, int n, int U, int E, int* grp, int* rows, int* rowsel, int* pos, int rows_cap,
                       hipStream_t s);
 void launch_moe_combine(const float* y, const int* pos, const float* w, float* x, int ntok, int n_embd,
-                        hipStream_t s);
+                        hipStream_t s, const float* addend = nullptr);
 
 // ---- load-time repack of GGUF blocks into planes ----
 void launch_repack(const uint8_t* raw, int type, long long rows, int K, uint8_t* const planes[4],
@@ -337,11 +342,13 @@ void launch_attn_mfma(const AttnParams& p, int ntok, float* out, hipStream_t s);
 constexpr int UB_MAX = 512;    // n_ubatch (reference Instance.hpp:24)
 // rows (optional): token t of the batch reads row rows[t] of x (the tokens routed to one expert)
 // part (optional): the split-K partial sums of the GEMM that produced x (see GemmParams::ksplit):
-// x = ((p0 + p1) + ...) + x first, written back
+// x = ((p0 + p1) + ...) + x first, written back; addend (optional, with part): [K] added to every
+// row after that, x = (((p0 + p1) + ...) + x) + addend
 // swiglu: part holds the gate/up parts of a pair launch ([nks][ntok][2 K]: gate rows, then up
 // rows); the row quantised is silu(sum gate) * (sum up) (x unused)
 void launch_quant_act(const float* x, int x_stride, const float* norm_w, float eps, const ActQ8& a, hipStream_t s,
-                      const int* rows = nullptr, const float* part = nullptr, int nks = 2, int swiglu = 0);
+                      const int* rows = nullptr, const float* part = nullptr, int nks = 2, int swiglu = 0,
+                      const float* addend = nullptr);
 // whether prompt-batch GEMMs take the mmq2 path (the only one with ksplit)
 bool mmq2_active();
 // ggml_rope_cache_init per token of the batch: out [ntok][n_rot/2] (cos, sin)
@@ -396,8 +403,9 @@ struct QkvFinish {
 };
 void launch_qkv_finish(const QkvFinish& F, hipStream_t s);
 // out[t][r] = ((p0 + p1) + ...) [+ resid[t][r]] over rows [0, rows) of the parts; swiglu > 0 (a
-// pair launch's parts, up rows from swiglu): silu(sum gate) * (sum up)
+// pair launch's parts, up rows from swiglu): silu(sum gate) * (sum up); addend (optional, with
+// resid): [rows] added to every token's row after the residual
 void launch_part_sum(const float* part, int kp, int ntok, int rows, int pstride, const float* resid, int rstride,
-                     float* out, int ostride, hipStream_t s, int swiglu = 0);
+                     float* out, int ostride, hipStream_t s, int swiglu = 0, const float* addend = nullptr);
 
 }  // namespace mi

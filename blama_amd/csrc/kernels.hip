@@ -183,8 +183,13 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
                     break;
                 case EPI_ADD: {
                     const float r0 = res[ra], r1 = hasB ? res[rb] : 0.0f;
-                    out[ra] = yA + r0;
-                    if (hasB) out[rb] = yB + r1;
+                    float oA = yA + r0, oB = yB + r1;
+                    if (P.addend) {   // (the control vector's direction, after the residual)
+                        oA = oA + P.addend[ra];
+                        if (hasB) oB = oB + P.addend[rb];
+                    }
+                    out[ra] = oA;
+                    if (hasB) out[rb] = oB;
                     break;
                 }
                 case EPI_ROPE_Q:
@@ -1762,20 +1767,25 @@ void launch_moe_group(const int* sel, int n, int U, int E, int* grp, int* rows, 
     MI_HIP(hipGetLastError());
 }
 
-__global__ void moe_combine_kernel(const float* y, const int* pos, const float* w, float* x, int n_embd) {
+__global__ void moe_combine_kernel(const float* y, const int* pos, const float* w, float* x, int n_embd,
+                                   const float* addend) {
     const int t = blockIdx.y;
     const float* y0 = y + (long long)pos[2 * t] * n_embd;
     const float* y1 = y + (long long)pos[2 * t + 1] * n_embd;
     const float w0 = w[2 * t], w1 = w[2 * t + 1];
     float* xr = x + (long long)t * n_embd;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_embd; i += gridDim.x * blockDim.x)
-        xr[i] = (y0[i] * w0 + y1[i] * w1) + xr[i];   // as the decode GEMV's EPI_MOE_DOWN
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_embd; i += gridDim.x * blockDim.x) {
+        float o = (y0[i] * w0 + y1[i] * w1) + xr[i];   // as the decode GEMV's EPI_MOE_DOWN
+        if (addend) o = o + addend[i];
+        xr[i] = o;
+    }
 }
 
 void launch_moe_combine(const float* y, const int* pos, const float* w, float* x, int ntok, int n_embd,
-                        hipStream_t s) {
+                        hipStream_t s, const float* addend) {
     if (ntok < 1) return;
-    hipLaunchKernelGGL(moe_combine_kernel, dim3((n_embd + 255) / 256, ntok), dim3(256), 0, s, y, pos, w, x, n_embd);
+    hipLaunchKernelGGL(moe_combine_kernel, dim3((n_embd + 255) / 256, ntok), dim3(256), 0, s, y, pos, w, x, n_embd,
+                       addend);
     MI_HIP(hipGetLastError());
 }
 

@@ -108,7 +108,7 @@ __device__ __forceinline__ V sum_parts(const V* p, long long stride, int n) {
 template <int QA_W, int XR>
 __global__ __launch_bounds__(64 * QA_W) void quant_act_kernel(const float* x, int x_stride, const float* norm_w,
                                                         float eps, ActQ8 a, const int* rows, const float* part, int nks,
-                                                        int swiglu) {
+                                                        int swiglu, const float* addend) {
     const int t = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nb = a.K >> 8;
@@ -161,6 +161,10 @@ __global__ __launch_bounds__(64 * QA_W) void quant_act_kernel(const float* x, in
                 const f32x4 acc = sum_parts(reinterpret_cast<const f32x4*>(part + (long long)t * a.K) + blk * 64 + lane,
                                             (long long)a.ntok * a.K / 4, nks);
                 xr[i] = f32x4{acc.x + xr[i].x, acc.y + xr[i].y, acc.z + xr[i].z, acc.w + xr[i].w};
+                if (addend) {   // the parts closed a layer's FFN: its control-vector direction, after the residual
+                    const f32x4 v = reinterpret_cast<const f32x4*>(addend)[blk * 64 + lane];
+                    xr[i] = f32x4{xr[i].x + v.x, xr[i].y + v.y, xr[i].z + v.z, xr[i].w + v.w};
+                }
                 xw[blk * 64 + lane] = xr[i];
             }
             asm volatile("" ::: "memory");   // one block's part loads in flight at a time (registers)
@@ -398,7 +402,9 @@ __device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, cons
         case EPI_ROPE_Q: out[(long long)tok * P.out_stride + row] = o; break;
         case EPI_ADD: {
             const long long i = (long long)tok * P.out_stride + row;
-            out[i] = o + P.resid[i];
+            float s = o + P.resid[i];
+            if (P.addend) s = s + P.addend[row];
+            out[i] = s;
             break;
         }
         case EPI_ROPE_K: {
@@ -1380,13 +1386,14 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(const QkvFinish F) {
 // swiglu + r) (a pair launch's gate and up rows)
 __global__ __launch_bounds__(256) void part_sum_kernel(const float* part, int kp, int ntok, int rows, int pstride,
                                                        const float* resid, int rstride, float* out, int ostride,
-                                                       int swiglu) {
+                                                       int swiglu, const float* addend) {
     const int t = blockIdx.y;
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
     float acc = sum_parts(part + (long long)t * pstride + r, (long long)ntok * pstride, kp);
     if (swiglu) acc = silu(acc) * sum_parts(part + (long long)t * pstride + swiglu + r, (long long)ntok * pstride, kp);
     if (resid) acc = acc + resid[(long long)t * rstride + r];
+    if (addend) acc = acc + addend[r];
     out[(long long)t * ostride + r] = acc;
 }
 
@@ -1395,7 +1402,8 @@ template <int T, int NST> constexpr int m2_lds() { return M2<T>::lds(NST); }
 }  // namespace mmq
 
 void launch_quant_act(const float* x, int x_stride, const float* norm_w, float eps, const ActQ8& a, hipStream_t s,
-                      const int* rows, const float* part, int nks, int swiglu) {
+                      const int* rows, const float* part, int nks, int swiglu, const float* addend) {
+    if (addend && (!part || swiglu)) throw Error("quant_act: an addend goes with the residual's split-K partials");
     if (part && (nks < 1 || nks > 64)) throw Error("quant_act: 1..64 split-K partials");
     // (swiglu with rows: the MoE rows of a grouped pair launch, rows[t] < 0 marking padding rows)
     if (swiglu && (!part || norm_w)) throw Error("quant_act: swiglu takes a pair launch's parts, no norm");
@@ -1412,7 +1420,7 @@ void launch_quant_act(const float* x, int x_stride, const float* norm_w, float e
     const int xr = (nb + 16 * ny - 1) / (16 * ny);
     auto f = xr <= 1 ? mmq::quant_act_kernel<16, 1> : xr <= 2 ? mmq::quant_act_kernel<16, 2>
            : xr <= 4 ? mmq::quant_act_kernel<16, 4> : mmq::quant_act_kernel<16, 16>;
-    hipLaunchKernelGGL(f, dim3(a.npad, ny), dim3(1024), 0, s, x, x_stride, norm_w, eps, a, rows, part, nks, swiglu);
+    hipLaunchKernelGGL(f, dim3(a.npad, ny), dim3(1024), 0, s, x, x_stride, norm_w, eps, a, rows, part, nks, swiglu, addend);
     MI_HIP(hipGetLastError());
 }
 
@@ -1664,10 +1672,11 @@ void launch_qkv_finish(const QkvFinish& F, hipStream_t s) {
 }
 
 void launch_part_sum(const float* part, int kp, int ntok, int rows, int pstride, const float* resid, int rstride,
-                     float* out, int ostride, hipStream_t s, int swiglu) {
+                     float* out, int ostride, hipStream_t s, int swiglu, const float* addend) {
+    if (addend && (!resid || swiglu)) throw Error("part_sum: an addend goes with a residual");
     if (ntok < 1 || kp < 1 || rows < 1 || rows + swiglu > pstride || (swiglu && swiglu < rows)) throw Error("part_sum: bad shape");
     hipLaunchKernelGGL(mmq::part_sum_kernel, dim3((rows + 255) / 256, ntok), dim3(256), 0, s, part, kp, ntok, rows, pstride,
-                       resid, rstride, out, ostride, swiglu);
+                       resid, rstride, out, ostride, swiglu, addend);
     MI_HIP(hipGetLastError());
 }
 

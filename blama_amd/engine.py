@@ -82,6 +82,8 @@ _SIGS = {
     "mi_state_size": (C.c_size_t, [_P]),
     "mi_state_get": (C.c_size_t, [_P, _P, C.c_size_t]),
     "mi_state_set": (C.c_size_t, [_P, _P, C.c_size_t]),
+    "mi_ctx_apply_cvec": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_size_t, C.c_int32, C.c_int32, C.c_int32]),
+    "mi_cvec_load": (C.c_int64, [C.c_char_p, C.c_float, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32)]),
     "mi_prof_enable": (C.c_int32, [_P, C.c_int32]),
     "mi_prof_read": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_int32]),
     "mi_prof_ffn_bytes": (C.c_int64, [_P]),
@@ -308,6 +310,17 @@ class Context:
         if got == 0:
             raise EngineError(f"state_set: {last_error()}")
 
+    def apply_cvec(self, data, il_start: int, il_end: int, n_embd: int | None = None):
+        """mi_ctx_apply_cvec (llama_apply_adapter_cvec): data holds the directions of layers 1, 2, ...
+        back to back; layers il_start..il_end (and no layer past the data, never layer 0) carry theirs
+        from the next decode on.  n_embd: the vectors' length (default: the model's)."""
+        d = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
+        _check(lib().mi_ctx_apply_cvec(self.h, d.ctypes.data_as(C.POINTER(C.c_float)), d.size,
+                                       self.model.n_embd if n_embd is None else n_embd, il_start, il_end), "apply_cvec")
+
+    def clear_cvec(self):
+        _check(lib().mi_ctx_apply_cvec(self.h, None, 0, self.model.n_embd, 0, 0), "clear_cvec")
+
     def prof_enable(self, stride: int):
         lib().mi_prof_enable(self.h, stride)
 
@@ -328,6 +341,22 @@ class Context:
     def prof_bytes(self) -> int:
         """Algorithmic bytes of the launch prof_read last timed (the FFN gate/up GEMV)."""
         return lib().mi_prof_bytes(self.h)
+
+
+def cvec_load(path, strength: float = 1.0):
+    """mi_cvec_load: the direction.N tensors of a control-vector GGUF times strength, as
+    (data [max N * n_embd] f32, layer 1 first; n_embd).  Raises EngineError for an invalid file."""
+    p = os.fspath(path).encode()
+    ne = C.c_int32(0)
+    need = lib().mi_cvec_load(p, strength, None, 0, C.byref(ne))
+    if need < 0:
+        raise EngineError(f"cvec_load: {last_error()}")
+    data = np.zeros(need, np.float32)
+    got = lib().mi_cvec_load(p, strength, data.ctypes.data_as(C.POINTER(C.c_float)), data.size, C.byref(ne))
+    if got != need:
+        raise EngineError(f"cvec_load: {last_error()}")
+    return data, int(ne.value)
+
 
 # ---- op-level entry points (parity tests / micro-benchmarks) ----
 

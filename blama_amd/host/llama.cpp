@@ -840,6 +840,29 @@ Token Sampler::sampleChain(mi_ctx* ctx, int idx) {
 }
 
 // --------------------------------------------------------------- Instance ---
+// ---------------------------------------------------------- ControlVector ---
+ControlVector::ControlVector(const Model& model, const std::vector<LoadInfo>& infos, int lStart, int lEnd)
+    : controlVectorLayerStart(lStart <= 0 ? 1 : lStart),
+      controlVectorLayerEnd(lEnd <= 0 ? mi_model_n_layer(model.mmodel()) : lEnd) {
+    for (const LoadInfo& info : infos) {
+        int32_t ne = -1;
+        const int64_t need = mi_cvec_load(info.ggufPath.c_str(), info.strength, nullptr, 0, &ne);
+        if (need < 0 || (nEmbd != -1 && ne != nEmbd)) {   // an invalid file, or one of another width
+            nEmbd = -1;
+            break;
+        }
+        nEmbd = ne;
+        std::vector<float> cur((size_t)need, 0.0f);
+        if (mi_cvec_load(info.ggufPath.c_str(), info.strength, cur.data(), cur.size(), &ne) != need) {
+            nEmbd = -1;
+            break;
+        }
+        if (data.size() < cur.size()) data.resize(cur.size(), 0.0f);
+        for (size_t i = 0; i < cur.size(); ++i) data[i] += cur[i];
+    }
+    if (nEmbd == -1) data.clear();
+}
+
 Instance::Instance(Model& model, InitParams params) : m_model(model) {
     m_ctx = mi_ctx_create(model.mmodel(), params.ctxSize, params.batchSize, params.ubatchSize);
     if (!m_ctx) BL_THROW("Failed to create llama context");
@@ -848,6 +871,16 @@ Instance::Instance(Model& model, InitParams params) : m_model(model) {
 Instance::~Instance() {
     m_session.reset();
     if (m_ctx) mi_ctx_free(m_ctx);
+}
+
+void Instance::addControlVector(const ControlVector& ctrlVector) {
+    const int err = mi_ctx_apply_cvec(m_ctx, ctrlVector.data.data(), ctrlVector.data.size(), ctrlVector.nEmbd,
+                                      ctrlVector.controlVectorLayerStart, ctrlVector.controlVectorLayerEnd);
+    if (err) BL_THROW("Failed to apply control vectors!");
+}
+
+void Instance::clearControlVector() {
+    if (mi_ctx_apply_cvec(m_ctx, nullptr, 0, 0, 0, 0)) BL_THROW("Failed to clear control vectors!");
 }
 
 void Instance::warmup() {

@@ -12,14 +12,16 @@
 //   TokenPrediction                           Session.hpp:20-27
 //   Model{Params{gpu, vocabOnly, prefixInputsWithBos}}   Model.hpp:26-58
 //   Vocab{tokenize, isEog, nTokens, tokenToString}       Vocab.hpp:16-34
-//   Instance{InitParams, warmup, startSession, stopSession}   Instance.hpp:19-51
+//   Instance{InitParams, warmup, startSession, stopSession,
+//            addControlVector}                            Instance.hpp:19-51
+//   ControlVector{LoadInfo}                               ControlVector.hpp:17-33
 //   Session{InitParams, setInitialPrompt, complete, completeStream, fillCtx,
 //           getState, setState, resetSampler}             Session.hpp:29-130
 //   Sampler{Params, sample, accept, reset}                Sampler.hpp:22-115
 //   LogitComparer / MetricsAggregator                     LogitComparer.hpp:12-34
 //
 // Not served (engine scope): Model::Params::gpu=false (the reference's CPU
-// verifier), LoRA, control vectors, grammar constraints, encoder models.
+// verifier), LoRA, grammar constraints, encoder models.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -208,6 +210,24 @@ private:
     Token sampleGrammarFirst(mi_ctx* ctx, int idx);
 };
 
+// Directions added to the residual stream of layers 1 .. (ControlVector.hpp:17-33): the
+// direction.N tensors of each file times its strength, the files summed.  data holds layer 1's
+// n_embd floats first; an invalid file (or files of differing n_embd) leaves nEmbd == -1 and no data.
+class ControlVector {
+public:
+    struct LoadInfo {
+        std::string ggufPath;
+        float strength;
+    };
+    // lStart <= 0: layer 1; lEnd <= 0: the model's layer count
+    ControlVector(const Model& model, const std::vector<LoadInfo>& infos, int lStart = 0, int lEnd = 0);
+
+    std::vector<float> data;
+    int nEmbd = -1;
+    int controlVectorLayerStart = 0;
+    int controlVectorLayerEnd = 0;
+};
+
 class Instance;
 
 class Session {
@@ -301,6 +321,10 @@ public:
     Instance(const Instance&) = delete;
     Instance& operator=(const Instance&) = delete;
 
+    // llama_apply_adapter_cvec (Instance.cpp:73-84): from the next decode on; throws when the
+    // engine refuses the vector (its nEmbd is not the model's)
+    void addControlVector(const ControlVector& ctrlVector);
+    void clearControlVector();
     void warmup();
     Session& startSession(const Session::InitParams params);
     void stopSession() noexcept;

@@ -596,3 +596,22 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
 
 def small_config(name: str, **kw) -> LlamaConfig:
     return replace(CONFIGS[name], **kw)
+
+
+def write_cvec_gguf(path, directions) -> None:
+    """A control-vector GGUF as llama.cpp's cvector-generator writes it: one tensor direction.N per
+    steered layer N >= 1.  directions: {N: vector} or a list of (N or tensor name, array) pairs (a
+    list can repeat a layer or carry a malformed entry for the loader's error tests); float32
+    arrays are stored as F32, float16 ones as F16, in the array's own shape."""
+    w = gguf.GGUFWriter()
+    w.add_str("general.architecture", "controlvector")
+    w.add_str("controlvector.model_hint", "llama")
+    items = directions.items() if isinstance(directions, dict) else directions
+    for key, v in items:
+        a = np.asarray(v)
+        if a.dtype != np.float16:
+            a = a.astype(np.float32)
+        name = key if isinstance(key, str) else f"direction.{int(key)}"
+        w.add_tensor(name, 1 if a.dtype == np.float16 else 0, a.shape[::-1], a)
+    with open(path, "wb") as f:
+        f.write(w.to_bytes().tobytes())

@@ -138,6 +138,25 @@ size_t mi_state_size(mi_ctx* ctx);
 size_t mi_state_get(mi_ctx* ctx, uint8_t* dst, size_t size);
 size_t mi_state_set(mi_ctx* ctx, const uint8_t* src, size_t size);
 
+/* Control vectors: llama_apply_adapter_cvec (Instance.cpp:74-79, Instance::addControlVector).
+ * data holds the directions of layers 1, 2, ... back to back (len floats, n_embd each; layer 0 has
+ * none).  Layer il (0-based) gets data[(il-1)*n_embd ..) added to its output -- after the FFN
+ * residual add, llm_build_llama / llm_build_gpt2's build_cvec -- when 1 <= il <= n_layer-1,
+ * il_start <= il <= il_end and il*n_embd <= len; every other layer gets nothing.  data NULL
+ * switches the vector off.  The vector belongs to the context (not to mi_state_get / mi_state_set),
+ * takes effect from the next mi_decode and leaves the KV entries of earlier tokens as they are.
+ * Synchronises.  0 ok; < 0 error (n_embd differs from the model's, null context). */
+int32_t mi_ctx_apply_cvec(mi_ctx* ctx, const float* data, size_t len, int32_t n_embd, int32_t il_start,
+                          int32_t il_end);
+/* The control-vector file loader (ControlVector.cpp:20-98, loadControlVector): every tensor of the
+ * GGUF must be named direction.N (N >= 1), F32 and 1-D, all of one length n_embd;
+ * data[n_embd*(N-1) + j] += src[j] * strength (tensors of one N accumulate, and so do several
+ * files loaded into one zero-initialised buffer: ControlVector.cpp:105-127).  Returns the floats
+ * needed, n_embd * max N, and writes data only when cap (floats) is at least that; data NULL is a
+ * size query.  *n_embd (optional) receives the tensors' length.  < 0: unreadable file, a tensor
+ * that is not direction.N with N >= 1, not F32, not 1-D, or of another length than the first. */
+int64_t mi_cvec_load(const char* gguf_path, float strength, float* data, size_t cap, int32_t* n_embd);
+
 /* ---- measurement: HIP events on the context's stream bracketing the FFN
  * gate/up GEMV launch of `layer` in every output-producing decode step (the
  * step's graph is split in three around it); layer < 0 disables.
