@@ -21,6 +21,7 @@ using namespace mi;
 
 struct mi_model { Model impl; };
 struct mi_ctx { std::unique_ptr<Ctx> impl; };
+struct mi_lora { std::shared_ptr<Lora> impl; };
 
 #define MI_TRY(fail) catch (const std::exception& e) { set_last_error(e.what()); return fail; } \
                      catch (...) { set_last_error("unknown error"); return fail; }
@@ -557,6 +558,67 @@ int64_t mi_cvec_load(const char* path, float strength, float* data, size_t cap, 
         return need;
     }
     MI_TRY(-1)
+}
+
+// ---- LoRA adapters (lora.cpp) ----
+mi_lora* mi_lora_load_from_memory(mi_model* model, const void* data, size_t size) {
+    try {
+        set_last_error("");
+        if (!model) throw Error("null model");
+        if (!data) throw Error("null adapter image");
+        std::unique_ptr<mi_lora> a(new mi_lora());
+        a->impl = Lora::load(&model->impl, static_cast<const uint8_t*>(data), size);
+        return a.release();
+    }
+    MI_TRY(nullptr)
+}
+
+mi_lora* mi_lora_load(mi_model* model, const char* path) {
+    try {
+        if (!path) throw Error("null path");
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) throw Error(std::string("cannot open ") + path);
+        struct stat st;
+        if (fstat(fd, &st) != 0) { ::close(fd); throw Error("fstat failed"); }
+        const size_t size = (size_t)st.st_size;
+        if (size == 0) { ::close(fd); throw Error(std::string("empty file ") + path); }
+        void* map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        ::close(fd);
+        if (map == MAP_FAILED) throw Error(std::string("mmap failed for ") + path);
+        mi_lora* a = mi_lora_load_from_memory(model, map, size);
+        munmap(map, size);
+        return a;
+    }
+    MI_TRY(nullptr)
+}
+
+void mi_lora_free(mi_lora* a) { delete a; }
+float mi_lora_alpha(const mi_lora* a) { return a ? a->impl->alpha : 0.0f; }
+int32_t mi_lora_n_pairs(const mi_lora* a) { return a ? (int32_t)a->impl->pairs.size() : -1; }
+
+int32_t mi_ctx_set_lora(mi_ctx* c, mi_lora* a, float scale) {
+    try {
+        if (!c) throw Error("null ctx");
+        if (!a) throw Error("null adapter");
+        c->impl->set_lora(a->impl, scale);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+int32_t mi_ctx_rm_lora(mi_ctx* c, mi_lora* a) {
+    try {
+        if (!c) throw Error("null ctx");
+        if (!a) throw Error("null adapter");
+        if (a->impl->m != c->impl->m) throw Error("rm_lora: the adapter belongs to another model");
+        if (c->impl->rm_lora(a->impl.get()) != 0) throw Error("rm_lora: the adapter is not set on this context");
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+void mi_ctx_clear_lora(mi_ctx* c) {
+    try { if (c) c->impl->clear_lora(); } catch (const std::exception& e) { set_last_error(e.what()); }
 }
 
 int32_t mi_prof_enable(mi_ctx* c, int32_t layer) {

@@ -21,7 +21,7 @@
 //    the dv_quant launches; profiles/r06_hq_ab.txt, r06_nq_ab.txt); an Infinity-Cache prefetch of the next layer's weights from a side stream slowed the
 //    chain 1.7-2.6x.
 //    Every sum is taken in a fixed order: results are bit-reproducible.
-#include "qdot.h"
+#include "lora.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -66,6 +66,7 @@ struct DvArgs {
     const float* freq_factors;
     float theta_scale, freq_scale;
     int n_rot, head_dim, kv_dim;
+    const LoraFold* lora[2];    // DV_QKV / DV_SWIGLU / DV_ADD, optional (GemvSeg::lora of each segment)
 };
 
 __device__ __forceinline__ void dv_lds_barrier() {
@@ -75,7 +76,9 @@ __device__ __forceinline__ void dv_lds_barrier() {
 
 // One workgroup's work for segment SI of type T.  RW: rows per unit (2: DV_QKV RoPE pairs /
 // DV_SWIGLU gate-up pairs); C: 8-superblock chunks per row (ceil(K / 2048)).
-template <int T, int SI, int RW, int C, int ROLE0>
+// LORA: the instantiation that adds a context's adapter terms (launched only when a segment has
+// them: the no-adapter kernels carry no trace of the branch)
+template <int T, int SI, int RW, int C, int ROLE0, bool LORA>
 __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     constexpr int ROLE = dv_base(ROLE0);
     using K = Kq<T>;
@@ -229,6 +232,24 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
         y[r] = wave_sum63(acc);
     }
 
+    // ---- 4b. a LoRA adapter's term, before the epilogue: y += B (s A cur) by the whole wave
+    // (a segment of the launch without one: uniform branch)
+    if constexpr (LORA && (ROLE == DV_QKV || ROLE == DV_SWIGLU || ROLE == DV_ADD)) {
+        const LoraFold* Fp = a.lora[SI];
+        if (Fp) {
+            const LoraFold& F = *Fp;
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                if (ROLE != DV_QKV) {   // SwiGLU: ranges gate, up; the residual launch: its one range
+                    y[r] = lora_fold_wave(F, r, uc, 0, lane, y[r]);
+                } else if (r0 + r < S.rows) {
+                    const int range = isq ? 0 : isk ? 1 : 2;
+                    y[r] = lora_fold_wave(F, range, r0 + r - (isq ? 0 : isk ? S.nq : S.nq + S.nk), 0, lane, y[r]);
+                }
+            }
+        }
+    }
+
     // ---- 5. epilogue (lane 63)
     if (lane != 63 || !uv) return;
     if (ROLE == DV_QKV) {
@@ -269,69 +290,73 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
 }
 
 // T1: -1 one segment, else the type of segment 1 (a mixed-type Q/K/V launch)
-template <int T0, int T1, int RW, int C, int ROLE>
+template <int T0, int T1, int RW, int C, int ROLE, bool LORA>
 __global__ __launch_bounds__(DV_NW * 64) void dgemv_kernel(const DvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    if (T1 < 0 || (int)blockIdx.x < a.seg[1].blk0) dv_body<T0, 0, RW, C, ROLE>(a, lds);
-    else dv_body<(T1 < 0 ? T0 : T1), 1, RW, C, ROLE>(a, lds);
+    if (T1 < 0 || (int)blockIdx.x < a.seg[1].blk0) dv_body<T0, 0, RW, C, ROLE, LORA>(a, lds);
+    else dv_body<(T1 < 0 ? T0 : T1), 1, RW, C, ROLE, LORA>(a, lds);
 }
 
 typedef void (*DvFn)(const DvArgs);
 
 // chunks per row: K <= 2048 -> 1, 4096 -> 2, 8192 -> 4 (the n_embd-wide inputs); the FFN down
 // input (n_ff) also 3 (5632), 6 (11008), 7 (14336)
-template <int T0, int T1, int RW, int ROLE>
+template <int T0, int T1, int RW, int ROLE, bool LORA>
 DvFn dv_fn_c(int c) {
     switch (c) {
-    case 1: return dgemv_kernel<T0, T1, RW, 1, ROLE>;
-    case 2: return dgemv_kernel<T0, T1, RW, 2, ROLE>;
-    case 4: return dgemv_kernel<T0, T1, RW, 4, ROLE>;
+    case 1: return dgemv_kernel<T0, T1, RW, 1, ROLE, LORA>;
+    case 2: return dgemv_kernel<T0, T1, RW, 2, ROLE, LORA>;
+    case 4: return dgemv_kernel<T0, T1, RW, 4, ROLE, LORA>;
     default: break;
     }
     if constexpr (dv_base(ROLE) == DV_ADD) {
         switch (c) {
-        case 3: return dgemv_kernel<T0, T1, RW, 3, ROLE>;
-        case 6: return dgemv_kernel<T0, T1, RW, 6, ROLE>;
-        case 7: return dgemv_kernel<T0, T1, RW, 7, ROLE>;
+        case 3: return dgemv_kernel<T0, T1, RW, 3, ROLE, LORA>;
+        case 6: return dgemv_kernel<T0, T1, RW, 6, ROLE, LORA>;
+        case 7: return dgemv_kernel<T0, T1, RW, 7, ROLE, LORA>;
         default: break;
         }
     }
     return nullptr;
 }
-template <int T0, int ROLE>
+template <int T0, int ROLE, bool LORA>
 DvFn dv_fn_t1(int t1, int c) {
     constexpr int RW = (dv_base(ROLE) == DV_QKV || dv_base(ROLE) == DV_SWIGLU) ? 2 : 1;
-    if (t1 < 0) return dv_fn_c<T0, -1, RW, ROLE>(c);
+    if (t1 < 0) return dv_fn_c<T0, -1, RW, ROLE, LORA>(c);
     if constexpr (dv_base(ROLE) == DV_QKV) {   // mixed-type Q/K/V launches only
         switch (t1) {
-        case T_Q6_K: return dv_fn_c<T0, T_Q6_K, RW, ROLE>(c);
-        case T_Q8_0: return dv_fn_c<T0, T_Q8_0, RW, ROLE>(c);
+        case T_Q6_K: return dv_fn_c<T0, T_Q6_K, RW, ROLE, LORA>(c);
+        case T_Q8_0: return dv_fn_c<T0, T_Q8_0, RW, ROLE, LORA>(c);
         default: return nullptr;
         }
     }
     return nullptr;
 }
-template <int ROLE>
+template <int ROLE, bool LORA>
 DvFn dv_fn_role(int t0, int t1, int c) {
     switch (t0) {
-    case T_Q4_K: return dv_fn_t1<T_Q4_K, ROLE>(t1, c);
-    case T_Q5_K: return dv_fn_t1<T_Q5_K, ROLE>(t1, c);
-    case T_Q6_K: return t1 == T_Q6_K ? nullptr : dv_fn_t1<T_Q6_K, ROLE>(t1, c);
-    case T_Q8_0: return t1 >= 0 ? nullptr : dv_fn_t1<T_Q8_0, ROLE>(t1, c);
+    case T_Q4_K: return dv_fn_t1<T_Q4_K, ROLE, LORA>(t1, c);
+    case T_Q5_K: return dv_fn_t1<T_Q5_K, ROLE, LORA>(t1, c);
+    case T_Q6_K: return t1 == T_Q6_K ? nullptr : dv_fn_t1<T_Q6_K, ROLE, LORA>(t1, c);
+    case T_Q8_0: return t1 >= 0 ? nullptr : dv_fn_t1<T_Q8_0, ROLE, LORA>(t1, c);
     default: return nullptr;
     }
 }
-DvFn dv_fn(int role, int t0, int t1, int c) {
+template <bool LORA>
+DvFn dv_fn_l(int role, int t0, int t1, int c) {
     switch (role) {
-    case DV_QKV: return dv_fn_role<DV_QKV>(t0, t1, c);
-    case DV_ADD: return dv_fn_role<DV_ADD>(t0, t1, c);
-    case DV_ADDQ: return dv_fn_role<DV_ADDQ>(t0, t1, c);
-    case DV_QKVN: return c <= 4 ? dv_fn_role<DV_QKVN>(t0, t1, c) : nullptr;
-    case DV_SWIGLUN: return c <= 4 ? dv_fn_role<DV_SWIGLUN>(t0, t1, c) : nullptr;
-    case DV_SWIGLU: return dv_fn_role<DV_SWIGLU>(t0, t1, c);
-    case DV_STORE: return dv_fn_role<DV_STORE>(t0, t1, c);
+    case DV_QKV: return dv_fn_role<DV_QKV, LORA>(t0, t1, c);
+    case DV_ADD: return dv_fn_role<DV_ADD, LORA>(t0, t1, c);
+    case DV_ADDQ: return dv_fn_role<DV_ADDQ, LORA>(t0, t1, c);
+    case DV_QKVN: return c <= 4 ? dv_fn_role<DV_QKVN, LORA>(t0, t1, c) : nullptr;
+    case DV_SWIGLUN: return c <= 4 ? dv_fn_role<DV_SWIGLUN, LORA>(t0, t1, c) : nullptr;
+    case DV_SWIGLU: return dv_fn_role<DV_SWIGLU, LORA>(t0, t1, c);
+    case DV_STORE: return LORA ? nullptr : dv_fn_role<DV_STORE, false>(t0, t1, c);
     default: return nullptr;
     }
+}
+DvFn dv_fn(int role, int t0, int t1, int c, bool lora = false) {
+    return lora ? dv_fn_l<true>(role, t0, t1, c) : dv_fn_l<false>(role, t0, t1, c);
 }
 int dv_chunks(int K) {
     const int c = (K / 256 + 7) / 8;
@@ -427,8 +452,10 @@ bool dgemv_supported(const GemvParams& p) {
     const int role = dv_role(p);
     if (role < 0 || g.bias || g.expA >= 0 || g.expB >= 0) return false;
     if (g.addend && dv_base(role) != DV_ADD) return false;
+    bool lora = false;
+    for (int i = 0; i < p.nseg; ++i) lora = lora || p.seg[i].lora;
     if (p.nseg == 2 && (dv_base(role) != DV_QKV || p.seg[1].epi != EPI_QKV)) return false;
-    return dv_fn(role, g.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K)) != nullptr;
+    return dv_fn(role, g.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K), lora) != nullptr;
 }
 
 void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -460,6 +487,7 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
         o.blk0 = blk;
         o.nblk = (o.units + DV_NW - 1) / DV_NW;
         blk += o.nblk;
+        a.lora[i] = g.lora;
     }
     if (p.nseg == 1) a.seg[1].blk0 = blk;
     a.act = p.act_in;
@@ -487,7 +515,7 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
     if (role0 == DV_ADDQ && p.K > DV_NW * 256 * dv_chunks(p.K)) throw Error("dgemv: activation too long to quantise in-launch");
     if (role == DV_ADD && !g0.resid) throw Error("dgemv: residual epilogue without resid");
     if (role == DV_QKV && !p.tokpos) throw Error("dgemv: QKV epilogue needs tokpos");
-    const DvFn fn = dv_fn(role0, g0.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K));
+    const DvFn fn = dv_fn(role0, g0.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K), a.lora[0] || a.lora[1]);
     const size_t smem = actb + (role0 == DV_QKVN || role0 == DV_SWIGLUN ? 4 * sizeof(double) : 0);
     if (ev_start || ev_stop)
         hipExtLaunchKernelGGL(fn, dim3(blk), dim3(DV_NW * 64), smem, s, ev_start, ev_stop, 0, a);

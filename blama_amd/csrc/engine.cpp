@@ -8,6 +8,7 @@
 //   llama_kv_self_*             /root/reference/inference/code/llama/Session.cpp:53,341-361
 //   llama_state_*               /root/reference/inference/code/llama/Session.cpp:291-304
 //   llama_apply_adapter_cvec    /root/reference/inference/code/llama/Instance.cpp:74
+//   llama_set_adapter_lora      /root/reference/inference/code/llama/Instance.cpp:52-61 (lora.cpp)
 #include "engine.h"
 
 #include <atomic>
@@ -356,7 +357,7 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
     }
     p.kcache = kcache + (size_t)l * n_ctx * kv_dim;
     p.vcache = vcache + (size_t)l * n_ctx * kv_dim;
-    int n = 0;
+    int n = 0, row0 = 0;   // row0: the group's first row among [Q | K | V]
     for (int g = 0; g < L.n_qkv; ++n) {
         p.nseg = 0;
         for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
@@ -366,6 +367,11 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
             sg.nq = L.qkv_nq[g];
             sg.nk = L.qkv_nk[g];
             sg.bias = L.bqkv;   // GPT-2 (its one fused group)
+            // LoRA: folded into the streaming launch (ranges Q, K, V: a segment picks its own);
+            // gemv_kernel adds the term precomputed in lora_pre, rows [Q | K | V]
+            if (src != ACT_PRO) sg.lora = lora_fold(l, 0);
+            else if (lora_group(l, 0)) sg.pre = lora_pre + row0;
+            row0 += L.qkv[g].rows;
         }
         out[n] = p;
     }
@@ -415,6 +421,8 @@ GemvParams Ctx::wo_params(int l, ActSrc src) const {
     p.seg[0] = seg_of(L.wo, PAIR_ADJ, EPI_ADD, x);
     p.seg[0].resid = x;
     p.seg[0].bias = L.bo;
+    if (src != ACT_PRO) p.seg[0].lora = lora_fold(l, 1);   // LoRA: before the residual add
+    else if (lora_group(l, 1)) p.seg[0].pre = lora_pre;
     return p;
 }
 
@@ -443,6 +451,11 @@ GemvParams Ctx::gate_up_params(int l, ActSrc src) const {
         p.seg[k] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
         p.seg[k].B = L.up;
         if (moe) p.seg[k].expA = p.seg[k].expB = k;
+        else if (src != ACT_PRO) p.seg[k].lora = lora_fold(l, 2);   // ranges gate, up
+        else if (lora_group(l, 2)) {
+            p.seg[k].pre = lora_pre;   // [gate rows | up rows]
+            p.seg[k].pre_up = hp.n_ff;
+        }
     }
     return p;
 }
@@ -467,6 +480,8 @@ GemvParams Ctx::down_params(int l, ActSrc src) const {
     } else {
         p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
         p.seg[0].bias = L.bdown;
+        if (src != ACT_PRO) p.seg[0].lora = lora_fold(l, 3);
+        else if (lora_group(l, 3)) p.seg[0].pre = lora_pre;
     }
     p.seg[0].resid = x;
     p.seg[0].addend = cvec_for(l);   // build_cvec: after the FFN residual add
@@ -602,19 +617,31 @@ void Ctx::enqueue_step_sp(bool with_logits) {
     };
     quant_x_for(0);
     for (int l = 0; l < hp.n_layer; ++l) {
+        // LoRA (build_lora_mm): one shrink per activation an adapter reads -- rms_norm(x) * norm_w
+        // rebuilt from x (the step keeps it only quantised), the attention output, h -- its B product
+        // folded into the consuming launch, ahead of its epilogue
+        const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
+        if (lq) lora_shrink(*lq, x, hp.n_embd, hp.n_embd, 1, m->layers[l].attn_norm);
         GemvParams qkv[3];
         const int n = qkv_params(l, in, qkv);
         for (int i = 0; i < n; ++i) run_gemv(qkv[i]);
-        run_attn(attn_params(l, true));
-        if (!attn_fused && seg_on())
+        AttnParams ap = attn_params(l, true);
+        if (lo && attn_fused) ap.out_f32 = part_o;   // the fp32 output too: split 0's slot
+        run_attn(ap);
+        if (!attn_fused && seg_on()) {
             launch_attn_combine_quant(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos,
                                       act_out(1, sp[l].fB, hp.n_embd, nullptr), stream);
+            if (lo) launch_attn_combine(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos, attn, stream);
+        }
+        if (lo) lora_shrink(*lo, attn_fused ? part_o : attn, hp.n_embd, hp.n_embd, 1, nullptr);
         run_gemv(wo_params(l, ACT_QUANT));
         if (moe) {
             enqueue_moe_ffn(l);
         } else {
+            if (lg) lora_shrink(*lg, x, hp.n_embd, hp.n_embd, 1, m->layers[l].ffn_norm);
             if (!sp_nq_in) quant(x, act_out(2, sp[l].fC, hp.n_embd, m->layers[l].ffn_norm));
             run_gemv(gate_up_params(l, in), l, true);
+            if (ld) lora_shrink(*ld, h, hp.n_ff, hp.n_ff, 1, nullptr);
             if (!sp_hq_down) quant(h, act_out(3, sp[l].fD, hp.n_ff, nullptr));
             run_gemv(down_params(l, sp_hq_down ? ACT_RAW : ACT_QUANT));
         }
@@ -634,15 +661,37 @@ void Ctx::enqueue_step(bool with_logits) {
         enqueue_step_sp(with_logits);
     } else {
         for (int l = 0; l < hp.n_layer; ++l) {
+            // LoRA on gemv_kernel (dense LLaMA geometries the streaming step does not serve): the
+            // terms precomputed into lora_pre ahead of the launch that adds them before its epilogue
+            const Layer& L = m->layers[l];
+            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
+            if (lq) {
+                const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows}, rows[3] = {L.wq.rows, L.wk.rows, L.wv.rows};
+                lora_shrink(*lq, x, hp.n_embd, hp.n_embd, 1, L.attn_norm);
+                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, rows[i], 1);
+            }
             GemvParams qkv[3];
             const int n = qkv_params(l, ACT_PRO, qkv);
             for (int i = 0; i < n; ++i) run_gemv(qkv[i]);
             run_attn(attn_params(l, false));
+            if (lo) {   // the attention output in fp32: the fused launch's one split, or the splits' sum
+                if (!attn_fused && seg_on()) launch_attn_combine(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos, attn, stream);
+                lora_shrink(*lo, attn_fused ? part_o : attn, hp.n_embd, hp.n_embd, 1, nullptr);
+                lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, 1);
+            }
             run_gemv(wo_params(l, ACT_PRO));
             if (hp.n_expert > 0) {
                 enqueue_moe_ffn(l);
             } else {
+                if (lg) {
+                    lora_shrink(*lg, x, hp.n_embd, hp.n_embd, 1, L.ffn_norm);
+                    for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, 1);
+                }
                 run_gemv(gate_up_params(l, ACT_PRO), l, true);
+                if (ld) {
+                    lora_shrink(*ld, h, hp.n_ff, hp.n_ff, 1, nullptr);
+                    lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, 1);
+                }
                 run_gemv(down_params(l, ACT_PRO));
             }
         }
@@ -733,6 +782,12 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
             // Q / K / V projections (+ RoPE, KV append)
             const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
             const int epis[3] = {EPI_ROPE_Q, EPI_ROPE_K, EPI_V};
+            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
+            const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows};
+            if (lq) {   // LoRA: the Q/K/V terms of the chunk, added before RoPE and the KV append
+                lora_shrink(*lq, xb, hp.n_embd, hp.n_embd, nt, L.attn_norm);
+                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, mats[i]->rows, nt);
+            }
             for (int i = 0; i < 3; ++i) {
                 GemmParams p = b;
                 p.A = *mats[i];
@@ -743,22 +798,39 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
                 p.out = qb;
                 p.out_stride = hp.n_embd;
                 p.n_rot = i < 2 ? hp.n_rot : 0;
+                if (lq) {
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                    p.pre_off = prow[i];
+                }
                 proj(p, xb, hp.n_embd, L.attn_norm, i == 0);   // the three share one quantisation
             }
             AttnParams a{qb, kl, vl, tokpos_b, cell_pos, attn_scores, attn_smax, attnb, hp.n_head, hp.n_head_kv,
                          hp.head_dim, kv_dim, (int)n_ctx, kq_scale};
             launch_attn_multi(a, nt, attnb, stream);
+            if (lo) {
+                lora_shrink(*lo, attnb, hp.n_embd, hp.n_embd, nt, nullptr);
+                lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
+            }
             {   // output projection + residual
                 GemmParams p = b;
                 p.A = L.wo;
                 p.pair = PAIR_ADJ;
                 p.epi = EPI_ADD;
+                if (lo) {
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                }
                 p.units = (L.wo.rows + 1) / 2;
                 p.K = hp.n_embd;
                 p.out = xb;
                 p.resid = xb;
                 p.out_stride = hp.n_embd;
                 proj(p, attnb, hp.n_embd, nullptr, true);
+            }
+            if (lg) {   // the gate and up terms, added before SwiGLU
+                lora_shrink(*lg, xb, hp.n_embd, hp.n_embd, nt, L.ffn_norm);
+                for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, nt);
             }
             {   // FFN gate/up + SwiGLU
                 GemmParams p = b;
@@ -770,13 +842,26 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
                 p.K = hp.n_embd;
                 p.out = hb;
                 p.out_stride = hp.n_ff;
+                if (lg) {
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                    p.pre_up = hp.n_ff;
+                }
                 proj(p, xb, hp.n_embd, L.ffn_norm, true);
+            }
+            if (ld) {
+                lora_shrink(*ld, hb, hp.n_ff, hp.n_ff, nt, nullptr);
+                lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
             }
             {   // FFN down + residual
                 GemmParams p = b;
                 p.A = L.down;
                 p.pair = PAIR_ADJ;
                 p.epi = EPI_ADD;
+                if (ld) {
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                }
                 p.units = (L.down.rows + 1) / 2;
                 p.K = hp.n_ff;
                 p.out = xb;
@@ -925,7 +1010,10 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             pos_max = pos;
         }
         MI_HIP(hipMemcpyAsync(tokpos_b, hpos, nt * 4 * sizeof(int), hipMemcpyHostToDevice, stream));
-        if (mmqs_max > 0 && nt <= mmqs_max && short_ok()) {   // a short batch (its launches captured as a
+        // (a context with a LoRA adapter runs its short batches on the tiled form below, whose
+        // epilogues take the adapter's terms; split-K is off for the W_o / down launches an adapter
+        // targets, and pending parts are added by the quant_act that precedes every shrink)
+        if (mmqs_max > 0 && nt <= mmqs_max && short_ok() && !lora_on()) {   // a short batch (its launches captured as a
             // hipGraph measured no faster: the GPU, not the enqueue, sets the pace)
             enqueue_ubatch_short(nt, all, c0, c0 + nt == n);
             continue;
@@ -968,6 +1056,12 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                     pend = nullptr;
                 }
             }
+            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
+            const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows};
+            if (lq) {   // LoRA: the Q/K/V terms of the batch, added before RoPE and the KV append
+                lora_shrink(*lq, xb, hp.n_embd, hp.n_embd, nt, L.attn_norm);
+                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, mats[i]->rows, nt);
+            }
             // the matrices of one type in one launch (7B: Q/K/V, or Q/K plus a Q6_K V)
             for (int i = 0; i < 3; ++i) {
                 bool first = true;
@@ -982,6 +1076,11 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                     ps[n].pair = PAIR_ADJ;
                     ps[n].epi = epis[j];
                     ps[n].out = qb;
+                    if (lq) {
+                        ps[n].pre = lora_pre;
+                        ps[n].pre_stride = lora_pre_stride;
+                        ps[n].pre_off = prow[j];
+                    }
                     ++n;
                 }
                 launch_mmq32_multi(ps, n, ub_act(hp.n_embd, nt, mats[i]->type), ub_rope, stream);
@@ -994,12 +1093,20 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                 const ActQ8 act = ub_act(hp.n_embd, nt, L.wo.type);
                 launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act, stream);
                 GemmParams p = b;
+                if (lo) {   // before the residual add
+                    lora_shrink(*lo, attnb, hp.n_embd, hp.n_embd, nt, nullptr);
+                    lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                }
                 p.A = L.wo;
                 p.pair = PAIR_ADJ;
                 p.epi = EPI_ADD;
                 p.out = xb;
                 p.resid = xb;
-                if (ub_part && L.wo.nb >= ks) {   // parts of K; the FFN's quant_act adds them
+                // parts of K; the FFN's quant_act adds them (not with an adapter on this W_o: its terms
+                // go in ahead of the residual add, which a split launch leaves to the next kernel)
+                if (ub_part && L.wo.nb >= ks && !lo) {
                     p.ksplit = ks;
                     p.part = ub_part;
                     pend = ub_part;
@@ -1022,19 +1129,32 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                 p.epi = EPI_SWIGLU;
                 p.out = hb;
                 p.out_stride = hp.n_ff;
+                if (lg) {   // the gate and up terms, added before SwiGLU
+                    lora_shrink(*lg, xb, hp.n_embd, hp.n_embd, nt, L.ffn_norm);
+                    for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, nt);
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                    p.pre_up = hp.n_ff;
+                }
                 launch_mmq32(p, act, ub_rope, stream);
             }
             {   // FFN down + residual
                 const ActQ8 act = ub_act(hp.n_ff, nt, L.down.type);
                 launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, act, stream);
                 GemmParams p = b;
+                if (ld) {
+                    lora_shrink(*ld, hb, hp.n_ff, hp.n_ff, nt, nullptr);
+                    lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
+                    p.pre = lora_pre;
+                    p.pre_stride = lora_pre_stride;
+                }
                 p.A = L.down;
                 p.pair = PAIR_ADJ;
                 p.epi = EPI_ADD;
                 p.K = hp.n_ff;
                 p.out = xb;
                 p.resid = xb;
-                if (ub_part && L.down.nb >= ks && l + 1 < hp.n_layer) {   // the next layer's quant_act adds them
+                if (ub_part && L.down.nb >= ks && l + 1 < hp.n_layer && !ld) {   // the next layer's quant_act adds them
                     p.ksplit = ks;
                     p.part = ub_part;
                     pend = ub_part;

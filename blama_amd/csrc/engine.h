@@ -120,6 +120,26 @@ struct Model {
     const QMat* find_qmat(const std::string& name) const;
 };
 
+// ---------------------------------------------------------------- LoRA ----
+// A LoRA adapter file (llama_adapter_lora_init, src/llama-adapter.cpp b5187), parsed and validated
+// against its base model (lora.cpp).  It keeps the pairs as they stand in the file; a context that
+// is given the adapter builds its device stacks from them (Ctx::lora_rebuild) and shares ownership,
+// so the handle may be freed while a context still uses it.
+enum LoraTarget { LT_Q = 0, LT_K, LT_V, LT_O, LT_GATE, LT_UP, LT_DOWN, LT_N };
+struct LoraPair {
+    int layer = 0, target = 0;
+    int r = 0, K = 0, rows = 0;          // A [r][K], B [rows][r] (row-major, as in the file)
+    int a_type = T_F32, b_type = T_F32;  // T_F16 or T_F32
+    std::vector<uint8_t> a, b;           // empty for a vocab_only model (validation only)
+};
+struct Lora {
+    const Model* m = nullptr;
+    float alpha = 0.0f;
+    std::vector<LoraPair> pairs;
+    // throws Error naming the tensor or the reason
+    static std::shared_ptr<Lora> load(const Model* m, const uint8_t* data, size_t size);
+};
+
 // ------------------------------------------------------------- context ----
 int dev_chain_contexts(int device);   // live contexts on the device
 
@@ -227,6 +247,41 @@ struct Ctx {
     // n_layer - 1)] with il * n_embd <= len carries data[(il - 1) * n_embd ..).  Synchronises the
     // stream and drops the captured decode graphs (their launches hold the old arguments).
     void apply_cvec(const float* data, size_t len, int n_embd, int il_start, int il_end);
+    // LoRA adapters (llama_set_adapter_lora / llama_rm_adapter_lora / llama_clear_adapter_lora): a
+    // property of the context like the control vector.  The adapters set are stacked into one
+    // adapter of concatenated rank per base tensor; the tensors that read one activation -- group
+    // 0: Q, K, V; 1: attn_output; 2: gate, up; 3: ffn_down -- share one A stack and one shrink launch.
+    struct LoraSet {
+        std::shared_ptr<Lora> a;
+        float scale;
+    };
+    struct LoraGroup {
+        void* A = nullptr;              // [R][K]
+        int a_f16 = 0, R = 0;
+        unsigned char* rnd = nullptr;   // [R]
+        void* B[3] = {nullptr, nullptr, nullptr};   // the group's tensors: [rows][Rt[i]]
+        int Rt[3] = {0, 0, 0}, off[3] = {0, 0, 0}, b_f16[3] = {0, 0, 0};
+        int* tab[3] = {nullptr, nullptr, nullptr};  // LoraFold::tab of each tensor
+    };
+    std::vector<LoraSet> loras;
+    std::vector<LoraGroup> lora_g;      // [n_layer][4]; empty: no adapter
+    char* lora_mem = nullptr;           // the stacks
+    float* lora_t = nullptr;            // [kBatchRows][3 * LORA_MAX_RANK]: the shrink's output
+    float* lora_pre = nullptr;          // batches: [kBatchRows][max(Q|K|V rows, 2 n_ff)] (GemmParams::pre)
+    int lora_pre_stride = 0;
+    bool lora_on() const { return !lora_g.empty(); }
+    const LoraGroup* lora_group(int l, int g) const {
+        return !lora_g.empty() && lora_g[(size_t)l * 4 + g].R ? &lora_g[(size_t)l * 4 + g] : nullptr;
+    }
+    void set_lora(const std::shared_ptr<Lora>& a, float scale);
+    int rm_lora(const Lora* a);          // 0, or -1 when not set
+    void clear_lora();
+    void lora_rebuild();                // synchronises, drops the graphs, rebuilds the stacks of `loras`
+    LoraFold* lora_folds = nullptr;     // [n_layer][4] on the device: the groups' LoraFold (GemvSeg::lora)
+    const LoraFold* lora_fold(int l, int g) const { return lora_group(l, g) ? lora_folds + (size_t)l * 4 + g : nullptr; }
+    void lora_shrink(const LoraGroup& G, const float* xin, int x_stride, int K, int ntok, const float* norm_w);
+    // tensor i of the group: out[tok][row] = its terms (zeros when it has no adapter)
+    void lora_expand(const LoraGroup& G, int i, float* out, int out_stride, int rows, int ntok);
     // diagnostics (MI_STAMPS builds only): s_memrealtime stamps of every
     // workgroup of every launch of the last enqueued step [launch][wg][8]
     static constexpr int kStampLaunches = 320, kStampWgs = 512;

@@ -41,7 +41,8 @@ struct GvSeg {
     const uint8_t* b[4];        // PAIR_AB: planes of B
     float* out;
     const float* resid;
-    const float* bias;          // optional per-row bias (GPT-2 projections)
+    const float* bias;          // optional per-row bias (GPT-2 projections); the PRE variants: GemvSeg::pre
+                                // (a SwiGLU pair's pre_up travels in nq, which it does not use)
     const float* addend;        // optional, EPI_ADD / EPI_MOE_DOWN: added after the residual
     int units, blk0, nblk, rows;
     int epi, nq, nk, expA, expB, actB;
@@ -212,7 +213,10 @@ template <bool P> __device__ __forceinline__ void gst(int* p, int v) {
 //       (the grid barrier that publishes the previous stage's outputs), the activation and the
 //       residuals are loaded after it, and every output is stored write-through (agent scope)
 //   ND  the launch has one activation slot (the FFN gate/up launch): no second-slot paths
-template <int T, int SI, int RW, int KB, int D, bool GX, bool P = false, typename Wait = GvNoWait, bool ND = false>
+// PRE: the instantiation that adds a LoRA adapter's precomputed terms before the epilogue (launched
+// only for a segment that has them: the other kernels carry no trace of the branch)
+template <int T, int SI, int RW, int KB, int D, bool GX, bool P = false, typename Wait = GvNoWait, bool ND = false,
+          bool PRE = false>
 __device__ __forceinline__ void gv_body(const GvArgs& a, char* lds, Wait&& wait = Wait()) {
     using K = Kq<T>;
     constexpr bool Q80 = gv_q80<T>();
@@ -772,6 +776,17 @@ __device__ __forceinline__ void gv_body(const GvArgs& a, char* lds, Wait&& wait 
             if (lane == 63) {
                 const long long u = u_first + (long long)cu * stride;
                 float* const out = S.out;
+                if constexpr (PRE) {
+                    if (S.bias) {   // (a segment of the launch without terms: uniform)
+                        if (ab) {
+                            y[0] += gptr(S.bias)[u];
+                            y[RW - 1] += gptr(S.bias)[S.nq + u];
+                        } else {
+                            y[0] += gptr(S.bias)[u * RW];
+                            if (RW == 2 && u * RW + 1 < S.rows) y[RW - 1] += gptr(S.bias)[u * RW + 1];
+                        }
+                    }
+                }
                 if (ab) {
                     if (epi == EPI_SWIGLU) gst<P>(out + u, silu_f(y[0]) * y[RW - 1]);
                     else {   // EPI_MOE_DOWN
@@ -877,8 +892,10 @@ template <int T0, int T1, int RW, int KB, int D, int TAG>
 __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const GvArgs ka) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const GvArgs a = gv_args_fetch(ka);
-    if (T1 == -1 || (int)blockIdx.x < a.seg[1].blk0) gv_body<T0, 0, RW, KB, D, TAG == 2, false, GvNoWait, TAG == 1>(a, lds);
-    else gv_body<(T1 < 0 ? T0 : T1), 1, RW, KB, D, TAG == 2, false, GvNoWait, TAG == 1>(a, lds);
+    // TAG 3 / 4: TAG 0 / 1 with a LoRA adapter's precomputed terms (PRE)
+    if (T1 == -1 || (int)blockIdx.x < a.seg[1].blk0)
+        gv_body<T0, 0, RW, KB, D, TAG == 2, false, GvNoWait, TAG == 1 || TAG == 4, TAG >= 3>(a, lds);
+    else gv_body<(T1 < 0 ? T0 : T1), 1, RW, KB, D, TAG == 2, false, GvNoWait, TAG == 1 || TAG == 4, TAG >= 3>(a, lds);
 }
 
 typedef void (*GvFn)(const GvArgs);
@@ -906,10 +923,12 @@ template <int T0, int RW>
 GvFn gv_fn_pair(int t1, int kb, int tag) {
     switch (t1) {
     case -1: return tag == 2 ? gv_fn_kb<T0, -1, RW, 2>(kb)
+                  : tag == 4 ? (RW == 2 ? gv_fn_kb<T0, -1, RW, 4>(kb) : gv_fn_kb<T0, -1, RW, 3>(kb))
+                  : tag == 3 ? gv_fn_kb<T0, -1, RW, 3>(kb)
                   : tag && RW == 2 ? gv_fn_kb<T0, -1, RW, 1>(kb) : gv_fn_kb<T0, -1, RW, 0>(kb);
-    case -2: return gv_fn_kb<T0, -2, RW, 0>(kb);
-    case T_Q6_K: return gv_fn_kb<T0, T_Q6_K, RW, 0>(kb);
-    case T_Q8_0: return gv_fn_kb<T0, T_Q8_0, RW, 0>(kb);
+    case -2: return tag >= 3 ? gv_fn_kb<T0, -2, RW, 3>(kb) : gv_fn_kb<T0, -2, RW, 0>(kb);
+    case T_Q6_K: return tag >= 3 ? gv_fn_kb<T0, T_Q6_K, RW, 3>(kb) : gv_fn_kb<T0, T_Q6_K, RW, 0>(kb);
+    case T_Q8_0: return tag >= 3 ? gv_fn_kb<T0, T_Q8_0, RW, 3>(kb) : gv_fn_kb<T0, T_Q8_0, RW, 0>(kb);
     default: return nullptr;
     }
 }
@@ -979,7 +998,7 @@ void init_kernel_attributes() {
         for (int kb : {1, 2, 4})
             for (int t0 : types)
                 for (int t1 : {-1, t0, (int)T_Q6_K, (int)T_Q8_0}) {
-                    for (int tag = 0; tag <= 2; ++tag) {
+                    for (int tag = 0; tag <= 4; ++tag) {
                         GvFn f = t1 < 0 ? gv_fn(1, t0, t0, rw, kb, tag) : gv_fn(2, t0, t1, rw, kb, tag);
                         if (f)
                             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f),
@@ -1009,6 +1028,8 @@ static void gv_prepare(const GemvParams& p, int cap, GvArgs& a, int& grid_out, G
         if (g.epi == EPI_GELU && (!p.gelu_tab || g.pair == PAIR_AB)) throw Error("gemv: GELU epilogue needs the table, one matrix");
         if (g.bias && g.pair == PAIR_AB) throw Error("gemv: no bias on a PAIR_AB segment");
         if (g.addend && g.epi != EPI_ADD && g.epi != EPI_MOE_DOWN) throw Error("gemv: an addend goes with a residual epilogue");
+        if (g.pre && g.epi != EPI_QKV && g.epi != EPI_SWIGLU && g.epi != EPI_ADD)
+            throw Error("gemv: a pre-epilogue term goes with Q/K/V, SwiGLU or the residual add");
     }
     if (p.nseg == 2 && !gemv_pair_supported(p.seg[0].A.type, p.seg[1].A.type))
         throw Error("gemv: unsupported pair of segment types");
@@ -1025,6 +1046,12 @@ static void gv_prepare(const GemvParams& p, int cap, GvArgs& a, int& grid_out, G
     key.rw = rw2 ? 2 : 1;
     key.kb = kb;
     key.tag = gx ? 2 : (p.nseg == 1 && p.seg[0].epi == EPI_SWIGLU && p.nslots <= 1 ? 1 : 0);
+    bool pre = false;
+    for (int i = 0; i < p.nseg; ++i) pre = pre || p.seg[i].pre;
+    if (pre) {   // the variants that add a LoRA adapter's precomputed terms
+        if (gx) throw Error("gemv: LayerNorm / bias / GELU launches take no pre-epilogue term");
+        key.tag += 3;
+    }
 
     std::memset(&a, 0, sizeof(a));
     // workgroups per segment in proportion to its bytes (at least one each)
@@ -1053,6 +1080,10 @@ static void gv_prepare(const GemvParams& p, int cap, GvArgs& a, int& grid_out, G
         o.epi = g.epi;
         o.nq = g.nq;
         o.nk = g.nk;
+        if (g.pre) {
+            o.bias = g.pre;
+            if (g.pair == PAIR_AB) o.nq = g.pre_up;
+        }
         o.expA = g.expA;
         o.expB = g.expB;
         o.actB = g.actB;

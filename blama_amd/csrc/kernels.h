@@ -10,6 +10,22 @@ namespace mi {
 // activation: ggml_mul_mat of batch 1 with the CPU path's integer arithmetic (activations
 // quantised to Q8_K / Q8_0, per-block integer dots), fused with the producer's epilogue.
 enum Pair { PAIR_ADJ = 0, PAIR_AB = 1 };
+// The low-rank terms of a context's LoRA adapters (lora.hip) a decode launch adds to its rows BEFORE
+// its epilogue (build_lora_mm: y = W cur + s B (A cur), then RoPE / the KV append / SwiGLU / the
+// residual add): row r of range i gains, adapter by adapter in the order they were set,
+// f32(sum_j B[i][r][j] * t[off[i] + j]) * s over the adapter's rank rows j, t = the shrink
+// launch's A cur.  Ranges: Q, K, V of a fused Q/K/V segment; gate, up of a SwiGLU pair; range 0 of
+// a residual launch.  t null: no adapter.
+constexpr int LORA_MAX_STACK = 4;         // adapters on a context
+struct LoraFold {
+    const float* t;       // [ntok][t_stride]
+    int t_stride;
+    const void* B[3];     // range i: [rows][R[i]], F16 (f16[i]) or F32; null: the range has no adapter
+    int R[3], off[3], f16[3];
+    // range i's adapters: {n, end[LORA_MAX_STACK] (rank rows [end[a-1], end[a]) are adapter a's),
+    // s[LORA_MAX_STACK] (float bits)}, in device memory
+    const int* tab[3];
+};
 enum Epi {
     EPI_STORE = 0,    // out[r] = y
     EPI_ADD = 1,      // out[r] = y + resid[r]            (residual add, llm_build_llama)
@@ -43,6 +59,13 @@ struct GemvSeg {
     // optional per-row addend of EPI_ADD / EPI_MOE_DOWN, added AFTER the residual: out[r] = (y +
     // resid[r]) + addend[r] (a control vector's layer direction, build_cvec after the FFN residual)
     const float* addend;
+    // EPI_QKV / EPI_SWIGLU / EPI_ADD of the streaming form (dgemv.hip), optional: a LoraFold in
+    // device memory (one pointer in the launch's arguments: the no-adapter launch stays lean)
+    const LoraFold* lora;
+    // the same terms precomputed, for gemv_kernel (gemv.hip), optional: row r of the segment gains
+    // pre[r] before the epilogue (a SwiGLU pair: gate row u pre[u], up row u pre[pre_up + u])
+    const float* pre;
+    int pre_up;
 };
 
 // Attention split over cells: split s of q head h holds the partial sum
@@ -162,6 +185,11 @@ struct GemmParams {
     int out_stride;
     const float* resid;        // EPI_ADD: [ntok][out_stride] (may alias out)
     const float* addend;       // EPI_ADD, optional: [rows], out = (y + resid) + addend[row] for every token
+    // optional, every epilogue but split-K parts: y += pre[tok * pre_stride + pre_off + row] BEFORE the
+    // epilogue (a LoRA adapter's precomputed s B (A cur), lora.hip); a SwiGLU pair's up rows read
+    // pre_up elements past the gate rows'
+    const float* pre;
+    int pre_stride, pre_off, pre_up;
     const int* tokpos;         // [ntok][4] {token, pos, cell, 0}
     int* cell_pos;
     float theta_scale, freq_scale;
@@ -235,6 +263,8 @@ struct AttnParams {
     int long_off;                  // 1: never the single launch (an exchange timed out before)
     ActOut act_out;                // fused kernel, decode (act_out.act set): the output also quantised
                                    // (a workgroup serves whole 256-blocks of it: 256 / (R * hd) kv heads)
+    float* out_f32;                // attn_dec_kernel, optional: the fp32 output too, [n_head * hd] (a LoRA
+                                   // adapter on attn_output reads it; the other kernels leave it in part_o)
     ActQ8 act_q8;                  // fused kernel, a short batch (act_q8.q set; launch_attn_multi): each
                                    // token's output quantised in the batch GEMMs' format, same blocks
 };
@@ -407,5 +437,35 @@ void launch_qkv_finish(const QkvFinish& F, hipStream_t s);
 // resid): [rows] added to every token's row after the residual
 void launch_part_sum(const float* part, int kp, int ntok, int rows, int pstride, const float* resid, int rstride,
                      float* out, int ostride, hipStream_t s, int swiglu = 0, const float* addend = nullptr);
+
+// ---- LoRA adapters (lora.hip): llama-graph.cpp build_lora_mm, b5187 ----
+// The adapters set on a context are stacked into one matrix pair of concatenated rank per base
+// tensor; every rank row carries its rounding rules (ggml rounds the f32 operand of an F16 matrix to
+// f16 before the dot), every adapter its s = scale * alpha / r (alpha 0: scale).  The dots are
+// summed in double and rounded to f32 once, as the tests' reference forms them (ggml's own f32
+// SIMD order is one of many).
+constexpr int LORA_MAX_RANK = 128;        // per base tensor, summed over the adapters of a context
+// Shrink: t[tok][j] = rt(A[j] . rc(cur[tok])) for the R rank rows of every target that reads one
+// activation; cur = x, or rms_norm(x) * norm_w rebuilt here (norm_w set).
+struct LoraShrink {
+    const float* x;        // [ntok][x_stride]
+    int x_stride, K, ntok;
+    const float* norm_w;   // optional
+    float eps;
+    const void* A;         // [R][K], F16 (a_f16) or F32
+    int a_f16, R;
+    const unsigned char* rnd;   // [R]: bit 0 round cur to f16 (an F16 A), bit 1 round A . cur to f16 (an F16 B)
+    float* t;              // [ntok][R]
+};
+void launch_lora_shrink(const LoraShrink& p, hipStream_t s);
+// Expand: out[tok][row] = the terms LoraFold describes (range 0 of F), stored for the launches
+// that take them precomputed (GemmParams::pre, GemvSeg::pre); a range without an adapter stores 0.
+struct LoraExpand {
+    LoraFold F;
+    int ntok, rows;
+    float* out;
+    int out_stride;
+};
+void launch_lora_expand(const LoraExpand& p, hipStream_t s);
 
 }  // namespace mi

@@ -26,7 +26,8 @@ namespace mi {
 // quantises the NT activation rows without the decode kernel's latency tricks
 // (one launch streams the weights once for NT tokens).
 // ---------------------------------------------------------------------------
-template <int T, int D>
+// PRE: the instantiation that adds GemmParams::pre (launched only when it is set)
+template <int T, int D, bool PRE>
 __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
     constexpr int NW = 8, NT = GEMM_NT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -170,10 +171,15 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 if (t >= ntok) continue;
-                const float yA = wave_sum63(accA[t]);
-                const float yB = wave_sum63(accB[t]);
+                float yA = wave_sum63(accA[t]);
+                float yB = wave_sum63(accB[t]);
                 accA[t] = accB[t] = 0.0f;
                 if (lane != 63) continue;
+                if constexpr (PRE) {   // a LoRA adapter's term, before the epilogue
+                    const float* pr = P.pre + (long long)t * P.pre_stride + P.pre_off;
+                    yA += pr[ra];
+                    if (hasB) yB += pr[adj ? rb : P.pre_up + rb];
+                }
                 float* out = P.out + (long long)t * P.out_stride;
                 const float* res = P.resid ? P.resid + (long long)t * P.out_stride : nullptr;
                 switch (P.epi) {
@@ -239,18 +245,19 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
 }
 
 typedef void (*GemmFn)(const GemmParams);
-static GemmFn gemm_fn(int type);
+static GemmFn gemm_fn(int type, bool pre);
 void init_gemm_attributes() {
     for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t)),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        for (bool pre : {false, true})
+            MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t, pre)),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
 }
-static GemmFn gemm_fn(int type) {
+static GemmFn gemm_fn(int type, bool pre) {
     switch (type) {
-    case T_Q4_K: return gemm_t<T_Q4_K, 4>;
-    case T_Q5_K: return gemm_t<T_Q5_K, 4>;
-    case T_Q6_K: return gemm_t<T_Q6_K, 4>;
-    case T_Q8_0: return gemm_t<T_Q8_0, 4>;
+    case T_Q4_K: return pre ? gemm_t<T_Q4_K, 4, true> : gemm_t<T_Q4_K, 4, false>;
+    case T_Q5_K: return pre ? gemm_t<T_Q5_K, 4, true> : gemm_t<T_Q5_K, 4, false>;
+    case T_Q6_K: return pre ? gemm_t<T_Q6_K, 4, true> : gemm_t<T_Q6_K, 4, false>;
+    case T_Q8_0: return pre ? gemm_t<T_Q8_0, 4, true> : gemm_t<T_Q8_0, 4, false>;
     default: return nullptr;
     }
 }
@@ -273,7 +280,7 @@ void launch_gemm(const GemmParams& p_in, hipStream_t s) {
     if ((long long)p.units * p.grid * 8 >= (1LL << 32)) throw Error("gemm: too many units");
     const size_t smem = gemm_smem_bytes(p);
     if (smem > 150 * 1024) throw Error("gemm: activations of GEMM_NT tokens do not fit LDS");
-    GemmFn fn = gemm_fn(p.A.type);
+    GemmFn fn = gemm_fn(p.A.type, p.pre != nullptr);
     if (!fn) throw Error("gemm: unsupported quant type");
     hipLaunchKernelGGL(fn, dim3(p.grid), dim3(512), smem, s, p);
     MI_HIP(hipGetLastError());
@@ -1189,7 +1196,8 @@ __global__ __launch_bounds__(64 * NWV * HG) void attn_dec_kernel(const AttnParam
         for (int e = 0; e < 8; ++e) red_o[grp][wave][L * 8 + e] = o[e];
     }
     __syncthreads();
-    // (no fp32 copy of the output: the streaming WO launch reads only the quantised one)
+    // (the fp32 output is stored only on request, out_f32 below: the streaming WO launch reads the
+    // quantised one)
     // the WO launch's quantised activation: the workgroup's HG heads are whole 256-blocks, one
     // wave per block; element e of the workgroup's span is head e / HD, dim e % HD
     constexpr int NE = HG * HD;
@@ -1204,6 +1212,11 @@ __global__ __launch_bounds__(64 * NWV * HG) void attn_dec_kernel(const AttnParam
 #pragma unroll
             for (int w = 1; w < NWV; ++w) s += red_o[gg][w][d];
             v[k] = s;
+        }
+        if (P.out_f32) {   // (uniform) a LoRA adapter on attn_output reads the fp32 row
+            float* of = P.out_f32 + (long long)tok * P.n_head * HD + e0 + b * 256 + lane * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) of[k] = v[k];
         }
         if (P.act_q8.q) quant_actq8_block(P.act_q8, tok, e0 / 256 + b, v, lane);   // a short batch's WO input
         else dv_quant_block(P.act_out, e0 / 256 + b, v, lane);

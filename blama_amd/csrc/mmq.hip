@@ -368,32 +368,35 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
 template <bool AB>
 __device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, const float2* rope, int ttok0,
                                              int lane, int row, const float v[16], int epi, int nrows,
-                                             float* out);
+                                             float* out, const float* pre);
 
 // The epilogue of one 32-token x 32-row D tile (v: this lane's 16 results).
 template <bool AB>
 __device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, const float2* rope, int ttok0,
                                              int lane, int row, const float v[16], int epi, int nrows,
-                                             float* out) {
+                                             float* out, const float* pre) {
     const int col = lane & 31, h = lane >> 5;
     const bool roped = epi == EPI_ROPE_Q || epi == EPI_ROPE_K;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int tok = ttok0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float pv = __shfl_xor(v[r], AB ? 16 : 1, 64);   // SwiGLU partner / RoPE partner
+        float vr = v[r];
+        if (pre && tok < tend && row < nrows)   // a LoRA adapter's term, before the epilogue
+            vr += pre[(long long)tok * P.pre_stride + row];
+        const float pv = __shfl_xor(vr, AB ? 16 : 1, 64);   // SwiGLU partner / RoPE partner
         if (tok >= tend) continue;
         if (AB) {
             if (col >= 16 || row >= nrows) continue;
-            out[(long long)tok * P.out_stride + row] = silu(v[r]) * pv;   // silu(gate) * up
+            out[(long long)tok * P.out_stride + row] = silu(vr) * pv;   // silu(gate) * up
             continue;
         }
         if (row >= nrows) continue;
-        float o = v[r];
+        float o = vr;
         if (roped) {
             const int i0 = row % P.head_dim;
             if (i0 < P.n_rot) {
                 const float2 cs = rope[(long long)tok * (P.n_rot / 2) + i0 / 2];
-                o = (col & 1) ? pv * cs.y + v[r] * cs.x : v[r] * cs.x - pv * cs.y;
+                o = (col & 1) ? pv * cs.y + vr * cs.x : vr * cs.x - pv * cs.y;
             }
         }
         const int* tp = P.tokpos + tok * 4;
@@ -445,6 +448,7 @@ struct MmqSegs {
     int rows[MMQ_SEGS];
     int epi[MMQ_SEGS];
     int n;
+    int pre_off[MMQ_SEGS];    // GemmParams::pre_off of each segment
 };
 
 template <int T> struct M2 {
@@ -547,7 +551,9 @@ __device__ __forceinline__ void q45_planes(const u32x4 hd, const u32x4 wq, const
 
 // NST 2: two stages (copy of sb + 1 during sb), one workgroup per CU.  NST 1: one stage, copy and
 // compute in turn, sized (LDS, <= 128 VGPRs) for two workgroups per CU that overlap each other.
-template <int T, bool AB, int NST>
+// PRE: the instantiation that adds GemmParams::pre (launched only when it is set: the other kernels
+// carry no trace of it).
+template <int T, bool AB, int NST, bool PRE>
 __global__ __launch_bounds__(64 * M2<T>::NW) __attribute__((amdgpu_waves_per_eu(NST == 1 ? 4 : 2)))
 void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSegs S) {
     using C = M2<T>;
@@ -852,9 +858,16 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
         // split-K: this part's partial sums, stored plainly; else the segment's epilogue
         if (P.ksplit > 1)
             mmq_epilogue<AB>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], EPI_STORE, rows_s,
-                             P.part + (long long)kh * P.ntok * P.out_stride);
-        else
-            mmq_epilogue<AB>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], epi_s, rows_s, P.out);
+                             P.part + (long long)kh * P.ntok * P.out_stride, nullptr);
+        else {
+            // (GemmParams::pre: this segment's rows; a pair's up lanes read the up rows' terms)
+            const float* pre = nullptr;
+            if constexpr (PRE) {
+                const int po = seg == 0 ? S.pre_off[0] : seg == 1 ? S.pre_off[1] : S.pre_off[2];
+                pre = P.pre + po + (AB && col >= 16 ? P.pre_up : 0);
+            }
+            mmq_epilogue<AB>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], epi_s, rows_s, P.out, pre);
+        }
     }
   }
 }
@@ -1476,23 +1489,28 @@ void launch_mmq2(const GemmParams& p, const mmq::MmqSegs& S, const ActQ8& act, c
         MI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
     const int nst = g2 >= 2 * n_cu ? 1 : 2;
-    decltype(&mmq::mmq2_t<T_Q4_K, false, 2>) f2;
+    decltype(&mmq::mmq2_t<T_Q4_K, false, 2, false>) f2;
+    const bool pre = p.pre != nullptr && p.ksplit <= 1;
     int lds;
 #define M2_PICK(NST_)                                                                                           \
     switch (T) {                                                                                                \
-    case T_Q4_K: f2 = ab ? mmq::mmq2_t<T_Q4_K, true, NST_> : mmq::mmq2_t<T_Q4_K, false, NST_>; lds = mmq::m2_lds<T_Q4_K, NST_>(); break; \
-    case T_Q5_K: f2 = ab ? mmq::mmq2_t<T_Q5_K, true, NST_> : mmq::mmq2_t<T_Q5_K, false, NST_>; lds = mmq::m2_lds<T_Q5_K, NST_>(); break; \
-    case T_Q6_K: f2 = ab ? mmq::mmq2_t<T_Q6_K, true, NST_> : mmq::mmq2_t<T_Q6_K, false, NST_>; lds = mmq::m2_lds<T_Q6_K, NST_>(); break; \
-    default: f2 = ab ? mmq::mmq2_t<T_Q8_0, true, NST_> : mmq::mmq2_t<T_Q8_0, false, NST_>; lds = mmq::m2_lds<T_Q8_0, NST_>(); break; \
+    case T_Q4_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q4_K, true, NST_, true> : mmq::mmq2_t<T_Q4_K, false, NST_, true>) \
+                           : (ab ? mmq::mmq2_t<T_Q4_K, true, NST_, false> : mmq::mmq2_t<T_Q4_K, false, NST_, false>); lds = mmq::m2_lds<T_Q4_K, NST_>(); break; \
+    case T_Q5_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q5_K, true, NST_, true> : mmq::mmq2_t<T_Q5_K, false, NST_, true>) \
+                           : (ab ? mmq::mmq2_t<T_Q5_K, true, NST_, false> : mmq::mmq2_t<T_Q5_K, false, NST_, false>); lds = mmq::m2_lds<T_Q5_K, NST_>(); break; \
+    case T_Q6_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q6_K, true, NST_, true> : mmq::mmq2_t<T_Q6_K, false, NST_, true>) \
+                           : (ab ? mmq::mmq2_t<T_Q6_K, true, NST_, false> : mmq::mmq2_t<T_Q6_K, false, NST_, false>); lds = mmq::m2_lds<T_Q6_K, NST_>(); break; \
+    default: f2 = pre ? (ab ? mmq::mmq2_t<T_Q8_0, true, NST_, true> : mmq::mmq2_t<T_Q8_0, false, NST_, true>) \
+                           : (ab ? mmq::mmq2_t<T_Q8_0, true, NST_, false> : mmq::mmq2_t<T_Q8_0, false, NST_, false>); lds = mmq::m2_lds<T_Q8_0, NST_>(); break; \
     }
     if (nst == 1) { M2_PICK(1) } else { M2_PICK(2) }
 #undef M2_PICK
-    static bool attr_done[2][4][2] = {};
+    static bool attr_done[2][4][2][2] = {};
     const int ti = T == T_Q4_K ? 0 : T == T_Q5_K ? 1 : T == T_Q6_K ? 2 : 3;
     const int ni = nst == 1 ? 0 : 1;
-    if (!attr_done[ni][ti][ab]) {
+    if (!attr_done[ni][ti][ab][pre]) {
         MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f2), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_done[ni][ti][ab] = true;
+        attr_done[ni][ti][ab][pre] = true;
     }
     hipLaunchKernelGGL(f2, dim3(g2), dim3(64 * NWv), (size_t)lds, s, p, act, rope, S);
     MI_HIP(hipGetLastError());
@@ -1525,6 +1543,9 @@ void launch_mmq32_multi(const GemmParams* ps, int n, const ActQ8& act, const flo
         S.sw[i] = ps[i].A.sw;
         S.rows[i] = ps[i].A.rows;
         S.epi[i] = ps[i].epi;
+        S.pre_off[i] = ps[i].pre_off;
+        if (ps[i].pre != ps[0].pre || ps[i].pre_stride != ps[0].pre_stride)
+            throw Error("mmq32 multi: the segments share one pre-epilogue buffer");
     }
     launch_mmq2(ps[0], S, act, rope, s);
 }
@@ -1548,6 +1569,7 @@ void launch_mmq32(const GemmParams& p, const ActQ8& act, const float2* rope, hip
     S.sw[0] = p.A.sw;
     S.rows[0] = p.A.rows;
     S.epi[0] = p.epi;
+    S.pre_off[0] = p.pre_off;
     launch_mmq2(p, S, act, rope, s);
 }
 

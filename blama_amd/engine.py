@@ -84,6 +84,14 @@ _SIGS = {
     "mi_state_set": (C.c_size_t, [_P, _P, C.c_size_t]),
     "mi_ctx_apply_cvec": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_size_t, C.c_int32, C.c_int32, C.c_int32]),
     "mi_cvec_load": (C.c_int64, [C.c_char_p, C.c_float, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32)]),
+    "mi_lora_load": (_P, [_P, C.c_char_p]),
+    "mi_lora_load_from_memory": (_P, [_P, C.c_void_p, C.c_size_t]),
+    "mi_lora_free": (None, [_P]),
+    "mi_lora_alpha": (C.c_float, [_P]),
+    "mi_lora_n_pairs": (C.c_int32, [_P]),
+    "mi_ctx_set_lora": (C.c_int32, [_P, _P, C.c_float]),
+    "mi_ctx_rm_lora": (C.c_int32, [_P, _P]),
+    "mi_ctx_clear_lora": (None, [_P]),
     "mi_prof_enable": (C.c_int32, [_P, C.c_int32]),
     "mi_prof_read": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_int32]),
     "mi_prof_ffn_bytes": (C.c_int64, [_P]),
@@ -215,6 +223,40 @@ class Model:
         return lib().mi_model_token_is_eog(self.h, tok) == 1
 
 
+class Lora:
+    """Owns an mi_lora (llama_adapter_lora_init + llama_adapter_lora_free): a LoRA adapter GGUF
+    (a path or an in-memory image) validated against `model`.  A context that was given the
+    adapter keeps it alive, so close() while it is still set is safe."""
+
+    def __init__(self, model: Model, source):
+        L = lib()
+        if isinstance(source, (str, os.PathLike)):
+            h = L.mi_lora_load(model.h, os.fspath(source).encode())
+        else:
+            if isinstance(source, (bytes, bytearray, memoryview)):
+                buf = np.frombuffer(source, np.uint8)
+            else:
+                buf = np.ascontiguousarray(source, dtype=np.uint8)
+            h = L.mi_lora_load_from_memory(model.h, _ptr(buf), buf.size)
+        if not h:
+            raise EngineError(f"lora load failed: {last_error()}")
+        self.h = h
+        self.model = model
+        self.alpha = float(L.mi_lora_alpha(h))
+        self.n_pairs = int(L.mi_lora_n_pairs(h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mi_lora_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """Owns an mi_ctx (llama_init_from_model + llama_free)."""
 
@@ -320,6 +362,16 @@ class Context:
 
     def clear_cvec(self):
         _check(lib().mi_ctx_apply_cvec(self.h, None, 0, self.model.n_embd, 0, 0), "clear_cvec")
+
+    def set_lora(self, lora: "Lora", scale: float = 1.0):
+        """mi_ctx_set_lora (llama_set_adapter_lora): adds the adapter or updates its scale."""
+        _check(lib().mi_ctx_set_lora(self.h, lora.h if lora is not None else None, scale), "set_lora")
+
+    def rm_lora(self, lora: "Lora"):
+        _check(lib().mi_ctx_rm_lora(self.h, lora.h if lora is not None else None), "rm_lora")
+
+    def clear_lora(self):
+        lib().mi_ctx_clear_lora(self.h)
 
     def prof_enable(self, stride: int):
         lib().mi_prof_enable(self.h, stride)

@@ -863,6 +863,16 @@ ControlVector::ControlVector(const Model& model, const std::vector<LoadInfo>& in
     if (nEmbd == -1) data.clear();
 }
 
+// ------------------------------------------------------------ LoraAdapter ---
+LoraAdapter::LoraAdapter(Model& model, std::string path) : m_model(model), m_path(std::move(path)) {
+    m_adapter = mi_lora_load(model.mmodel(), m_path.c_str());
+    if (!m_adapter) BL_THROW("Failed to load LoRA adapter " << m_path << ": " << last_error());
+}
+
+LoraAdapter::~LoraAdapter() {
+    if (m_adapter) mi_lora_free(m_adapter);
+}
+
 Instance::Instance(Model& model, InitParams params) : m_model(model) {
     m_ctx = mi_ctx_create(model.mmodel(), params.ctxSize, params.batchSize, params.ubatchSize);
     if (!m_ctx) BL_THROW("Failed to create llama context");
@@ -882,6 +892,13 @@ void Instance::addControlVector(const ControlVector& ctrlVector) {
 void Instance::clearControlVector() {
     if (mi_ctx_apply_cvec(m_ctx, nullptr, 0, 0, 0, 0)) BL_THROW("Failed to clear control vectors!");
 }
+
+void Instance::addLora(LoraAdapter& lora, float scale) {
+    if (&lora.model() != &m_model) BL_THROW("LoraAdapter model does not match the instance model");
+    if (mi_ctx_set_lora(m_ctx, lora.madapter(), scale)) BL_THROW("Failed to set LoRA adapter: " << last_error());
+}
+
+void Instance::clearLoraState() { mi_ctx_clear_lora(m_ctx); }
 
 void Instance::warmup() {
     std::vector<Token> t;

@@ -13,7 +13,8 @@
 //   Model{Params{gpu, vocabOnly, prefixInputsWithBos}}   Model.hpp:26-58
 //   Vocab{tokenize, isEog, nTokens, tokenToString}       Vocab.hpp:16-34
 //   Instance{InitParams, warmup, startSession, stopSession,
-//            addControlVector}                            Instance.hpp:19-51
+//            addControlVector, addLora, clearLoraState}   Instance.hpp:19-51
+//   LoraAdapter                                           LoraAdapter.hpp, LoraAdapter.cpp:12-19
 //   ControlVector{LoadInfo}                               ControlVector.hpp:17-33
 //   Session{InitParams, setInitialPrompt, complete, completeStream, fillCtx,
 //           getState, setState, resetSampler}             Session.hpp:29-130
@@ -21,7 +22,7 @@
 //   LogitComparer / MetricsAggregator                     LogitComparer.hpp:12-34
 //
 // Not served (engine scope): Model::Params::gpu=false (the reference's CPU
-// verifier), LoRA, grammar constraints, encoder models.
+// verifier), grammar constraints, encoder models.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -38,6 +39,7 @@
 
 struct mi_model;
 struct mi_ctx;
+struct mi_lora;
 
 namespace bl::llama {
 
@@ -228,6 +230,25 @@ public:
     int controlVectorLayerEnd = 0;
 };
 
+// A LoRA adapter file loaded for one model (LoraAdapter.cpp:12-19, llama_adapter_lora_init);
+// throws when the engine refuses the file (mi_last_error() in the message).
+class LoraAdapter {
+public:
+    LoraAdapter(Model& model, std::string path);
+    ~LoraAdapter();
+    LoraAdapter(const LoraAdapter&) = delete;
+    LoraAdapter& operator=(const LoraAdapter&) = delete;
+
+    mi_lora* madapter() const noexcept { return m_adapter; }
+    const Model& model() const noexcept { return m_model; }
+    const std::string& path() const noexcept { return m_path; }
+
+private:
+    Model& m_model;
+    std::string m_path;
+    mi_lora* m_adapter = nullptr;
+};
+
 class Instance;
 
 class Session {
@@ -325,6 +346,11 @@ public:
     // engine refuses the vector (its nEmbd is not the model's)
     void addControlVector(const ControlVector& ctrlVector);
     void clearControlVector();
+    // llama_set_adapter_lora (Instance.cpp:52-57): adds the adapter or updates its scale, from the
+    // next decode on; throws "LoraAdapter model does not match the instance model" for an adapter of
+    // another Model.  clearLoraState: llama_clear_adapter_lora (Instance.cpp:59-61).
+    void addLora(LoraAdapter& lora, float scale = 1.0f);
+    void clearLoraState();
     void warmup();
     Session& startSession(const Session::InitParams params);
     void stopSession() noexcept;

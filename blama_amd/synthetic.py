@@ -615,3 +615,43 @@ def write_cvec_gguf(path, directions) -> None:
         w.add_tensor(name, 1 if a.dtype == np.float16 else 0, a.shape[::-1], a)
     with open(path, "wb") as f:
         f.write(w.to_bytes().tobytes())
+
+
+LORA_TARGETS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+
+
+def lora_tensors(cfg: LlamaConfig, targets, rank: int, dtype, seed: int, layers=None, std: float = 0.05) -> dict:
+    """The pairs of a synthetic adapter: {"blk.L.T.weight": (A [rank][K], B [rows][rank])} of `dtype`
+    (float16 or float32), normal(0, std) entries, each tensor from its own generator."""
+    shapes = tensor_shapes(cfg)
+    out = {}
+    for l in (range(cfg.n_layer) if layers is None else layers):
+        for t in targets:
+            name = f"blk.{l}.{t}.weight"
+            K, rows = shapes[name][0], shapes[name][1]
+            a = _rng(seed, name + ".lora_a").standard_normal((rank, K)).astype(np.float32) * np.float32(std)
+            b = _rng(seed, name + ".lora_b").standard_normal((rows, rank)).astype(np.float32) * np.float32(std)
+            out[name] = (a.astype(dtype), b.astype(dtype))
+    return out
+
+
+def write_lora_gguf(dst, cfg: LlamaConfig, targets=LORA_TARGETS, rank: int = 4, alpha: float = 8.0, dtype=np.float16,
+                    seed: int = 0, layers=None, std: float = 0.05) -> np.ndarray:
+    """A LoRA adapter GGUF as llama.cpp's convert_lora_to_gguf.py writes it (general.type "adapter",
+    adapter.type "lora", adapter.lora.alpha, pairs <base tensor>.lora_a ne [K, r] / .lora_b ne
+    [r, rows]) over `targets` of `layers` (None: all).  Returns the image as a uint8 array and,
+    when dst is a path, writes it there."""
+    w = gguf.GGUFWriter()
+    w.add_str("general.architecture", cfg.arch)
+    w.add_str("general.type", "adapter")
+    w.add_str("adapter.type", "lora")
+    w.add_f32("adapter.lora.alpha", alpha)
+    for name, (a, b) in lora_tensors(cfg, targets, rank, dtype, seed, layers, std).items():
+        gt = 1 if a.dtype == np.float16 else 0
+        w.add_tensor(name + ".lora_a", gt, a.shape[::-1], a)
+        w.add_tensor(name + ".lora_b", gt, b.shape[::-1], b)
+    img = w.to_bytes()
+    if dst is not None:
+        with open(dst, "wb") as f:
+            f.write(img.tobytes())
+    return img

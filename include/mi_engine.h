@@ -157,6 +157,38 @@ int32_t mi_ctx_apply_cvec(mi_ctx* ctx, const float* data, size_t len, int32_t n_
  * that is not direction.N with N >= 1, not F32, not 1-D, or of another length than the first. */
 int64_t mi_cvec_load(const char* gguf_path, float strength, float* data, size_t cap, int32_t* n_embd);
 
+/* LoRA adapters (llama.cpp b5187 src/llama-adapter.cpp, llama-graph.cpp build_lora_mm): for every
+ * base tensor W an adapter holds, y = W cur + s * (B (A cur)) with s = scale * alpha / r (alpha 0:
+ * s = scale), ahead of everything downstream (RoPE, the KV append, SwiGLU, the residual add).
+ * Dense LLaMA models; the per-layer attn_q/k/v/output and ffn_gate/up/down tensors; F16 or F32
+ * adapter tensors; rank 1..128 per pair, at most 4 adapters on a context with a summed rank of at
+ * most 128 per base tensor.
+ *
+ * mi_lora_load / _from_memory: llama_adapter_lora_init (LoraAdapter.cpp:12-19).  NULL and
+ * mi_last_error() when general.type is not "adapter" or adapter.type not "lora", the architecture
+ * differs from the model's, a tensor name ends in neither .lora_a nor .lora_b, a pair lacks a
+ * half, the base tensor does not exist in the model or is not one of the seven above, a shape does
+ * not fit (invalid shape, not transposed), a type is neither F16 nor F32, the rank is above 128,
+ * the model is MoE or GPT-2, or the file is truncated.  On a vocab_only model the file is parsed
+ * and validated only.  The adapter is shared-owned: a context keeps what it was given alive, so
+ * mi_lora_free on an adapter still set on a context is safe. */
+typedef struct mi_lora mi_lora;
+mi_lora* mi_lora_load(mi_model* model, const char* gguf_path);
+mi_lora* mi_lora_load_from_memory(mi_model* model, const void* data, size_t size);
+void mi_lora_free(mi_lora* lora);
+float mi_lora_alpha(const mi_lora* lora);
+int32_t mi_lora_n_pairs(const mi_lora* lora);
+/* llama_set_adapter_lora (Instance.cpp:52-57, Instance::addLora): adds the adapter to the context
+ * or updates its scale; adapters stack.  mi_ctx_rm_lora: llama_rm_adapter_lora, 0 or < 0 when the
+ * adapter is not set.  mi_ctx_clear_lora: llama_clear_adapter_lora (Instance.cpp:59-61,
+ * Instance::clearLoraState).  Like the control vector the adapters belong to the context (not to
+ * mi_state_get / mi_state_set), take effect from the next mi_decode and leave the KV entries of
+ * earlier tokens as they are; the calls synchronise.  < 0: a null argument, an adapter of another
+ * model (Instance.cpp:53-55), a fifth adapter or a summed rank above 128. */
+int32_t mi_ctx_set_lora(mi_ctx* ctx, mi_lora* lora, float scale);
+int32_t mi_ctx_rm_lora(mi_ctx* ctx, mi_lora* lora);
+void mi_ctx_clear_lora(mi_ctx* ctx);
+
 /* ---- measurement: HIP events on the context's stream bracketing the FFN
  * gate/up GEMV launch of `layer` in every output-producing decode step (the
  * step's graph is split in three around it); layer < 0 disables.
