@@ -1,0 +1,496 @@
+// Engine host code: the prompt-batch paths of the decode context -- prompt chunks on the v_dot4
+// GEMM (decode_batch), physical batches on the tiled int8-MFMA GEMM (decode_ubatch) and short
+// batches on the split-K streaming GEMM (ubatch_layers_short) -- over one builder per launch.
+#include "engine.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace mi {
+
+// ========================================================= batch launches ===
+void Ctx::upload_batch(const int32_t* tokens, int nt) {
+    const long long slot = tokb_slot++ % kTokbRing;
+    if (slot == 0 && tokb_slot > 1) MI_HIP(hipStreamSynchronize(stream));
+    int* hpos = h_tokpos_b + slot * kBatchRows * 4;
+    for (int t = 0; t < nt; ++t) {
+        const int pos = pos_max + 1, cell = n_cells;
+        hpos[t * 4 + 0] = tokens[t];
+        hpos[t * 4 + 1] = pos;
+        hpos[t * 4 + 2] = cell;
+        hpos[t * 4 + 3] = 0;
+        h_cell_pos[cell] = pos;
+        n_cells++;
+        pos_max = pos;
+    }
+    MI_HIP(hipMemcpyAsync(tokpos_b, hpos, nt * 4 * sizeof(int), hipMemcpyHostToDevice, stream));
+}
+
+GemmParams Ctx::gemm_base(int l, int nt, bool vdot4) const {
+    const HParams& hp = m->hp;
+    GemmParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.ntok = nt;
+    p.tokpos = tokpos_b;
+    p.cell_pos = cell_pos;
+    p.head_dim = hp.head_dim;
+    p.kcache = k_layer(l);
+    p.vcache = v_layer(l);
+    p.kv_dim = kv_dim;
+    if (vdot4) {   // (n_rot: on the Q and K launches only)
+        p.theta_scale = theta_scale();
+        p.freq_scale = hp.freq_scale;
+        p.freq_factors = m->rope_freqs;
+        p.eps = hp.eps;
+    } else {
+        p.n_rot = hp.n_rot;
+    }
+    return p;
+}
+
+// Q, K or V projection (+ RoPE, KV append) into qb
+GemmParams Ctx::bqkv_params(int l, int nt, bool vdot4, int i, const float* pre) const {
+    const Layer& L = m->layers[l];
+    const int epis[3] = {EPI_ROPE_Q, EPI_ROPE_K, EPI_V};
+    GemmParams p = gemm_base(l, nt, vdot4);
+    p.A = i == 0 ? L.wq : i == 1 ? L.wk : L.wv;
+    p.pair = PAIR_ADJ;
+    p.epi = epis[i];
+    p.K = m->hp.n_embd;
+    p.out = qb;
+    p.out_stride = m->hp.n_embd;
+    if (vdot4 && i < 2) p.n_rot = m->hp.n_rot;
+    set_pre(p, pre, l, 0, i);   // LoRA: added before RoPE and the KV append
+    return p;
+}
+
+// output projection + residual, in place
+GemmParams Ctx::bwo_params(int l, int nt, bool vdot4, const float* pre) const {
+    GemmParams p = gemm_base(l, nt, vdot4);
+    p.A = m->layers[l].wo;
+    p.pair = PAIR_ADJ;
+    p.epi = EPI_ADD;
+    p.K = m->hp.n_embd;
+    p.out = xb;
+    p.resid = xb;
+    p.out_stride = m->hp.n_embd;
+    set_pre(p, pre, l, 1, 0);   // before the residual add
+    return p;
+}
+
+// FFN gate/up + SwiGLU into hb
+GemmParams Ctx::bgate_up_params(int l, int nt, bool vdot4, const float* pre) const {
+    GemmParams p = gemm_base(l, nt, vdot4);
+    p.A = m->layers[l].gate;
+    p.B = m->layers[l].up;
+    p.pair = PAIR_AB;
+    p.epi = EPI_SWIGLU;
+    p.K = m->hp.n_embd;
+    p.out = hb;
+    p.out_stride = m->hp.n_ff;
+    set_pre(p, pre, l, 2, 0);   // the gate and up terms, before SwiGLU
+    return p;
+}
+
+// FFN down + residual, in place, then the control vector's row (build_cvec)
+GemmParams Ctx::bdown_params(int l, int nt, bool vdot4, const float* pre) const {
+    GemmParams p = gemm_base(l, nt, vdot4);
+    p.A = m->layers[l].down;
+    p.pair = PAIR_ADJ;
+    p.epi = EPI_ADD;
+    p.K = m->hp.n_ff;
+    p.out = xb;
+    p.resid = xb;
+    p.addend = cvec_for(l);
+    p.out_stride = m->hp.n_embd;
+    set_pre(p, pre, l, 3, 0);
+    return p;
+}
+
+// causal attention of the batch's tokens, qb -> attnb
+AttnParams Ctx::battn_params(int l) const {
+    const HParams& hp = m->hp;
+    return AttnParams{qb, k_layer(l), v_layer(l), tokpos_b, cell_pos, attn_scores, attn_smax, attnb, hp.n_head, hp.n_head_kv,
+                      hp.head_dim, kv_dim, (int)n_ctx, kq_scale()};
+}
+
+Ctx::QkvGroups Ctx::qkv_type_groups(const Layer& L) {
+    const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
+    QkvGroups G{};
+    for (const QMat* q : mats) G.fmt |= q->type == T_Q8_0 ? 2 : 1;
+    for (int i = 0; i < 3; ++i) {   // (7B: Q/K/V, or Q/K plus a Q6_K V)
+        bool first = true;
+        for (int j = 0; j < i; ++j) first = first && mats[j]->type != mats[i]->type;
+        if (!first) continue;
+        for (int j = i; j < 3; ++j)
+            if (mats[j]->type == mats[i]->type) G.idx[G.n][G.cnt[G.n]++] = j;
+        ++G.n;
+    }
+    return G;
+}
+
+int Ctx::mmqs_one(const QMat& A, bool pair, int nff, const ActQ8& act, int pstride) {
+    const QMat* mo[1] = {&A};
+    const int pr[1] = {0};
+    return launch_mmqs(mo, pr, 1, pair, nff, act, ub_spart, pstride, stream);
+}
+
+void Ctx::finish_logits_all(int c0, int nt, bool last) {
+    if (!last) return;
+    const int nv = m->hp.n_vocab;
+    MI_HIP(hipMemcpyAsync(logits, logits_all + (size_t)(c0 + nt - 1) * nv, (size_t)nv * sizeof(float), hipMemcpyDeviceToDevice,
+                          stream));
+    run_topk(logits);
+}
+
+// Prompt ingestion: n tokens in chunks of GEMM_NT, every weight matrix streamed once per
+// chunk (launch_gemm), causal attention of the chunk's tokens (launch_attn_multi), the
+// output head for the last token only (llama_batch_get_one: logits of the last token).
+void Ctx::decode_batch(const int32_t* tokens, int n) {
+    const HParams& hp = m->hp;
+    // one projection on the v_dot4 GEMM, which quantises its own rows [ntok][K] of x
+    auto proj = [&](GemmParams p, const float* x, const float* norm) {
+        p.units = p.pair == PAIR_AB ? p.A.rows : (p.A.rows + 1) / 2;
+        p.x = x;
+        p.x_stride = p.K;
+        p.norm_w = norm;
+        p.pro = norm ? PRO_RMSNORM : PRO_PLAIN;
+        launch_gemm(p, stream);
+    };
+    for (int c0 = 0; c0 < n; c0 += GEMM_NT) {
+        const int nt = std::min(GEMM_NT, n - c0);
+        upload_batch(tokens + c0, nt);
+        EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
+        launch_embed_multi(ep, nt, stream);
+        for (int l = 0; l < hp.n_layer; ++l) {
+            const Layer& L = m->layers[l];
+            // LoRA: each group's terms of the chunk ahead of the launches that add them
+            const float* pre = lora_pre_terms(l, 0, xb, hp.n_embd, nt, L.attn_norm);
+            for (int i = 0; i < 3; ++i) proj(bqkv_params(l, nt, true, i, pre), xb, L.attn_norm);
+            launch_attn_multi(battn_params(l), nt, attnb, stream);
+            pre = lora_pre_terms(l, 1, attnb, hp.n_embd, nt, nullptr);
+            proj(bwo_params(l, nt, true, pre), attnb, nullptr);
+            pre = lora_pre_terms(l, 2, xb, hp.n_embd, nt, L.ffn_norm);
+            proj(bgate_up_params(l, nt, true, pre), xb, L.ffn_norm);
+            pre = lora_pre_terms(l, 3, hb, hp.n_ff, nt, nullptr);
+            proj(bdown_params(l, nt, true, pre), hb, nullptr);
+        }
+        if (c0 + nt == n) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+    }
+    logits_valid = true;
+}
+
+// build_moe_ffn's routing (src/llama-graph.cpp, b5187: softmax gating, top-2, weights normalised)
+// over a physical batch, on the device: the router of every token (the decode step's
+// router_kernel), the (token, slot) picks grouped by expert (launch_moe_group: tokens ascending
+// within an expert, each expert's rows whole 32-row MFMA tiles).  No host round trip.
+int Ctx::moe_route(int l, int nt, const float* pend) {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    const int U = hp.n_expert_used, E = hp.n_expert;
+    RouterParams rp{xb, L.ffn_norm, hp.eps, L.router, hp.n_embd, E, U, sel_b, selw_b, hp.n_embd, pend, nt};
+    launch_router_multi(rp, nt, stream);
+    const int cap = moe_rows_cap(nt * U, E);
+    launch_moe_group(sel_b, nt * U, U, E, moe_grp, moe_rows, moe_rowsel, moe_pos, cap, stream);
+    return cap;
+}
+
+ActQ8 Ctx::moe_act(int K, int cap, bool q80) const {
+    ActQ8 a;
+    a.q = moe_q;
+    a.dT = moe_dT;
+    a.bsb = moe_bsb;
+    a.K = K;
+    a.ntok = cap;
+    a.npad = cap;
+    a.q80 = q80 ? 1 : 0;
+    return a;
+}
+
+// build_moe_ffn over a physical batch: routing, one quantisation of every row, ONE grouped mmq32
+// launch for the experts' gate/up + SwiGLU and one for their down projections (a workgroup per
+// (expert, row tile) over that expert's token tiles), then every token's x += w0*y0 + w1*y1 in
+// slot order (launch_moe_combine, the decode GEMV's EPI_MOE_DOWN arithmetic).
+void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    const int cap = moe_route(l, nt, pend);
+    GemmParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.ntok = cap;
+    p.tokpos = tokpos_b;
+    p.grp = moe_grp;
+    p.grp_n = hp.n_expert;
+    p.grp_max = nt;
+    // gate/up + SwiGLU: rms_norm(x) * ffn_norm of each row's token
+    const ActQ8 act = moe_act(hp.n_embd, cap, L.gate.type == T_Q8_0);
+    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
+    p.A = L.gate;
+    p.B = L.up;
+    p.pair = PAIR_AB;
+    p.epi = EPI_SWIGLU;
+    p.K = hp.n_embd;
+    p.out = hb;
+    p.out_stride = hp.n_ff;
+    p.grp_stride = L.gate.sw_expert_stride;
+    launch_mmq32(p, act, ub_rope, stream);
+    // down: every row of the FFN output, stored (weighted and summed by the combine)
+    const ActQ8 a2 = moe_act(hp.n_ff, cap, L.down.type == T_Q8_0);
+    launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel);
+    GemmParams d = p;
+    d.A = L.down;
+    std::memset(&d.B, 0, sizeof(d.B));
+    d.pair = PAIR_ADJ;
+    d.epi = EPI_STORE;
+    d.K = hp.n_ff;
+    d.out = yb;
+    d.out_stride = hp.n_embd;
+    d.grp_stride = L.down.sw_expert_stride;
+    launch_mmq32(d, a2, ub_rope, stream);
+    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
+}
+
+// The same build_moe_ffn over a short batch (<= MMQS_MAX tokens; x already holds the residual) on
+// the grouped streaming GEMM: routing, one quantisation of every MoE row, the experts' gate/up
+// pair parts (launch_mmqs_grouped: workgroups per (row tile, K-part, expert, 32-row tile), each
+// expert's matrix streamed once for the rows routed to it), SwiGLU of the parts quantised for
+// down, down's parts, their sum per row, then every token's x += w0*y0 + w1*y1 in slot order.
+void Ctx::moe_ffn_short(int l, int nt) {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    const int E = hp.n_expert;
+    const int cap = moe_route(l, nt, nullptr);
+    const ActQ8 act = moe_act(hp.n_embd, cap, false);
+    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
+    // an expert receives each token at most once: at most nt rows
+    const int kg = launch_mmqs_grouped(L.gate, true, hp.n_ff, act, ub_spart, 2 * hp.n_ff, moe_grp, E, nt, stream);
+    const ActQ8 a2 = moe_act(hp.n_ff, cap, false);
+    launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel, ub_spart, kg, 1);
+    const int kd = launch_mmqs_grouped(L.down, false, 0, a2, ub_spart, hp.n_embd, moe_grp, E, nt, stream);
+    launch_part_sum(ub_spart, kd, cap, hp.n_embd, hp.n_embd, nullptr, 0, yb, hp.n_embd, stream);
+    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
+}
+
+ActQ8 Ctx::ub_act(int K, int ntok, int type) const {
+    const bool q80 = type == T_Q8_0;
+    const bool second = q80 && !ub_q80 && ub_q0;   // the Q8_0 set of a mixed model
+    ActQ8 a;
+    a.q = second ? ub_q0 : ub_q;
+    a.dT = second ? ub_dT0 : ub_dT;
+    a.bsb = ub_bsb;
+    a.K = K;
+    a.ntok = ntok;
+    a.npad = (ntok + 31) / 32 * 32;
+    a.q80 = q80 ? 1 : 0;
+    return a;
+}
+
+// Prompt ingestion / batched verification in physical batches of up to UB_MAX tokens on the
+// int8-MFMA GEMM (mmq.hip): per layer every weight matrix is streamed once per batch; each
+// activation is quantised to Q8_K once (RMSNorm fused) and shared by the matrices that read it.
+// `all`: the output head runs over every token (rows of logits_all), else over the last one.
+void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
+    const HParams& hp = m->hp;
+    for (int c0 = 0; c0 < n; c0 += UB_MAX) {
+        const int nt = std::min(UB_MAX, n - c0);
+        upload_batch(tokens + c0, nt);
+        // (a context with a LoRA adapter runs its short batches on the tiled form below, whose
+        // epilogues take the adapter's terms; split-K is off for the W_o / down launches an adapter
+        // targets, and pending parts are added by the quant_act that precedes every shrink)
+        if (mmqs_max > 0 && nt <= mmqs_max && short_ok() && !lora_on()) {   // a short batch (its launches captured as a
+            // hipGraph measured no faster: the GPU, not the enqueue, sets the pace)
+            enqueue_ubatch_short(nt, all, c0, c0 + nt == n);
+            continue;
+        }
+        EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
+        launch_embed_multi(ep, nt, stream);
+        launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale(), hp.freq_scale, m->rope_freqs, ub_rope, stream);
+        const float* pend = nullptr;   // split-K partials not yet added into xb (the next quant_act does)
+        const float* pend_add = nullptr;   // the control-vector row that goes in after them (FFN down's parts)
+        // split-K parts of the residual GEMMs: 4 for short batches of dense models (verification
+        // of tens of tokens: more workgroups, a quarter of the superblock steps each; 4 x nt rows
+        // fit the 2 x UB_MAX partials buffer), else 2 (the MoE router adds 2)
+        const int ks = hp_dense() && nt <= 64 ? 4 : 2;   // 4 x 64 rows fit the 2 x UB_MAX partials buffer
+        for (int l = 0; l < hp.n_layer; ++l) {
+            const Layer& L = m->layers[l];
+            // Q / K / V (+ RoPE, KV append) over one quantisation of rms_norm(x) * attn_norm per
+            // activation format the three matrices read, the matrices of one type in one launch
+            const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
+            const QkvGroups G = qkv_type_groups(L);
+            for (int f = 0; f < 2; ++f)
+                if (G.fmt >> f & 1) {
+                    launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
+                                     nullptr, pend, ks, 0, pend ? pend_add : nullptr);
+                    pend = nullptr;
+                }
+            // LoRA: a group's terms of the batch after the quant_act of its input, before the GEMM
+            const float* pre = lora_pre_terms(l, 0, xb, hp.n_embd, nt, L.attn_norm);
+            for (int g = 0; g < G.n; ++g) {
+                GemmParams ps[3];
+                for (int k = 0; k < G.cnt[g]; ++k) ps[k] = bqkv_params(l, nt, false, G.idx[g][k], pre);
+                launch_mmq32_multi(ps, G.cnt[g], ub_act(hp.n_embd, nt, mats[G.idx[g][0]]->type), ub_rope, stream);
+            }
+            if (attn_mfma) launch_attn_mfma(battn_params(l), nt, attnb, stream);
+            else launch_attn_multi(battn_params(l), nt, attnb, stream);
+            {   // output projection + residual
+                const ActQ8 act = ub_act(hp.n_embd, nt, L.wo.type);
+                launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act, stream);
+                pre = lora_pre_terms(l, 1, attnb, hp.n_embd, nt, nullptr);
+                GemmParams p = bwo_params(l, nt, false, pre);
+                // parts of K; the FFN's quant_act adds them (not with an adapter on this W_o: its terms
+                // go in ahead of the residual add, which a split launch leaves to the next kernel)
+                if (ub_part && L.wo.nb >= ks && !pre) {
+                    p.ksplit = ks;
+                    p.part = ub_part;
+                    pend = ub_part;
+                }
+                launch_mmq32(p, act, ub_rope, stream);
+            }
+            if (hp.n_expert > 0) {   // routed experts (build_moe_ffn) + residual
+                moe_ffn_batch(l, nt, pend);
+                pend = nullptr;
+                continue;
+            }
+            {   // FFN gate/up + SwiGLU
+                const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
+                launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, pend, ks);
+                pend = nullptr;
+                pre = lora_pre_terms(l, 2, xb, hp.n_embd, nt, L.ffn_norm);
+                launch_mmq32(bgate_up_params(l, nt, false, pre), act, ub_rope, stream);
+            }
+            {   // FFN down + residual
+                const ActQ8 act = ub_act(hp.n_ff, nt, L.down.type);
+                launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, act, stream);
+                pre = lora_pre_terms(l, 3, hb, hp.n_ff, nt, nullptr);
+                GemmParams p = bdown_params(l, nt, false, pre);
+                if (ub_part && L.down.nb >= ks && l + 1 < hp.n_layer && !pre) {   // the next layer's quant_act adds them,
+                    p.ksplit = ks;                                               // and the control vector's row after them
+                    p.part = ub_part;
+                    pend = ub_part;
+                    pend_add = p.addend;
+                    p.addend = nullptr;
+                }
+                launch_mmq32(p, act, ub_rope, stream);
+            }
+        }
+        if (all) {   // final norm + output head over every token of the batch
+            const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);   // the head's own activation format
+            launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream);
+            GemmParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.A = m->output;
+            p.pair = PAIR_ADJ;
+            p.epi = EPI_STORE;
+            p.K = hp.n_embd;
+            p.ntok = nt;
+            p.tokpos = tokpos_b;
+            p.out = logits_all + (size_t)c0 * hp.n_vocab;
+            p.out_stride = hp.n_vocab;
+            launch_mmq32(p, a_out, ub_rope, stream);
+            finish_logits_all(c0, nt, c0 + nt == n);
+        } else if (c0 + nt == n) {
+            enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+        }
+    }
+    logits_valid = true;
+}
+
+// One short physical batch (tokens uploaded to tokpos_b): embedding, the rope table, the layers on
+// mmqs, then the output -- every token's logits rows (`all`, rows c0.. of logits_all; the last
+// chunk's last row also feeds `logits` and the top-k) or the last token's through the decode head.
+void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
+    const HParams& hp = m->hp;
+    EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
+    launch_embed_multi(ep, nt, stream);
+    launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale(), hp.freq_scale, m->rope_freqs, ub_rope, stream);
+    const int pend_k = ubatch_layers_short(nt);
+    // (the parts pending are the last layer's FFN down's -- dense models; its control-vector row
+    // goes in with them)
+    const float* pend_add = pend_k ? cvec_for(hp.n_layer - 1) : nullptr;
+    if (all) {   // final norm + output head on mmqs, its parts summed into the logits rows
+        const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);
+        launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream, nullptr, pend_k ? ub_spart : nullptr,
+                         pend_k ? pend_k : 2, 0, pend_add);
+        const int kp = mmqs_one(m->output, false, 0, a_out, hp.n_vocab);
+        launch_part_sum(ub_spart, kp, nt, hp.n_vocab, hp.n_vocab, nullptr, 0, logits_all + (size_t)c0 * hp.n_vocab,
+                        hp.n_vocab, stream);
+        finish_logits_all(c0, nt, last);
+    } else {
+        // the last residual parts into xb (the next chunk, or the output, reads it)
+        if (pend_k)
+            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream, 0, pend_add);
+        if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+    }
+}
+
+// One short physical batch (<= mmqs_max tokens) through the layers on the split-K streaming GEMM
+// (mmq.hip mmqs): every launch writes K-part sums to ub_spart, and the next kernel adds them --
+// quant_act (the residual, or SwiGLU of the gate/up parts), qkv_finish (RoPE, KV append).
+// Returns the count of the last FFN down's parts, still to be added into xb.
+int Ctx::ubatch_layers_short(int nt) {
+    const HParams& hp = m->hp;
+    const int qkv_rows = hp.n_embd + 2 * kv_dim;
+    int pend_k = 0;   // residual parts of ub_spart not yet added into xb
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const Layer& L = m->layers[l];
+        // Q / K / V: one quantisation of rms_norm(x) * attn_norm per activation format (the first
+        // also adds the residual parts), the matrices of one type in one launch, rows [Q | K | V]
+        const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
+        const QkvGroups G = qkv_type_groups(L);
+        for (int f = 0; f < 2; ++f)
+            if (G.fmt >> f & 1) {
+                // (parts pending here are the previous layer's FFN down's: its control-vector row with them)
+                launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
+                                 nullptr, pend_k ? ub_spart : nullptr, pend_k ? pend_k : 2, 0,
+                                 pend_k && l > 0 ? cvec_for(l - 1) : nullptr);
+                pend_k = 0;
+            }
+        int kp = 0;
+        for (int g = 0; g < G.n; ++g) {
+            const QMat* ms[3];
+            int pr[3];
+            for (int k = 0; k < G.cnt[g]; ++k) {
+                ms[k] = mats[G.idx[g][k]];
+                pr[k] = lora_pre_row(l, 0, G.idx[g][k]);   // the parts' rows share the [Q | K | V] layout
+            }
+            kp = launch_mmqs(ms, pr, G.cnt[g], false, 0, ub_act(hp.n_embd, nt, ms[0]->type), ub_spart, qkv_rows, stream);
+        }
+        QkvFinish F{ub_spart, qkv_rows, kp, nt, L.wq.rows, L.wk.rows, L.wv.rows, qb, hp.n_embd, k_layer(l), v_layer(l), kv_dim,
+                    cell_pos, tokpos_b, ub_rope, hp.n_rot, hp.head_dim};
+        launch_qkv_finish(F, stream);
+        AttnParams a = battn_params(l);
+        // within ATTN_SHORT cells the decode step's fused kernel, one workgroup per (kv head, token)
+        // (20-token verify 3.52 -> 3.30 ms against the MFMA kernel's 32-token tiles; 64 tokens
+        // equal, same box)
+        const ActQ8 act_wo = ub_act(hp.n_embd, nt, L.wo.type);
+        const bool qattn = attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim);
+        if (attn_mfma && n_cells > ATTN_SHORT) {
+            launch_attn_mfma(a, nt, attnb, stream);
+            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
+        } else if (qattn) {   // the fused kernel also quantises each token's output for W_o
+            a.act_q8 = act_wo;
+            launch_attn_multi(a, nt, attnb, stream);
+        } else {
+            launch_attn_multi(a, nt, attnb, stream);
+            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
+        }
+        // output projection: parts of W_o attn, added to x by the FFN's quant_act
+        pend_k = mmqs_one(L.wo, false, 0, act_wo, hp.n_embd);
+        if (hp.n_expert > 0) {   // routed experts: x += W_o parts first (the router reads x)
+            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream);
+            pend_k = 0;
+            moe_ffn_short(l, nt);
+            continue;
+        }
+        // FFN gate/up: parts of both, SwiGLU'd by the down input's quant_act
+        const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
+        launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, ub_spart, pend_k);
+        const int kg = mmqs_one(L.gate, true, hp.n_ff, act, 2 * hp.n_ff);
+        const ActQ8 a2 = ub_act(hp.n_ff, nt, L.down.type);
+        launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, nullptr, ub_spart, kg, 1);
+        pend_k = mmqs_one(L.down, false, 0, a2, hp.n_embd);
+    }
+    return pend_k;
+}
+
+}  // namespace mi

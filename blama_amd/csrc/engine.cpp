@@ -1,5 +1,6 @@
 // Engine host code: the decode context -- its buffers, the batch-1 decode schedule captured
-// into HIP graphs, prompt batches, sampling reads and the KV cache (the model: model.cpp).
+// into HIP graphs, sampling reads, the KV cache and state (the model: model.cpp; prompt batches:
+// batch.cpp).
 //
 // Reference anchors (the llama.h functions this replaces):
 //   llama_init_from_model       /root/reference/inference/code/llama/Instance.cpp:36
@@ -350,13 +351,13 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
     p.K = hp.n_embd;
     set_act(p, src, 0, src == ACT_PRO ? 0 : sp[l].fA, x, L.attn_norm, L.attn_norm_b);
     if (hp.arch == ARCH_LLAMA) {   // (GPT-2: learned positions, n_rot 0)
-        p.theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
+        p.theta_scale = theta_scale();
         p.freq_scale = hp.freq_scale;
         p.n_rot = hp.n_rot;
         p.freq_factors = m->rope_freqs;
     }
-    p.kcache = kcache + (size_t)l * n_ctx * kv_dim;
-    p.vcache = vcache + (size_t)l * n_ctx * kv_dim;
+    p.kcache = k_layer(l);
+    p.vcache = v_layer(l);
     int n = 0, row0 = 0;   // row0: the group's first row among [Q | K | V]
     for (int g = 0; g < L.n_qkv; ++n) {
         p.nseg = 0;
@@ -384,9 +385,8 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
 // (r04 step) or attn_combine_quant (streaming step) adds in split order.
 AttnParams Ctx::attn_params(int l, bool quant_out) const {
     const HParams& hp = m->hp;
-    AttnParams a{q, kcache + (size_t)l * n_ctx * kv_dim, vcache + (size_t)l * n_ctx * kv_dim, tokpos, cell_pos,
-                 attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv, hp.head_dim, kv_dim, (int)n_ctx,
-                 1.0f / std::sqrt((float)hp.head_dim)};
+    AttnParams a{q, k_layer(l), v_layer(l), tokpos, cell_pos, attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv,
+                 hp.head_dim, kv_dim, (int)n_ctx, kq_scale()};
     a.fused = attn_fused;
     if (attn_fused) {
         if (quant_out) a.act_out = act_out(1, sp[l].fB, hp.n_embd, nullptr);
@@ -664,34 +664,22 @@ void Ctx::enqueue_step(bool with_logits) {
             // LoRA on gemv_kernel (dense LLaMA geometries the streaming step does not serve): the
             // terms precomputed into lora_pre ahead of the launch that adds them before its epilogue
             const Layer& L = m->layers[l];
-            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
-            if (lq) {
-                const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows}, rows[3] = {L.wq.rows, L.wk.rows, L.wv.rows};
-                lora_shrink(*lq, x, hp.n_embd, hp.n_embd, 1, L.attn_norm);
-                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, rows[i], 1);
-            }
+            lora_pre_terms(l, 0, x, hp.n_embd, 1, L.attn_norm);
             GemvParams qkv[3];
             const int n = qkv_params(l, ACT_PRO, qkv);
             for (int i = 0; i < n; ++i) run_gemv(qkv[i]);
             run_attn(attn_params(l, false));
-            if (lo) {   // the attention output in fp32: the fused launch's one split, or the splits' sum
+            if (lora_group(l, 1)) {   // the attention output in fp32: the fused launch's one split, or the splits' sum
                 if (!attn_fused && seg_on()) launch_attn_combine(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos, attn, stream);
-                lora_shrink(*lo, attn_fused ? part_o : attn, hp.n_embd, hp.n_embd, 1, nullptr);
-                lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, 1);
+                lora_pre_terms(l, 1, attn_fused ? part_o : attn, hp.n_embd, 1, nullptr);
             }
             run_gemv(wo_params(l, ACT_PRO));
             if (hp.n_expert > 0) {
                 enqueue_moe_ffn(l);
             } else {
-                if (lg) {
-                    lora_shrink(*lg, x, hp.n_embd, hp.n_embd, 1, L.ffn_norm);
-                    for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, 1);
-                }
+                lora_pre_terms(l, 2, x, hp.n_embd, 1, L.ffn_norm);
                 run_gemv(gate_up_params(l, ACT_PRO), l, true);
-                if (ld) {
-                    lora_shrink(*ld, h, hp.n_ff, hp.n_ff, 1, nullptr);
-                    lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, 1);
-                }
+                lora_pre_terms(l, 3, h, hp.n_ff, 1, nullptr);
                 run_gemv(down_params(l, ACT_PRO));
             }
         }
@@ -704,7 +692,11 @@ void Ctx::enqueue_output(ActSrc src, const float* xrow, unsigned long long* stam
     GemvParams p = head_params(src, xrow);
     p.stamps = stamps_slab;
     (src == ACT_PRO ? launch_gemv : launch_dgemv)(p, stream, nullptr, nullptr);
-    TopkParams tp{logits, m->hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
+    run_topk(logits);
+}
+
+void Ctx::run_topk(const float* src) {
+    TopkParams tp{src, m->hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
     launch_topk(tp, stream);
 }
 
@@ -726,596 +718,6 @@ hipGraphExec_t Ctx::build_graph(bool with_logits, int seg) {
     MI_HIP(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
     MI_HIP(hipGraphDestroy(g));
     return ex;
-}
-
-// Prompt ingestion: n tokens in chunks of GEMM_NT, every weight matrix streamed once per
-// chunk (launch_gemm), causal attention of the chunk's tokens (launch_attn_multi), the
-// output head for the last token only (llama_batch_get_one: logits of the last token).
-void Ctx::decode_batch(const int32_t* tokens, int n) {
-    const HParams& hp = m->hp;
-    const float theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    const int chunk = GEMM_NT;
-    // one projection on the v_dot4 GEMM, which quantises its own rows
-    auto proj = [&](GemmParams p, const float* x, int x_stride, const float* norm, bool) {
-        p.x = x;
-        p.x_stride = x_stride;
-        p.norm_w = norm;
-        p.pro = norm ? PRO_RMSNORM : PRO_PLAIN;
-        launch_gemm(p, stream);
-    };
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nt = std::min(chunk, n - c0);
-        const long long slot = tokb_slot++ % kTokbRing;
-        if (slot == 0 && tokb_slot > 1) MI_HIP(hipStreamSynchronize(stream));
-        int* hpos = h_tokpos_b + slot * kBatchRows * 4;
-        for (int t = 0; t < nt; ++t) {
-            const int pos = pos_max + 1, cell = n_cells;
-            hpos[t * 4 + 0] = tokens[c0 + t];
-            hpos[t * 4 + 1] = pos;
-            hpos[t * 4 + 2] = cell;
-            hpos[t * 4 + 3] = 0;
-            h_cell_pos[cell] = pos;
-            n_cells++;
-            pos_max = pos;
-        }
-        MI_HIP(hipMemcpyAsync(tokpos_b, hpos, nt * 4 * sizeof(int), hipMemcpyHostToDevice, stream));
-        EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
-        launch_embed_multi(ep, nt, stream);
-        for (int l = 0; l < hp.n_layer; ++l) {
-            const Layer& L = m->layers[l];
-            __half* kl = kcache + (size_t)l * n_ctx * kv_dim;
-            __half* vl = vcache + (size_t)l * n_ctx * kv_dim;
-            GemmParams b;
-            std::memset(&b, 0, sizeof(b));
-            b.ntok = nt;
-            b.tokpos = tokpos_b;
-            b.cell_pos = cell_pos;
-            b.theta_scale = theta_scale;
-            b.freq_scale = hp.freq_scale;
-            b.head_dim = hp.head_dim;
-            b.freq_factors = m->rope_freqs;
-            b.kcache = kl;
-            b.vcache = vl;
-            b.kv_dim = kv_dim;
-            b.eps = hp.eps;
-            // Q / K / V projections (+ RoPE, KV append)
-            const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
-            const int epis[3] = {EPI_ROPE_Q, EPI_ROPE_K, EPI_V};
-            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
-            const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows};
-            if (lq) {   // LoRA: the Q/K/V terms of the chunk, added before RoPE and the KV append
-                lora_shrink(*lq, xb, hp.n_embd, hp.n_embd, nt, L.attn_norm);
-                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, mats[i]->rows, nt);
-            }
-            for (int i = 0; i < 3; ++i) {
-                GemmParams p = b;
-                p.A = *mats[i];
-                p.pair = PAIR_ADJ;
-                p.epi = epis[i];
-                p.units = (mats[i]->rows + 1) / 2;
-                p.K = hp.n_embd;
-                p.out = qb;
-                p.out_stride = hp.n_embd;
-                p.n_rot = i < 2 ? hp.n_rot : 0;
-                if (lq) {
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                    p.pre_off = prow[i];
-                }
-                proj(p, xb, hp.n_embd, L.attn_norm, i == 0);   // the three share one quantisation
-            }
-            AttnParams a{qb, kl, vl, tokpos_b, cell_pos, attn_scores, attn_smax, attnb, hp.n_head, hp.n_head_kv,
-                         hp.head_dim, kv_dim, (int)n_ctx, kq_scale};
-            launch_attn_multi(a, nt, attnb, stream);
-            if (lo) {
-                lora_shrink(*lo, attnb, hp.n_embd, hp.n_embd, nt, nullptr);
-                lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
-            }
-            {   // output projection + residual
-                GemmParams p = b;
-                p.A = L.wo;
-                p.pair = PAIR_ADJ;
-                p.epi = EPI_ADD;
-                if (lo) {
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                }
-                p.units = (L.wo.rows + 1) / 2;
-                p.K = hp.n_embd;
-                p.out = xb;
-                p.resid = xb;
-                p.out_stride = hp.n_embd;
-                proj(p, attnb, hp.n_embd, nullptr, true);
-            }
-            if (lg) {   // the gate and up terms, added before SwiGLU
-                lora_shrink(*lg, xb, hp.n_embd, hp.n_embd, nt, L.ffn_norm);
-                for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, nt);
-            }
-            {   // FFN gate/up + SwiGLU
-                GemmParams p = b;
-                p.A = L.gate;
-                p.B = L.up;
-                p.pair = PAIR_AB;
-                p.epi = EPI_SWIGLU;
-                p.units = L.gate.rows;
-                p.K = hp.n_embd;
-                p.out = hb;
-                p.out_stride = hp.n_ff;
-                if (lg) {
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                    p.pre_up = hp.n_ff;
-                }
-                proj(p, xb, hp.n_embd, L.ffn_norm, true);
-            }
-            if (ld) {
-                lora_shrink(*ld, hb, hp.n_ff, hp.n_ff, nt, nullptr);
-                lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
-            }
-            {   // FFN down + residual
-                GemmParams p = b;
-                p.A = L.down;
-                p.pair = PAIR_ADJ;
-                p.epi = EPI_ADD;
-                if (ld) {
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                }
-                p.units = (L.down.rows + 1) / 2;
-                p.K = hp.n_ff;
-                p.out = xb;
-                p.resid = xb;
-                p.addend = cvec_for(l);
-                p.out_stride = hp.n_embd;
-                proj(p, hb, hp.n_ff, nullptr, true);
-            }
-        }
-        if (c0 + nt == n) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
-    }
-    logits_valid = true;
-}
-
-// build_moe_ffn (src/llama-graph.cpp, b5187: softmax gating, top-2, weights normalised) over a
-// physical batch, all on the device: the router of every token (the decode step's router_kernel),
-// the (token, slot) picks grouped by expert (launch_moe_group: tokens ascending within an expert,
-// each expert's rows whole 32-row MFMA tiles), one quantisation of every row, ONE grouped mmq32
-// launch for the experts' gate/up + SwiGLU and one for their down projections (a workgroup per
-// (expert, row tile) over that expert's token tiles), then every token's x += w0*y0 + w1*y1 in
-// slot order (launch_moe_combine, the decode GEMV's EPI_MOE_DOWN arithmetic).  No host round trip.
-void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
-    const HParams& hp = m->hp;
-    const Layer& L = m->layers[l];
-    const int U = hp.n_expert_used, E = hp.n_expert;
-    RouterParams rp{xb, L.ffn_norm, hp.eps, L.router, hp.n_embd, E, U, sel_b, selw_b, hp.n_embd, pend, nt};
-    launch_router_multi(rp, nt, stream);
-    const int cap = moe_rows_cap(nt * U, E);
-    launch_moe_group(sel_b, nt * U, U, E, moe_grp, moe_rows, moe_rowsel, moe_pos, cap, stream);
-    auto act_of = [&](int K, int type) {
-        ActQ8 a;
-        a.q = moe_q;
-        a.dT = moe_dT;
-        a.bsb = moe_bsb;
-        a.K = K;
-        a.ntok = cap;
-        a.npad = cap;
-        a.q80 = type == T_Q8_0 ? 1 : 0;
-        return a;
-    };
-    GemmParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.ntok = cap;
-    p.tokpos = tokpos_b;
-    p.grp = moe_grp;
-    p.grp_n = E;
-    p.grp_max = nt;
-    // gate/up + SwiGLU: rms_norm(x) * ffn_norm of each row's token
-    const ActQ8 act = act_of(hp.n_embd, L.gate.type);
-    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
-    p.A = L.gate;
-    p.B = L.up;
-    p.pair = PAIR_AB;
-    p.epi = EPI_SWIGLU;
-    p.K = hp.n_embd;
-    p.out = hb;
-    p.out_stride = hp.n_ff;
-    p.grp_stride = L.gate.sw_expert_stride;
-    launch_mmq32(p, act, ub_rope, stream);
-    // down: every row of the FFN output, stored (weighted and summed by the combine)
-    const ActQ8 a2 = act_of(hp.n_ff, L.down.type);
-    launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel);
-    GemmParams d = p;
-    d.A = L.down;
-    std::memset(&d.B, 0, sizeof(d.B));
-    d.pair = PAIR_ADJ;
-    d.epi = EPI_STORE;
-    d.K = hp.n_ff;
-    d.out = yb;
-    d.out_stride = hp.n_embd;
-    d.grp_stride = L.down.sw_expert_stride;
-    launch_mmq32(d, a2, ub_rope, stream);
-    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
-}
-
-// The same build_moe_ffn over a short batch (<= MMQS_MAX tokens; x already holds the residual) on
-// the grouped streaming GEMM: router, grouping, one quantisation of every MoE row, the experts'
-// gate/up pair parts (launch_mmqs_grouped: workgroups per (row tile, K-part, expert, 32-row tile),
-// each expert's matrix streamed once for the rows routed to it), SwiGLU of the parts quantised for
-// down, down's parts, their sum per row, then every token's x += w0*y0 + w1*y1 in slot order.
-void Ctx::moe_ffn_short(int l, int nt) {
-    const HParams& hp = m->hp;
-    const Layer& L = m->layers[l];
-    const int U = hp.n_expert_used, E = hp.n_expert;
-    RouterParams rp{xb, L.ffn_norm, hp.eps, L.router, hp.n_embd, E, U, sel_b, selw_b, hp.n_embd, nullptr, nt};
-    launch_router_multi(rp, nt, stream);
-    const int cap = moe_rows_cap(nt * U, E);
-    launch_moe_group(sel_b, nt * U, U, E, moe_grp, moe_rows, moe_rowsel, moe_pos, cap, stream);
-    auto act_of = [&](int K) {
-        ActQ8 a;
-        a.q = moe_q;
-        a.dT = moe_dT;
-        a.bsb = moe_bsb;
-        a.K = K;
-        a.ntok = cap;
-        a.npad = cap;
-        a.q80 = 0;
-        return a;
-    };
-    const ActQ8 act = act_of(hp.n_embd);
-    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
-    // an expert receives each token at most once: at most nt rows
-    const int kg = launch_mmqs_grouped(L.gate, true, hp.n_ff, act, ub_spart, 2 * hp.n_ff, moe_grp, E, nt, stream);
-    const ActQ8 a2 = act_of(hp.n_ff);
-    launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel, ub_spart, kg, 1);
-    const int kd = launch_mmqs_grouped(L.down, false, 0, a2, ub_spart, hp.n_embd, moe_grp, E, nt, stream);
-    launch_part_sum(ub_spart, kd, cap, hp.n_embd, hp.n_embd, nullptr, 0, yb, hp.n_embd, stream);
-    launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
-}
-
-ActQ8 Ctx::ub_act(int K, int ntok, int type) const {
-    const bool q80 = type == T_Q8_0;
-    const bool second = q80 && !ub_q80 && ub_q0;   // the Q8_0 set of a mixed model
-    ActQ8 a;
-    a.q = second ? ub_q0 : ub_q;
-    a.dT = second ? ub_dT0 : ub_dT;
-    a.bsb = ub_bsb;
-    a.K = K;
-    a.ntok = ntok;
-    a.npad = (ntok + 31) / 32 * 32;
-    a.q80 = q80 ? 1 : 0;
-    return a;
-}
-
-// Prompt ingestion / batched verification in physical batches of up to UB_MAX tokens on the
-// int8-MFMA GEMM (mmq.hip): per layer every weight matrix is streamed once per batch; each
-// activation is quantised to Q8_K once (RMSNorm fused) and shared by the matrices that read it.
-// `all`: the output head runs over every token (rows of logits_all), else over the last one.
-void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
-    const HParams& hp = m->hp;
-    const float theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    for (int c0 = 0; c0 < n; c0 += UB_MAX) {
-        const int nt = std::min(UB_MAX, n - c0);
-        const long long slot = tokb_slot++ % kTokbRing;
-        if (slot == 0 && tokb_slot > 1) MI_HIP(hipStreamSynchronize(stream));
-        int* hpos = h_tokpos_b + slot * kBatchRows * 4;
-        for (int t = 0; t < nt; ++t) {
-            const int pos = pos_max + 1, cell = n_cells;
-            hpos[t * 4 + 0] = tokens[c0 + t];
-            hpos[t * 4 + 1] = pos;
-            hpos[t * 4 + 2] = cell;
-            hpos[t * 4 + 3] = 0;
-            h_cell_pos[cell] = pos;
-            n_cells++;
-            pos_max = pos;
-        }
-        MI_HIP(hipMemcpyAsync(tokpos_b, hpos, nt * 4 * sizeof(int), hipMemcpyHostToDevice, stream));
-        // (a context with a LoRA adapter runs its short batches on the tiled form below, whose
-        // epilogues take the adapter's terms; split-K is off for the W_o / down launches an adapter
-        // targets, and pending parts are added by the quant_act that precedes every shrink)
-        if (mmqs_max > 0 && nt <= mmqs_max && short_ok() && !lora_on()) {   // a short batch (its launches captured as a
-            // hipGraph measured no faster: the GPU, not the enqueue, sets the pace)
-            enqueue_ubatch_short(nt, all, c0, c0 + nt == n);
-            continue;
-        }
-        EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
-        launch_embed_multi(ep, nt, stream);
-        launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale, hp.freq_scale, m->rope_freqs, ub_rope, stream);
-        const float* pend = nullptr;   // split-K partials not yet added into xb (the next quant_act does)
-        const float* pend_add = nullptr;   // the control-vector row that goes in after them (FFN down's parts)
-        // split-K parts of the residual GEMMs: 4 for short batches of dense models (verification
-        // of tens of tokens: more workgroups, a quarter of the superblock steps each; 4 x nt rows
-        // fit the 2 x UB_MAX partials buffer), else 2 (the MoE router adds 2)
-        const int ks = hp_dense() && nt <= 64 ? 4 : 2;   // 4 x 64 rows fit the 2 x UB_MAX partials buffer
-        for (int l = 0; l < hp.n_layer; ++l) {
-            const Layer& L = m->layers[l];
-            __half* kl = kcache + (size_t)l * n_ctx * kv_dim;
-            __half* vl = vcache + (size_t)l * n_ctx * kv_dim;
-            GemmParams b;
-            std::memset(&b, 0, sizeof(b));
-            b.ntok = nt;
-            b.tokpos = tokpos_b;
-            b.cell_pos = cell_pos;
-            b.head_dim = hp.head_dim;
-            b.n_rot = hp.n_rot;
-            b.kcache = kl;
-            b.vcache = vl;
-            b.kv_dim = kv_dim;
-            b.K = hp.n_embd;
-            b.out_stride = hp.n_embd;
-            // Q / K / V (+ RoPE, KV append) over one quantisation of rms_norm(x) * attn_norm per
-            // activation format the three matrices read
-            const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
-            const int epis[3] = {EPI_ROPE_Q, EPI_ROPE_K, EPI_V};
-            for (int f = 0; f < 2; ++f) {
-                bool need = false;
-                for (const QMat* q : mats) need = need || (q->type == T_Q8_0) == (f == 1);
-                if (need) {
-                    launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                     nullptr, pend, ks, 0, pend ? pend_add : nullptr);
-                    pend = nullptr;
-                }
-            }
-            const LoraGroup *lq = lora_group(l, 0), *lo = lora_group(l, 1), *lg = lora_group(l, 2), *ld = lora_group(l, 3);
-            const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows};
-            if (lq) {   // LoRA: the Q/K/V terms of the batch, added before RoPE and the KV append
-                lora_shrink(*lq, xb, hp.n_embd, hp.n_embd, nt, L.attn_norm);
-                for (int i = 0; i < 3; ++i) lora_expand(*lq, i, lora_pre + prow[i], lora_pre_stride, mats[i]->rows, nt);
-            }
-            // the matrices of one type in one launch (7B: Q/K/V, or Q/K plus a Q6_K V)
-            for (int i = 0; i < 3; ++i) {
-                bool first = true;
-                for (int j = 0; j < i; ++j) first = first && mats[j]->type != mats[i]->type;
-                if (!first) continue;
-                GemmParams ps[3];
-                int n = 0;
-                for (int j = i; j < 3; ++j) {
-                    if (mats[j]->type != mats[i]->type) continue;
-                    ps[n] = b;
-                    ps[n].A = *mats[j];
-                    ps[n].pair = PAIR_ADJ;
-                    ps[n].epi = epis[j];
-                    ps[n].out = qb;
-                    if (lq) {
-                        ps[n].pre = lora_pre;
-                        ps[n].pre_stride = lora_pre_stride;
-                        ps[n].pre_off = prow[j];
-                    }
-                    ++n;
-                }
-                launch_mmq32_multi(ps, n, ub_act(hp.n_embd, nt, mats[i]->type), ub_rope, stream);
-            }
-            AttnParams a{qb, kl, vl, tokpos_b, cell_pos, attn_scores, attn_smax, attnb, hp.n_head, hp.n_head_kv,
-                         hp.head_dim, kv_dim, (int)n_ctx, kq_scale};
-            if (attn_mfma) launch_attn_mfma(a, nt, attnb, stream);
-            else launch_attn_multi(a, nt, attnb, stream);
-            {   // output projection + residual
-                const ActQ8 act = ub_act(hp.n_embd, nt, L.wo.type);
-                launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act, stream);
-                GemmParams p = b;
-                if (lo) {   // before the residual add
-                    lora_shrink(*lo, attnb, hp.n_embd, hp.n_embd, nt, nullptr);
-                    lora_expand(*lo, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                }
-                p.A = L.wo;
-                p.pair = PAIR_ADJ;
-                p.epi = EPI_ADD;
-                p.out = xb;
-                p.resid = xb;
-                // parts of K; the FFN's quant_act adds them (not with an adapter on this W_o: its terms
-                // go in ahead of the residual add, which a split launch leaves to the next kernel)
-                if (ub_part && L.wo.nb >= ks && !lo) {
-                    p.ksplit = ks;
-                    p.part = ub_part;
-                    pend = ub_part;
-                }
-                launch_mmq32(p, act, ub_rope, stream);
-            }
-            if (hp.n_expert > 0) {   // routed experts (build_moe_ffn) + residual
-                moe_ffn_batch(l, nt, pend);
-                pend = nullptr;
-                continue;
-            }
-            {   // FFN gate/up + SwiGLU
-                const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
-                launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, pend, ks);
-                pend = nullptr;
-                GemmParams p = b;
-                p.A = L.gate;
-                p.B = L.up;
-                p.pair = PAIR_AB;
-                p.epi = EPI_SWIGLU;
-                p.out = hb;
-                p.out_stride = hp.n_ff;
-                if (lg) {   // the gate and up terms, added before SwiGLU
-                    lora_shrink(*lg, xb, hp.n_embd, hp.n_embd, nt, L.ffn_norm);
-                    for (int i = 0; i < 2; ++i) lora_expand(*lg, i, lora_pre + (size_t)i * hp.n_ff, lora_pre_stride, hp.n_ff, nt);
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                    p.pre_up = hp.n_ff;
-                }
-                launch_mmq32(p, act, ub_rope, stream);
-            }
-            {   // FFN down + residual
-                const ActQ8 act = ub_act(hp.n_ff, nt, L.down.type);
-                launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, act, stream);
-                GemmParams p = b;
-                if (ld) {
-                    lora_shrink(*ld, hb, hp.n_ff, hp.n_ff, nt, nullptr);
-                    lora_expand(*ld, 0, lora_pre, lora_pre_stride, hp.n_embd, nt);
-                    p.pre = lora_pre;
-                    p.pre_stride = lora_pre_stride;
-                }
-                p.A = L.down;
-                p.pair = PAIR_ADJ;
-                p.epi = EPI_ADD;
-                p.K = hp.n_ff;
-                p.out = xb;
-                p.resid = xb;
-                if (ub_part && L.down.nb >= ks && l + 1 < hp.n_layer && !ld) {   // the next layer's quant_act adds them
-                    p.ksplit = ks;
-                    p.part = ub_part;
-                    pend = ub_part;
-                    pend_add = cvec_for(l);
-                } else {
-                    p.addend = cvec_for(l);
-                }
-                launch_mmq32(p, act, ub_rope, stream);
-            }
-        }
-        if (all) {   // final norm + output head over every token of the batch
-            const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);   // the head's own activation format
-            launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream);
-            GemmParams p;
-            std::memset(&p, 0, sizeof(p));
-            p.A = m->output;
-            p.pair = PAIR_ADJ;
-            p.epi = EPI_STORE;
-            p.K = hp.n_embd;
-            p.ntok = nt;
-            p.tokpos = tokpos_b;
-            p.out = logits_all + (size_t)c0 * hp.n_vocab;
-            p.out_stride = hp.n_vocab;
-            launch_mmq32(p, a_out, ub_rope, stream);
-            if (c0 + nt == n) {   // the last row also feeds `logits` and the mapped top-k
-                MI_HIP(hipMemcpyAsync(logits, logits_all + (size_t)(n - 1) * hp.n_vocab, (size_t)hp.n_vocab * sizeof(float),
-                                      hipMemcpyDeviceToDevice, stream));
-                TopkParams tp{logits, hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
-                launch_topk(tp, stream);
-            }
-        } else if (c0 + nt == n) {
-            enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
-        }
-    }
-    logits_valid = true;
-}
-
-// One short physical batch (tokens uploaded to tokpos_b): embedding, the rope table, the layers on
-// mmqs, then the output -- every token's logits rows (`all`, rows c0.. of logits_all; the last
-// chunk's last row also feeds `logits` and the top-k) or the last token's through the decode head.
-void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
-    const HParams& hp = m->hp;
-    const float theta_scale = std::pow(hp.rope_base, -2.0f / (float)hp.n_rot);
-    EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
-    launch_embed_multi(ep, nt, stream);
-    launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale, hp.freq_scale, m->rope_freqs, ub_rope, stream);
-    const int pend_k = ubatch_layers_short(nt);
-    // (the parts pending are the last layer's FFN down's -- dense models; its control-vector row
-    // goes in with them)
-    const float* pend_add = pend_k ? cvec_for(hp.n_layer - 1) : nullptr;
-    if (all) {   // final norm + output head on mmqs, its parts summed into the logits rows
-        const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);
-        launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream, nullptr, pend_k ? ub_spart : nullptr,
-                         pend_k ? pend_k : 2, 0, pend_add);
-        const QMat* mo[1] = {&m->output};
-        const int pr[1] = {0};
-        const int kp = launch_mmqs(mo, pr, 1, false, 0, a_out, ub_spart, hp.n_vocab, stream);
-        launch_part_sum(ub_spart, kp, nt, hp.n_vocab, hp.n_vocab, nullptr, 0, logits_all + (size_t)c0 * hp.n_vocab,
-                        hp.n_vocab, stream);
-        if (last) {
-            MI_HIP(hipMemcpyAsync(logits, logits_all + (size_t)(c0 + nt - 1) * hp.n_vocab, (size_t)hp.n_vocab * sizeof(float),
-                                  hipMemcpyDeviceToDevice, stream));
-            TopkParams tp{logits, hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
-            launch_topk(tp, stream);
-        }
-    } else {
-        // the last residual parts into xb (the next chunk, or the output, reads it)
-        if (pend_k)
-            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream, 0, pend_add);
-        if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
-    }
-}
-
-// One short physical batch (<= mmqs_max tokens) through the layers on the split-K streaming GEMM
-// (mmq.hip mmqs): every launch writes K-part sums to ub_spart, and the next kernel adds them --
-// quant_act (the residual, or SwiGLU of the gate/up parts), qkv_finish (RoPE, KV append).
-// Returns the count of the last FFN down's parts, still to be added into xb.
-int Ctx::ubatch_layers_short(int nt) {
-    const HParams& hp = m->hp;
-    const float kq_scale = 1.0f / std::sqrt((float)hp.head_dim);
-    const int qkv_rows = hp.n_embd + 2 * kv_dim;
-    int pend_k = 0;   // residual parts of ub_spart not yet added into xb
-    for (int l = 0; l < hp.n_layer; ++l) {
-        const Layer& L = m->layers[l];
-        __half* kl = kcache + (size_t)l * n_ctx * kv_dim;
-        __half* vl = vcache + (size_t)l * n_ctx * kv_dim;
-        // Q / K / V: one quantisation of rms_norm(x) * attn_norm per activation format (the first
-        // also adds the residual parts), the matrices of one type in one launch, rows [Q | K | V]
-        const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
-        const int prow[3] = {0, L.wq.rows, L.wq.rows + L.wk.rows};
-        for (int f = 0; f < 2; ++f) {
-            bool need = false;
-            for (const QMat* q : mats) need = need || (q->type == T_Q8_0) == (f == 1);
-            if (need) {
-                // (parts pending here are the previous layer's FFN down's: its control-vector row with them)
-                launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                 nullptr, pend_k ? ub_spart : nullptr, pend_k ? pend_k : 2, 0,
-                                 pend_k && l > 0 ? cvec_for(l - 1) : nullptr);
-                pend_k = 0;
-            }
-        }
-        int kp = 0;
-        for (int i = 0; i < 3; ++i) {
-            bool first = true;
-            for (int j = 0; j < i; ++j) first = first && mats[j]->type != mats[i]->type;
-            if (!first) continue;
-            const QMat* ms[3];
-            int pr[3], n = 0;
-            for (int j = i; j < 3; ++j)
-                if (mats[j]->type == mats[i]->type) {
-                    ms[n] = mats[j];
-                    pr[n++] = prow[j];
-                }
-            kp = launch_mmqs(ms, pr, n, false, 0, ub_act(hp.n_embd, nt, mats[i]->type), ub_spart, qkv_rows, stream);
-        }
-        QkvFinish F{ub_spart, qkv_rows, kp, nt, L.wq.rows, L.wk.rows, L.wv.rows, qb, hp.n_embd, kl, vl, kv_dim, cell_pos,
-                    tokpos_b, ub_rope, hp.n_rot, hp.head_dim};
-        launch_qkv_finish(F, stream);
-        AttnParams a{qb, kl, vl, tokpos_b, cell_pos, attn_scores, attn_smax, attnb, hp.n_head, hp.n_head_kv,
-                     hp.head_dim, kv_dim, (int)n_ctx, kq_scale};
-        // within ATTN_SHORT cells the decode step's fused kernel, one workgroup per (kv head, token)
-        // (20-token verify 3.52 -> 3.30 ms against the MFMA kernel's 32-token tiles; 64 tokens
-        // equal, same box)
-        const ActQ8 act_wo = ub_act(hp.n_embd, nt, L.wo.type);
-        const bool qattn = attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim);
-        if (attn_mfma && n_cells > ATTN_SHORT) {
-            launch_attn_mfma(a, nt, attnb, stream);
-            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
-        } else if (qattn) {   // the fused kernel also quantises each token's output for W_o
-            a.act_q8 = act_wo;
-            launch_attn_multi(a, nt, attnb, stream);
-        } else {
-            launch_attn_multi(a, nt, attnb, stream);
-            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
-        }
-        {   // output projection: parts of W_o attn, added to x by the FFN's quant_act
-            const ActQ8& act = act_wo;
-            const QMat* mo[1] = {&L.wo};
-            const int pr[1] = {0};
-            pend_k = launch_mmqs(mo, pr, 1, false, 0, act, ub_spart, hp.n_embd, stream);
-        }
-        if (hp.n_expert > 0) {   // routed experts: x += W_o parts first (the router reads x)
-            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream);
-            pend_k = 0;
-            moe_ffn_short(l, nt);
-            continue;
-        }
-        {   // FFN gate/up: parts of both, SwiGLU'd by the down input's quant_act
-            const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
-            launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, ub_spart, pend_k);
-            pend_k = 0;
-            const QMat* mg[1] = {&L.gate};
-            const int pr[1] = {0};
-            const int kg = launch_mmqs(mg, pr, 1, true, hp.n_ff, act, ub_spart, 2 * hp.n_ff, stream);
-            const ActQ8 a2 = ub_act(hp.n_ff, nt, L.down.type);
-            launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, nullptr, ub_spart, kg, 1);
-            const QMat* md[1] = {&L.down};
-            pend_k = launch_mmqs(md, pr, 1, false, 0, a2, ub_spart, hp.n_embd, stream);
-        }
-    }
-    return pend_k;
 }
 
 int Ctx::decode(const int32_t* tokens, int n, bool all) {
@@ -1436,8 +838,7 @@ int Ctx::topk(int row, int k, int32_t* ids, float* vals) {
     const float* src = out_row(row);
     if (src != logits || topk_row != -1) {   // another row than the mapped buffers hold
         MI_HIP(hipSetDevice(device));
-        TopkParams tp{src, m->hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
-        launch_topk(tp, stream);
+        run_topk(src);
         topk_row = src == logits ? -1 : row;
     }
     sync();
@@ -1567,7 +968,7 @@ int Ctx::kv_seq_shift(int p0, int p1, int delta, int div) {
         const HParams& hp = m->hp;
         MI_HIP(hipMemcpyAsync(cell_delta, dlt.data(), n_cells * sizeof(int), hipMemcpyHostToDevice, stream));
         KvShiftParams kp{kcache, hp.n_layer, (int)n_ctx, kv_dim, hp.head_dim, hp.n_rot, cell_delta, n_cells,
-                         std::pow(hp.rope_base, -2.0f / (float)hp.n_rot), hp.freq_scale, m->rope_freqs};
+                         theta_scale(), hp.freq_scale, m->rope_freqs};
         launch_kv_shift(kp, stream);
         MI_HIP(hipMemcpyAsync(cell_pos, h_cell_pos.data(), n_cells * sizeof(int), hipMemcpyHostToDevice, stream));
         sync();
@@ -1654,8 +1055,7 @@ size_t Ctx::state_set(const uint8_t* src, size_t size) {
     logits_valid = hd.logits_valid != 0;
     if (logits_valid) {
         MI_HIP(hipMemcpy(logits, s, (size_t)hp.n_vocab * sizeof(float), hipMemcpyHostToDevice));
-        TopkParams tp{logits, hp.n_vocab, cand, topk_ids, topk_vals, d_h_topk_ids, d_h_topk_vals};
-        launch_topk(tp, stream);
+        run_topk(logits);
         sync();
     }
     return need;

@@ -1,7 +1,9 @@
-// Engine internals: GGUF parsing and the device-resident model (model.cpp), the decode
-// context (engine.cpp).  The public surface is the C ABI in include/mi_engine.h.
+// Engine internals: GGUF parsing and the device-resident model (model.cpp), the decode context
+// (engine.cpp: buffers, the decode step, graphs, sampling reads, KV cache, state; batch.cpp: the
+// prompt-batch paths; lora.cpp: adapters).  The public surface is the C ABI in include/mi_engine.h.
 #pragma once
 #include <mutex>
+#include <cmath>
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
@@ -282,6 +284,21 @@ struct Ctx {
     void lora_shrink(const LoraGroup& G, const float* xin, int x_stride, int K, int ntok, const float* norm_w);
     // tensor i of the group: out[tok][row] = its terms (zeros when it has no adapter)
     void lora_expand(const LoraGroup& G, int i, float* out, int out_stride, int rows, int ntok);
+    // The terms of group g of layer l for the launches that take them precomputed (GemvSeg::pre,
+    // GemmParams::pre): the shrink over act [ntok][K] (rms_norm'd with norm_w when set) and every
+    // tensor's expand into lora_pre, row layout lora_pre_row.  Returns lora_pre, or null when the
+    // group has no adapter (nothing launched).
+    const float* lora_pre_terms(int l, int g, const float* act, int K, int ntok, const float* norm_w);
+    // first row of tensor i of group g in a lora_pre row: [Q | K | V], [W_o], [gate | up], [down]
+    int lora_pre_row(int l, int g, int i) const;
+    // the terms at `pre` (null: none) into a GEMM launch: tensor i of group g (a gate/up pair: i = 0)
+    void set_pre(GemmParams& p, const float* pre, int l, int g, int i) const {
+        if (!pre) return;
+        p.pre = pre;
+        p.pre_stride = lora_pre_stride;
+        p.pre_off = lora_pre_row(l, g, i);
+        p.pre_up = p.pair == PAIR_AB ? lora_pre_row(l, g, 1) : 0;
+    }
     // diagnostics (MI_STAMPS builds only): s_memrealtime stamps of every
     // workgroup of every launch of the last enqueued step [launch][wg][8]
     static constexpr int kStampLaunches = 320, kStampWgs = 512;
@@ -360,6 +377,40 @@ struct Ctx {
     ActOut act_out(int role, int fmt, int K, const float* norm_w) const;
     void set_act(GemvParams& p, ActSrc src, int role, int fmt, const float* xin, const float* norm_w,
                  const float* norm_b) const;
+    // values every path's launches share
+    __half* k_layer(int l) const { return kcache + (size_t)l * n_ctx * kv_dim; }
+    __half* v_layer(int l) const { return vcache + (size_t)l * n_ctx * kv_dim; }
+    float theta_scale() const { return std::pow(m->hp.rope_base, -2.0f / (float)m->hp.n_rot); }
+    float kq_scale() const { return 1.0f / std::sqrt((float)m->hp.head_dim); }
+    void run_topk(const float* src);    // top-k of a logits row into the device and the mapped buffers
+    // ---- the parameter block of each batch launch, built in one place (batch.cpp) for the three
+    // batch paths: decode_batch (v_dot4 GEMM), decode_ubatch (tiled mmq32), ubatch_layers_short (mmqs)
+    // the next nt tokens into a ring slot and tokpos_b, the cell mirror advanced
+    void upload_batch(const int32_t* tokens, int nt);
+    // the dense layer's GEMMs over nt rows.  vdot4: the launch's own RoPE scalars and eps (the caller
+    // adds its input row, prologue and units); else mmq32's form, which reads the rope table.  pre:
+    // lora_pre_terms' result for the launch's group.  The caller sets ksplit / part.
+    GemmParams gemm_base(int l, int nt, bool vdot4) const;
+    GemmParams bqkv_params(int l, int nt, bool vdot4, int i, const float* pre) const;   // i: Q, K, V
+    GemmParams bwo_params(int l, int nt, bool vdot4, const float* pre) const;
+    GemmParams bgate_up_params(int l, int nt, bool vdot4, const float* pre) const;
+    GemmParams bdown_params(int l, int nt, bool vdot4, const float* pre) const;   // addend: the control vector's row
+    AttnParams battn_params(int l) const;
+    // Q / K / V by type: the activation formats they read (bit 0 Q8_K, bit 1 Q8_0) and the launches,
+    // each the matrices of one type (idx: 0 Q, 1 K, 2 V, ascending; launches ordered by their first)
+    struct QkvGroups {
+        int fmt, n, cnt[3], idx[3][3];
+    };
+    static QkvGroups qkv_type_groups(const Layer& L);
+    // one matrix (or gate/up pair) on mmqs, its rows from 0 of the parts; returns the part count
+    int mmqs_one(const QMat& A, bool pair, int nff, const ActQ8& act, int pstride);
+    // MoE: router and grouping of nt tokens (pend: W_o's split-K parts, added first); returns the
+    // row capacity.  moe_act: the grouped rows' activation buffers.
+    int moe_route(int l, int nt, const float* pend);
+    ActQ8 moe_act(int K, int cap, bool q80) const;
+    // MI_OUT_ALL: after rows c0.. of logits_all are written, the last chunk's last row also feeds
+    // `logits` and the mapped top-k
+    void finish_logits_all(int c0, int nt, bool last);
     // ---- the profiling gate of the step being enqueued: with seg_filter >= 0 only the launches of
     // that segment go out (0: up to layer prof_layer's FFN gate/up, 1: that launch, 2: the rest)
     int enq_seg = 0, enq_launch = 0;

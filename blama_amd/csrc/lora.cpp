@@ -353,4 +353,26 @@ void Ctx::lora_expand(const LoraGroup& G, int i, float* out, int out_stride, int
     launch_lora_expand(p, stream);
 }
 
+// rows of tensor i of group g (0: the group has no such tensor); a lora_pre row holds them in order
+static int lora_rows(const Model& m, int l, int g, int i) {
+    const Layer& L = m.layers[l];
+    const int rows[4][3] = {{L.wq.rows, L.wk.rows, L.wv.rows}, {m.hp.n_embd, 0, 0}, {m.hp.n_ff, m.hp.n_ff, 0}, {m.hp.n_embd, 0, 0}};
+    return i < 3 ? rows[g][i] : 0;
+}
+
+int Ctx::lora_pre_row(int l, int g, int i) const {
+    int row = 0;
+    for (int j = 0; j < i; ++j) row += lora_rows(*m, l, g, j);
+    return row;
+}
+
+const float* Ctx::lora_pre_terms(int l, int g, const float* act, int K, int ntok, const float* norm_w) {
+    const LoraGroup* G = lora_group(l, g);
+    if (!G) return nullptr;
+    lora_shrink(*G, act, K, K, ntok, norm_w);
+    for (int i = 0; lora_rows(*m, l, g, i); ++i)
+        lora_expand(*G, i, lora_pre + lora_pre_row(l, g, i), lora_pre_stride, lora_rows(*m, l, g, i), ntok);
+    return lora_pre;
+}
+
 }  // namespace mi
