@@ -175,9 +175,10 @@ void Ctx::decode_batch(const int32_t* tokens, int n) {
             pre = lora_pre_terms(l, 3, hb, hp.n_ff, nt, nullptr);
             proj(bdown_params(l, nt, true, pre), hb, nullptr);
         }
-        if (c0 + nt == n) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+        if (embeddings) embd_tail(xb, nt, c0);   // embeddings mode: the chunk's rows, no head
+        else if (c0 + nt == n) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
-    logits_valid = true;
+    logits_valid = !embeddings;
 }
 
 // build_moe_ffn's routing (src/llama-graph.cpp, b5187: softmax gating, top-2, weights normalised)
@@ -373,7 +374,9 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
                 launch_mmq32(p, act, ub_rope, stream);
             }
         }
-        if (all) {   // final norm + output head over every token of the batch
+        if (embeddings) {   // embeddings mode: the batch's result_norm rows (xb is whole: the last layer's down is not split)
+            embd_tail(xb, nt, c0);
+        } else if (all) {   // final norm + output head over every token of the batch
             const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);   // the head's own activation format
             launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream);
             GemmParams p;
@@ -392,12 +395,13 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
         }
     }
-    logits_valid = true;
+    logits_valid = !embeddings;
 }
 
 // One short physical batch (tokens uploaded to tokpos_b): embedding, the rope table, the layers on
 // mmqs, then the output -- every token's logits rows (`all`, rows c0.. of logits_all; the last
-// chunk's last row also feeds `logits` and the top-k) or the last token's through the decode head.
+// chunk's last row also feeds `logits` and the top-k) or the last token's through the decode head;
+// in embeddings mode the embedding tail over xb once the pending parts are in.
 void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
     const HParams& hp = m->hp;
     EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
@@ -407,7 +411,7 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
     // (the parts pending are the last layer's FFN down's -- dense models; its control-vector row
     // goes in with them)
     const float* pend_add = pend_k ? cvec_for(hp.n_layer - 1) : nullptr;
-    if (all) {   // final norm + output head on mmqs, its parts summed into the logits rows
+    if (all && !embeddings) {   // final norm + output head on mmqs, its parts summed into the logits rows
         const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);
         launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream, nullptr, pend_k ? ub_spart : nullptr,
                          pend_k ? pend_k : 2, 0, pend_add);
@@ -419,7 +423,8 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
         // the last residual parts into xb (the next chunk, or the output, reads it)
         if (pend_k)
             launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream, 0, pend_add);
-        if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
+        if (embeddings) embd_tail(xb, nt, c0);   // embeddings mode: the rows of the now whole xb, no head
+        else if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
 }
 

@@ -621,6 +621,28 @@ void mi_ctx_clear_lora(mi_ctx* c) {
     try { if (c) c->impl->clear_lora(); } catch (const std::exception& e) { set_last_error(e.what()); }
 }
 
+// ---- embeddings ----
+int32_t mi_model_pooling_type(const mi_model* m) { return m ? m->impl.hp.pooling_type : -1; }
+
+int32_t mi_ctx_set_embeddings(mi_ctx* c, int32_t on, int32_t pooling) {
+    try {
+        if (!c) throw Error("null ctx");
+        c->impl->set_embeddings(on != 0, pooling);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+int32_t mi_ctx_pooling(const mi_ctx* c) { return c ? c->impl->pooling : -1; }
+
+const float* mi_embeddings(mi_ctx* c, int32_t row) {
+    try {
+        if (!c) throw Error("null ctx");
+        return c->impl->embeddings_host(row);
+    }
+    MI_TRY(nullptr)
+}
+
 int32_t mi_prof_enable(mi_ctx* c, int32_t layer) {
     if (!c) return -1;
     if (layer >= c->impl->m->hp.n_layer) layer = c->impl->m->hp.n_layer - 1;

@@ -10,6 +10,7 @@
 //   llama_state_*               /root/reference/inference/code/llama/Session.cpp:291-304
 //   llama_apply_adapter_cvec    /root/reference/inference/code/llama/Instance.cpp:74
 //   llama_set_adapter_lora      /root/reference/inference/code/llama/Instance.cpp:52-61 (lora.cpp)
+//   llama_get_embeddings_ith    /root/reference/inference/code/llama/InstanceEmbedding.cpp:24-32,113-164
 #include "engine.h"
 
 #include <atomic>
@@ -42,6 +43,11 @@ int act_fmt(std::initializer_list<int> types) {
     int f = 0;
     for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
     return f;
+}
+const char* const kEmbdMode = "the context is in embeddings mode: no logits (mi_ctx_set_embeddings)";
+// unspecified pooling: the model's {arch}.pooling_type when it names a type served here, else NONE
+int model_pooling(const HParams& hp) {
+    return hp.pooling_type >= MI_POOLING_NONE && hp.pooling_type < MI_POOLING_RANK ? hp.pooling_type : MI_POOLING_NONE;
 }
 }  // namespace
 int dev_chain_contexts(int device) { return dev_chain(device).nctx.load(); }
@@ -114,6 +120,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
     n_ubatch = nubatch ? std::min(nubatch, n_batch) : n_batch;
     const HParams& hp = m->hp;
     kv_dim = hp.n_head_kv * hp.head_dim;
+    pooling = model_pooling(hp);
     if (device < (int)g_attr_done.size() && !g_attr_done[device]) {
         init_kernel_attributes();
         g_attr_done[device] = 1;
@@ -263,7 +270,7 @@ Ctx::~Ctx() {
 
 void Ctx::invalidate_graphs() {
     for (int m = 0; m < 2; ++m) {
-        for (hipGraphExec_t* g : {&g_full[m], &g_nolog[m], &g_seg[m][0], &g_seg[m][1], &g_seg[m][2]}) {
+        for (hipGraphExec_t* g : {&g_full[m], &g_nolog[m], &g_embd[m], &g_seg[m][0], &g_seg[m][1], &g_seg[m][2]}) {
             if (*g) hipGraphExecDestroy(*g);
             *g = nullptr;
         }
@@ -610,7 +617,7 @@ void Ctx::enqueue_step_sp(bool with_logits) {
     // the residual quantised for its next reader: layer l's Q/K/V, or (l == n_layer) the output head
     auto quant_x_for = [&](int l) {
         if (l == hp.n_layer) {
-            if (with_logits) quant(x, act_out(4, sp_fH, hp.n_embd, m->output_norm));
+            if (with_logits && !embeddings) quant(x, act_out(4, sp_fH, hp.n_embd, m->output_norm));   // (the embedding tail reads x)
         } else if (!sp_nq_in) {
             quant(x, act_out(0, sp[l].fA, hp.n_embd, m->layers[l].attn_norm));
         }
@@ -684,7 +691,10 @@ void Ctx::enqueue_step(bool with_logits) {
             }
         }
     }
-    if (with_logits && seg_on()) enqueue_output(sp_ok ? ACT_QUANT : ACT_PRO, x, next_stamp());
+    if (with_logits && seg_on()) {
+        if (embeddings) enqueue_embd_norm(x, 1, embd_step());   // embeddings mode: result_norm of this token, no head
+        else enqueue_output(sp_ok ? ACT_QUANT : ACT_PRO, x, next_stamp());
+    }
 }
 
 // the output head of one residual row (ACT_QUANT: quantised at sp_act[4] already), then the top-k
@@ -736,7 +746,20 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     if (all && n > (int)n_batch) throw Error("decode: MI_OUT_ALL takes at most n_batch tokens");
     out_rows = 0;
     topk_row = -1;
-    if (all && logits_all_cap < n) {   // every token's logits: [n_batch][n_vocab], allocated once
+    const bool pooled = embeddings && pooling != MI_POOLING_NONE;
+    if (pooled && n > (int)n_batch) throw Error("decode: a pooled embeddings call takes at most n_batch tokens");
+    if (embeddings) {   // the rows of this call (a pooled call yields one row whatever out_mode says)
+        if (!embd) {    // [n_batch] token rows, the pooled row, the step's row: allocated once
+            embd = mem.dev<float>(((size_t)n_batch + 2) * m->hp.n_embd);
+            h_embd = mem.host<float>(m->hp.n_embd);
+        }
+        embd_n = n;
+        embd_all = all && !pooled;
+        embd_rows = 0;
+        embd_valid = false;
+        logits_valid = false;   // no head runs
+    }
+    if (all && !embeddings && logits_all_cap < n) {   // every token's logits: [n_batch][n_vocab], allocated once
         mem.release(logits_all);
         logits_all = mem.dev<float>((size_t)n_batch * m->hp.n_vocab);
         logits_all_cap = (int)n_batch;
@@ -746,17 +769,18 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     const bool fits = n >= 2 && batch_ok && hp_dense() && n_cells + n <= ATTN_SHORT && prof_layer < 0;
     // the MFMA batch path attends over any number of cells with the MFMA attention kernel
     const bool ub = n >= 2 && batch_ok && mmq_ok && prof_layer < 0 && (attn_mfma || n_cells + n <= ATTN_SHORT);
-    if (ub && (!all || out_mmq)) {
+    if (ub && (!all || out_mmq || embeddings)) {
         decode_ubatch(tokens, n, all);
-        if (all) out_rows = n;
+        if (all && !embeddings) out_rows = n;
         return 0;
     }
-    if (fits && !all) {
+    if (fits && (!all || embeddings)) {
         decode_batch(tokens, n);
         return 0;
     }
     for (int i = 0; i < n; ++i) {
-        const bool last = i == n - 1 || all;
+        // embeddings mode: the steps whose row the call's result needs end in the embedding row
+        const bool last = i == n - 1 || (all && !pooled) || (pooled && (pooling == MI_POOLING_MEAN || (pooling == MI_POOLING_CLS && i == 0)));
         const int pos = pos_max + 1, cell = n_cells;
         attn_fused = cell + 1 <= ATTN_SHORT ? 1 : 0;   // this step attends over cell + 1 cells
         const long long slot = tok_slot++ % kTokRing;
@@ -787,16 +811,26 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
         } else if (!use_graphs) {
             enqueue_step(last);
         } else {
-            hipGraphExec_t& g = last ? g_full[attn_fused] : g_nolog[attn_fused];
+            hipGraphExec_t& g = !last ? g_nolog[attn_fused] : embeddings ? g_embd[attn_fused] : g_full[attn_fused];
             if (!g) g = build_graph(last, -1);
             MI_HIP(hipGraphLaunch(g, stream));
         }
-        if (all)   // this token's logits -> row i
+        if (embeddings) {   // this token's embedding -> row i
+            if (last && (embd_all || pooled))
+                MI_HIP(hipMemcpyAsync(embd + (size_t)i * m->hp.n_embd, embd_step(), (size_t)m->hp.n_embd * sizeof(float),
+                                      hipMemcpyDeviceToDevice, stream));
+        } else if (all)   // this token's logits -> row i
             MI_HIP(hipMemcpyAsync(logits_all + (size_t)i * m->hp.n_vocab, logits, (size_t)m->hp.n_vocab * sizeof(float),
                                   hipMemcpyDeviceToDevice, stream));
         h_cell_pos[cell] = pos;
         n_cells++;
         pos_max = pos;
+    }
+    if (embeddings) {
+        if (pooled) embd_pool_rows(0, n);
+        else if (embd_all) embd_rows = n;
+        embd_valid = true;
+        return 0;
     }
     if (all) out_rows = n;
     logits_valid = true;
@@ -811,6 +845,7 @@ void Ctx::sync() {
     if (h_attn_xerr && *h_attn_xerr) {   // an attention exchange gave up: the step's logits are invalid
         *h_attn_xerr = 0;
         logits_valid = false;
+        embd_valid = false;
         // the cells decoded since the last good sync hold KV rows built from a wrong attention
         // output: drop them, and use the two-launch split kernels from now on
         if (was_unsynced) {
@@ -831,7 +866,86 @@ const float* Ctx::out_row(int row) const {
     return logits_all + (size_t)row * m->hp.n_vocab;
 }
 
+// ---- embeddings ----
+
+void Ctx::set_embeddings(bool on, int pooling_type) {
+    if (pooling_type < MI_POOLING_UNSPECIFIED || pooling_type > MI_POOLING_RANK)
+        throw Error("set_embeddings: pooling type out of range (-1 .. 3)");
+    if (pooling_type == MI_POOLING_RANK)
+        throw Error("set_embeddings: RANK pooling needs a classification head, which this engine does not load");
+    if (pooling_type == MI_POOLING_UNSPECIFIED) pooling_type = model_pooling(m->hp);
+    MI_HIP(hipSetDevice(device));
+    sync();                 // steps in flight still write the old mode's outputs
+    invalidate_graphs();    // the step graphs end in the other tail
+    embeddings = on;
+    pooling = pooling_type;
+    embd_valid = false;
+    embd_rows = 0;
+    if (on) logits_valid = false;
+}
+
+void Ctx::enqueue_embd_norm(const float* xrows, int nt, float* out) {
+    const HParams& hp = m->hp;
+    if (hp.arch == ARCH_GPT2 && !m->output_norm_b) throw Error("embeddings: gpt2 without output_norm.bias");
+    launch_embd_norm(EmbdNorm{xrows, hp.n_embd, nt, hp.n_embd, m->output_norm, hp.arch == ARCH_GPT2 ? m->output_norm_b : nullptr,
+                              hp.eps, out, hp.n_embd},
+                     stream);
+}
+
+void Ctx::embd_pool_rows(int r0, int nt) {
+    const int ne = m->hp.n_embd, n = embd_n;
+    EmbdPool p{embd + (size_t)r0 * ne, ne, 0, ne, 1.0f / (float)n, r0 > 0 ? 1 : 0, embd_pooled()};
+    if (pooling == MI_POOLING_MEAN) {
+        p.nt = nt;
+    } else if (pooling == MI_POOLING_CLS) {
+        if (r0 > 0) return;
+    } else {   // LAST
+        if (r0 + nt < n) return;
+        p.rows = embd + (size_t)(n - 1) * ne;
+    }
+    launch_embd_pool(p, stream);
+}
+
+void Ctx::embd_tail(const float* xrows, int nt, int c0) {
+    const int ne = m->hp.n_embd, n = embd_n;
+    const bool last = c0 + nt == n;
+    if (pooling == MI_POOLING_NONE) {
+        if (embd_all) enqueue_embd_norm(xrows, nt, embd + (size_t)c0 * ne);
+        else if (last) enqueue_embd_norm(xrows + (size_t)(nt - 1) * ne, 1, embd_step());
+        if (last && embd_all) embd_rows = n;
+    } else {
+        // the rows the pooled row reads: all of them (MEAN), the call's first (CLS) or last (LAST)
+        if (pooling == MI_POOLING_MEAN) enqueue_embd_norm(xrows, nt, embd + (size_t)c0 * ne);
+        else if (pooling == MI_POOLING_CLS && c0 == 0) enqueue_embd_norm(xrows, 1, embd);
+        else if (pooling == MI_POOLING_LAST && last) enqueue_embd_norm(xrows + (size_t)(nt - 1) * ne, 1, embd + (size_t)(n - 1) * ne);
+        embd_pool_rows(c0, nt);
+    }
+    if (last) embd_valid = true;
+}
+
+const float* Ctx::embeddings_host(int row) {
+    if (!embeddings) throw Error("embeddings: the context is not in embeddings mode (mi_ctx_set_embeddings)");
+    if (!embd_valid) throw Error("no embeddings: decode since the mode was set first");
+    const int ne = m->hp.n_embd;
+    const float* src;
+    if (pooling != MI_POOLING_NONE) {
+        if (row != 0 && row != -1) throw Error("embeddings: a pooled context has one row (0 or -1)");
+        src = embd_pooled();
+    } else if (embd_rows > 0) {
+        if (row < -1 || row >= embd_rows) throw Error("embeddings: output row out of range");
+        src = embd + (size_t)(row < 0 ? embd_rows - 1 : row) * ne;
+    } else {
+        if (row != 0 && row != -1) throw Error("embeddings: output row out of range");
+        src = embd_step();
+    }
+    MI_HIP(hipSetDevice(device));
+    MI_HIP(hipMemcpyAsync(h_embd, src, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, stream));
+    sync();
+    return h_embd;
+}
+
 int Ctx::topk(int row, int k, int32_t* ids, float* vals) {
+    if (embeddings) throw Error(kEmbdMode);
     if (!logits_valid) throw Error("no logits: decode a token first");
     if (k < 0 || k > TOPK_MAX) throw Error("topk: k must be in [0, 64]");
     if (out_rows > 0 && row == out_rows - 1) row = -1;   // the last row's top-k is already computed
@@ -850,6 +964,7 @@ int Ctx::topk(int row, int k, int32_t* ids, float* vals) {
 }
 
 int Ctx::gather(int row, const int32_t* ids, int n, float* out) {
+    if (embeddings) throw Error(kEmbdMode);
     if (!logits_valid) throw Error("no logits: decode a token first");
     const float* src = out_row(row);
     if (n < 0 || n > 4096) throw Error("gather: n must be in [0, 4096]");
@@ -868,6 +983,7 @@ int Ctx::gather(int row, const int32_t* ids, int n, float* out) {
 // Logits of rows row0..row0+nrows-1 at k ids each (ids [nrows][k]): the batched form of gather
 // for a verification pass -- one copy in, one kernel, one copy out.
 int Ctx::gather_rows(int row0, int nrows, const int32_t* ids, int k, float* out) {
+    if (embeddings) throw Error(kEmbdMode);
     if (!logits_valid) throw Error("no logits: decode a token first");
     if (nrows < 0 || k < 0) throw Error("gather_rows: negative count");
     const size_t n = (size_t)nrows * k;
@@ -897,6 +1013,7 @@ int Ctx::gather_rows(int row0, int nrows, const int32_t* ids, int k, float* out)
 }
 
 const float* Ctx::logits_host(int row) {
+    if (embeddings) throw Error(kEmbdMode);
     if (!logits_valid) throw Error("no logits: decode a token first");
     const float* src = out_row(row);
     MI_HIP(hipSetDevice(device));

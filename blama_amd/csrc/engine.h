@@ -59,6 +59,7 @@ struct HParams {
     int n_rot = 0, head_dim = 0, n_expert = 0, n_expert_used = 0;
     float eps = 1e-5f, rope_base = 10000.0f, freq_scale = 1.0f;
     int arch = 0;                       // ARCH_LLAMA (llm_build_llama) or ARCH_GPT2 (llm_build_gpt2)
+    int pooling_type = -1;              // {arch}.pooling_type (llama_pooling_type), -1: the GGUF has none
 };
 enum { ARCH_LLAMA = 0, ARCH_GPT2 = 1 };
 
@@ -237,6 +238,28 @@ struct Ctx {
     int logits_all_cap = 0;
     int out_rows = 0;                   // rows of logits_all valid (0: the last decode was MI_OUT_LAST)
     int topk_row = -1;                  // output row the mapped top-k buffers hold (-1: the last token)
+    // Embeddings mode (llama_context_params.embeddings + pooling_type, b5187): every pass ends in
+    // the embedding tail -- the final norm to f32 rows (embd.hip), pooled over the tokens of the
+    // decode call -- in place of the output head; no logits then.  A property of the context, not
+    // of its state.  embd: [n_batch] token rows, the pooled row, the decode step's row (the
+    // captured step graph writes there); allocated by the first embeddings decode.
+    bool embeddings = false;
+    int pooling = MI_POOLING_NONE;      // resolved (never unspecified)
+    float* embd = nullptr;
+    float* h_embd = nullptr;            // pinned [n_embd]: the row mi_embeddings returns
+    bool embd_valid = false;            // a decode has written embd since the mode was set
+    int embd_rows = 0;                  // token rows valid (pooling NONE after MI_OUT_ALL), else 0
+    int embd_n = 0;                     // the decode call being enqueued: its tokens, and whether
+    bool embd_all = false;              // every token's row is wanted (MI_OUT_ALL, pooling NONE)
+    float* embd_pooled() const { return embd + (size_t)n_batch * m->hp.n_embd; }
+    float* embd_step() const { return embd + ((size_t)n_batch + 1) * m->hp.n_embd; }
+    void set_embeddings(bool on, int pooling_type);   // synchronises, drops the graphs
+    void enqueue_embd_norm(const float* xrows, int nt, float* out);
+    // the tail of one physical batch: residual rows xrows [nt][n_embd] are tokens c0.. of the call
+    void embd_tail(const float* xrows, int nt, int c0);
+    // token rows r0 .. r0 + nt - 1 of embd into the pooled row (MEAN: accumulated; CLS: row 0; LAST: row n - 1)
+    void embd_pool_rows(int r0, int nt);
+    const float* embeddings_host(int row);
     // control vector (llama_adapter_cvec, b5187): row l is layer l's direction, added to the
     // residual stream after the layer's FFN residual add (build_cvec) in every path.  A property
     // of the context, not of its state (mi_state_get / mi_state_set leave it alone).
@@ -329,6 +352,7 @@ struct Ctx {
     // [attention mode]: 1 = the context fits the fused short-attention launch (ATTN_SHORT
     // cells), 0 = split attention; the host knows the cell count of every step.
     hipGraphExec_t g_full[2] = {nullptr, nullptr}, g_nolog[2] = {nullptr, nullptr};
+    hipGraphExec_t g_embd[2] = {nullptr, nullptr};   // embeddings mode: the step ending in the embedding row
     hipGraphExec_t g_seg[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     int attn_fused = 0;                 // mode of the step being enqueued
     bool attn_long_off = false;         // an exchange of attn_long_kernel timed out: split kernels only

@@ -468,4 +468,28 @@ struct LoraExpand {
 };
 void launch_lora_expand(const LoraExpand& p, hipStream_t s);
 
+// ---- embeddings (embd.hip): result_norm rows and build_pooling, b5187 ----
+// The final norm of nt residual rows to f32 rows, a workgroup per row: rms_norm(x, eps) * w, or
+// (b set: GPT-2) layer_norm(x, eps) * w + b, in the arithmetic of the quantising kernels.
+struct EmbdNorm {
+    const float* x;        // [nt][x_stride]
+    int x_stride, nt, K;
+    const float* w;        // [K]
+    const float* b;        // [K], or null
+    float eps;
+    float* out;            // [nt][out_stride]
+    int out_stride;
+};
+void launch_embd_norm(const EmbdNorm& p, hipStream_t s);
+// nt > 0 (MEAN): out[j] = (accumulate ? out[j] : 0) + rows[0][j] * inv_n + rows[1][j] * inv_n + ...,
+// each term rounded to f32, added in ascending token order; nt == 0 (CLS, LAST): out = rows[0].
+struct EmbdPool {
+    const float* rows;     // [nt][stride]
+    int stride, nt, K;
+    float inv_n;           // 1.0f / (tokens of the whole call)
+    int accumulate;
+    float* out;            // [K]
+};
+void launch_embd_pool(const EmbdPool& p, hipStream_t s);
+
 }  // namespace mi

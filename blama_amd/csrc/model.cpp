@@ -256,6 +256,8 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     hp.freq_scale = (rope_type == "linear" && fs > 0.0) ? (float)(1.0 / fs) : 1.0f;
     hp.n_expert = (int)gguf.get_int(key("expert_count"), 0);
     hp.n_expert_used = (int)gguf.get_int(key("expert_used_count"), 0);
+    // llama_pooling_type of the model ({arch}.pooling_type, u32), read for every architecture; absent: unspecified
+    hp.pooling_type = (int)gguf.get_int(key("pooling_type"), -1);
     if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0) throw Error("GGUF: missing llama hparams");
     hp.head_dim = hp.n_embd / hp.n_head;
     hp.n_rot = hp.arch == ARCH_GPT2 ? 0 : (int)gguf.get_int(key("rope.dimension_count"), hp.head_dim);

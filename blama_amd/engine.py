@@ -32,6 +32,9 @@ class ModelParams(C.Structure):
                 ("vocab_only", C.c_int32), ("no_upload", C.c_int32)]
 
 
+# llama_pooling_type (mi_engine.h MI_POOLING_*)
+POOLING_UNSPECIFIED, POOLING_NONE, POOLING_MEAN, POOLING_CLS, POOLING_LAST, POOLING_RANK = -1, 0, 1, 2, 3, 4
+
 _P = C.c_void_p
 _SIGS = {
     "mi_last_error": (C.c_char_p, []),
@@ -92,6 +95,10 @@ _SIGS = {
     "mi_ctx_set_lora": (C.c_int32, [_P, _P, C.c_float]),
     "mi_ctx_rm_lora": (C.c_int32, [_P, _P]),
     "mi_ctx_clear_lora": (None, [_P]),
+    "mi_model_pooling_type": (C.c_int32, [_P]),
+    "mi_ctx_set_embeddings": (C.c_int32, [_P, C.c_int32, C.c_int32]),
+    "mi_ctx_pooling": (C.c_int32, [_P]),
+    "mi_embeddings": (C.POINTER(C.c_float), [_P, C.c_int32]),
     "mi_prof_enable": (C.c_int32, [_P, C.c_int32]),
     "mi_prof_read": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_int32]),
     "mi_prof_ffn_bytes": (C.c_int64, [_P]),
@@ -221,6 +228,11 @@ class Model:
 
     def is_eog(self, tok: int) -> bool:
         return lib().mi_model_token_is_eog(self.h, tok) == 1
+
+    @property
+    def pooling_type(self) -> int:
+        """The GGUF's {arch}.pooling_type (llama_pooling_type), or -1 when it has none."""
+        return int(lib().mi_model_pooling_type(self.h))
 
 
 class Lora:
@@ -372,6 +384,24 @@ class Context:
 
     def clear_lora(self):
         lib().mi_ctx_clear_lora(self.h)
+
+    def set_embeddings(self, on: bool = True, pooling: int = POOLING_UNSPECIFIED):
+        """mi_ctx_set_embeddings: from the next decode every pass ends in the embedding rows (no
+        logits); pooling -1 resolves to the model's key, else NONE."""
+        _check(lib().mi_ctx_set_embeddings(self.h, 1 if on else 0, pooling), "set_embeddings")
+
+    @property
+    def pooling(self) -> int:
+        """The resolved pooling type (llama_pooling_type(ctx))."""
+        return int(lib().mi_ctx_pooling(self.h))
+
+    def embeddings(self, row: int = -1) -> np.ndarray:
+        """mi_embeddings: n_embd floats -- pooling NONE: the row of an output token (as logits());
+        pooled: the sequence embedding of the last decode call (row 0 or -1)."""
+        p = lib().mi_embeddings(self.h, row)
+        if not p:
+            raise EngineError(f"embeddings: {last_error()}")
+        return np.ctypeslib.as_array(p, shape=(self.model.n_embd,)).copy()
 
     def prof_enable(self, stride: int):
         lib().mi_prof_enable(self.h, stride)

@@ -883,6 +883,66 @@ Instance::~Instance() {
     if (m_ctx) mi_ctx_free(m_ctx);
 }
 
+// ---- InstanceEmbedding (InstanceEmbedding.cpp) ----
+InstanceEmbedding::InstanceEmbedding(Model& model, InitParams params) : m_model(model), m_params(params) {
+    m_ctx = mi_ctx_create(model.mmodel(), params.ctxSize, params.batchSize, params.ubatchSize);
+    if (!m_ctx) BL_THROW("Failed to create llama context");
+    // llamaParams.embeddings = true, pooling_type left at LLAMA_POOLING_TYPE_UNSPECIFIED (InstanceEmbedding.cpp:24-32)
+    if (mi_ctx_set_embeddings(m_ctx, 1, MI_POOLING_UNSPECIFIED) != 0) {
+        mi_ctx_free(m_ctx);
+        m_ctx = nullptr;
+        BL_THROW("Failed to create llama context");
+    }
+}
+
+InstanceEmbedding::~InstanceEmbedding() {
+    if (m_ctx) mi_ctx_free(m_ctx);
+}
+
+void InstanceEmbedding::normalize(std::span<const float> in, std::span<float> out, int32_t normalization) {
+    const size_t n = in.size();
+    if (out.size() < n) BL_THROW("InstanceEmbedding::normalize: output shorter than input");
+    double sum = 0.0;
+    switch (normalization) {
+    case -1:   // no normalisation
+        sum = 1.0;
+        break;
+    case 0:    // max absolute, scaled to an int16 range
+        for (size_t i = 0; i < n; ++i) sum = std::max(sum, (double)std::abs(in[i]));
+        sum /= 32760.0;
+        break;
+    case 2:    // Euclidean
+        for (size_t i = 0; i < n; ++i) sum += in[i] * in[i];   // (the f32 product, as the reference forms it)
+        sum = std::sqrt(sum);
+        break;
+    default:   // p-norm
+        for (size_t i = 0; i < n; ++i) sum += std::pow((double)std::abs(in[i]), (double)normalization);
+        sum = std::pow(sum, 1.0 / (double)normalization);
+        break;
+    }
+    const float norm = sum > 0.0 ? (float)(1.0 / sum) : 0.0f;
+    for (size_t i = 0; i < n; ++i) out[i] = in[i] * norm;
+}
+
+std::vector<float> InstanceEmbedding::getEmbeddingVector(std::span<const Token> prompt, int32_t normalization) const {
+    if (prompt.empty()) BL_THROW("InstanceEmbedding: empty prompt");
+    if (prompt.size() > mi_n_batch(m_ctx)) BL_THROW("InstanceEmbedding: prompt longer than the batch size");
+    if (prompt.size() > mi_n_ctx(m_ctx)) BL_THROW("InstanceEmbedding: prompt longer than the context");
+    mi_kv_clear(m_ctx);
+    // only the last token is an output (batchAddSeq, InstanceEmbedding.cpp:95-110)
+    if (mi_decode(m_ctx, prompt.data(), (int32_t)prompt.size(), MI_OUT_LAST) != 0)
+        BL_THROW("Failed to decode! " << last_error());
+    // llama_get_embeddings_ith of that token (pooling NONE) or llama_get_embeddings_seq (pooled)
+    const float* embd = mi_embeddings(m_ctx, -1);
+    if (!embd) BL_THROW("Failed to get embeddings: " << last_error());
+    const size_t n = embeddingDim();
+    std::vector<float> out(n, 0.0f);
+    normalize(std::span<const float>(embd, n), out, normalization);
+    return out;
+}
+
+uint32_t InstanceEmbedding::embeddingDim() const noexcept { return (uint32_t)mi_model_n_embd(m_model.mmodel()); }
+
 void Instance::addControlVector(const ControlVector& ctrlVector) {
     const int err = mi_ctx_apply_cvec(m_ctx, ctrlVector.data.data(), ctrlVector.data.size(), ctrlVector.nEmbd,
                                       ctrlVector.controlVectorLayerStart, ctrlVector.controlVectorLayerEnd);

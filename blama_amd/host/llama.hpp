@@ -14,6 +14,8 @@
 //   Vocab{tokenize, isEog, nTokens, tokenToString}       Vocab.hpp:16-34
 //   Instance{InitParams, warmup, startSession, stopSession,
 //            addControlVector, addLora, clearLoraState}   Instance.hpp:19-51
+//   InstanceEmbedding{InitParams, getEmbeddingVector,
+//                     embeddingDim, model}                InstanceEmbedding.hpp:22-49
 //   LoraAdapter                                           LoraAdapter.hpp, LoraAdapter.cpp:12-19
 //   ControlVector{LoadInfo}                               ControlVector.hpp:17-33
 //   Session{InitParams, setInitialPrompt, complete, completeStream, fillCtx,
@@ -361,6 +363,43 @@ private:
     Model& m_model;
     mi_ctx* m_ctx = nullptr;
     std::optional<Session> m_session;
+};
+
+// The embeddings instance (InstanceEmbedding.hpp:22-49, InstanceEmbedding.cpp): a context of its own
+// in embeddings mode (llama_context_params.embeddings = true) with the pooling type left
+// unspecified, i.e. the model's {arch}.pooling_type or NONE.  Decoder models only; encoder models
+// (BERT) are not served.
+class InstanceEmbedding {
+public:
+    struct InitParams {
+        uint32_t ctxSize = 0;       // 0 = the model's training context
+        uint32_t batchSize = 2048;  // may be silently truncated to ctxSize
+        uint32_t ubatchSize = 512;
+        bool flashAttn = false;
+    };
+    // throws "Failed to create llama context"
+    explicit InstanceEmbedding(Model& model, InitParams params);
+    ~InstanceEmbedding();
+    InstanceEmbedding(const InstanceEmbedding&) = delete;
+    InstanceEmbedding& operator=(const InstanceEmbedding&) = delete;
+
+    // InstanceEmbedding.cpp:113-164: clears the KV cache, decodes the prompt in one call and returns
+    // its embedding -- pooling NONE: the last token's row; pooled: the sequence row -- normalised
+    // (-1 none, 0 max-abs / 32760, 1 taxicab, 2 Euclidean [default], other p: p-norm).  Throws on an
+    // empty prompt or one longer than the batch or the context, where the reference only logs.
+    std::vector<float> getEmbeddingVector(std::span<const Token> prompt, int32_t normalization = 2) const;
+    uint32_t embeddingDim() const noexcept;
+    const Model& model() const noexcept { return m_model; }
+    mi_ctx* mctx() const noexcept { return m_ctx; }
+
+    // normalizeEmbedding (InstanceEmbedding.cpp:59-93): sums in double, norm = sum > 0 ?
+    // float(1 / sum) : 0, out[i] = in[i] * norm.  out.size() >= in.size(); in == out is fine.
+    static void normalize(std::span<const float> in, std::span<float> out, int32_t normalization);
+
+private:
+    Model& m_model;
+    InitParams m_params;
+    mi_ctx* m_ctx = nullptr;
 };
 
 struct ComparisonMetrics {

@@ -48,6 +48,7 @@ class LlamaConfig:
     rope_scaling_type: str = "linear"  # the rope.scaling.type written beside rope.scaling.factor
     rope_freqs: bool = False          # an F32 rope_freqs.weight of n_rot/2 frequency factors (Llama-3.1)
     init: str = ""                    # _init_params overrides of this config, "key=value,..." as BLAMA_SYNTH_INIT
+    pooling_type: int = -1            # >= 0: written as {arch}.pooling_type (llama_pooling_type)
 
     @property
     def head_dim(self):
@@ -538,6 +539,8 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     if cfg.n_expert:
         w.add_u32(f"{arch}.expert_count", cfg.n_expert)
         w.add_u32(f"{arch}.expert_used_count", cfg.n_expert_used)
+    if cfg.pooling_type >= 0:
+        w.add_u32(f"{arch}.pooling_type", cfg.pooling_type)
     if vocab is None:
         w.add_str("tokenizer.ggml.model", "llama")
         toks = vocab_tokens(cfg.n_vocab)

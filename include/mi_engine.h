@@ -189,6 +189,43 @@ int32_t mi_ctx_set_lora(mi_ctx* ctx, mi_lora* lora, float scale);
 int32_t mi_ctx_rm_lora(mi_ctx* ctx, mi_lora* lora);
 void mi_ctx_clear_lora(mi_ctx* ctx);
 
+/* Embeddings (InstanceEmbedding.cpp:24-32: llama_context_params.embeddings = true, pooling_type;
+ * InstanceEmbedding.cpp:113-164: llama_decode, llama_pooling_type, llama_get_embeddings_ith /
+ * llama_get_embeddings_seq).  The embedding of a token is result_norm: the residual stream after the
+ * last layer (its control-vector add and any LoRA included) through the final norm, in f32 --
+ * rms_norm(x) * output_norm (LLaMA, MoE), layer_norm(x) * output_norm + bias (GPT-2).  Pooling
+ * (llama_pooling_type) reduces the rows of the tokens of ONE mi_decode call (n <= n_batch) to one
+ * row: MEAN = sum_t row_t * (1.0f / n) in f32 in token order, CLS = the first token's row, LAST =
+ * the last token's; NONE keeps a row per output token.  RANK needs a classification head the engine
+ * does not load and is refused.  Encoder models (BERT) are not served. */
+#define MI_POOLING_UNSPECIFIED (-1)
+#define MI_POOLING_NONE 0
+#define MI_POOLING_MEAN 1
+#define MI_POOLING_CLS 2
+#define MI_POOLING_LAST 3
+#define MI_POOLING_RANK 4
+/* The model's {arch}.pooling_type key (read for every architecture), or -1 when the GGUF has none
+ * or the model is NULL. */
+int32_t mi_model_pooling_type(const mi_model* model);
+/* llama_set_embeddings + pooling_type (InstanceEmbedding.cpp:24-32).  on != 0: every mi_decode from
+ * the next one ends in the embedding rows and runs no output head -- mi_logits then returns NULL and
+ * mi_topk / mi_gather / mi_gather_rows < 0, mi_last_error() saying that the context is in
+ * embeddings mode; the KV cache is written as usual.  pooling MI_POOLING_UNSPECIFIED resolves to the
+ * model's key, else NONE.  With a pooled type a call yields one row whatever its out_mode and takes
+ * at most n_batch tokens.  on == 0: back to logits (pooling is still validated and kept).
+ * Synchronises; leaves the KV cache alone; embeddings are not part of mi_state_get / mi_state_set.
+ * 0 ok; < 0: null context, pooling outside -1..3, RANK. */
+int32_t mi_ctx_set_embeddings(mi_ctx* ctx, int32_t on, int32_t pooling);
+/* llama_pooling_type(ctx) (InstanceEmbedding.cpp:114): the resolved type; -1 for a null context. */
+int32_t mi_ctx_pooling(const mi_ctx* ctx);
+/* llama_get_embeddings_ith (pooling NONE; InstanceEmbedding.cpp:149) / llama_get_embeddings_seq
+ * (pooled; InstanceEmbedding.cpp:154): n_embd floats, context-owned, valid until the next decode or
+ * mi_embeddings call.  Synchronises.  NONE: rows as for mi_logits (-1 the last token's; 0..n-1
+ * after MI_OUT_ALL, row 0 only after MI_OUT_LAST); pooled: row 0 or -1 is the sequence embedding.
+ * NULL with a message when the mode is off, no decode has happened since it was set, or the row is
+ * out of range. */
+const float* mi_embeddings(mi_ctx* ctx, int32_t row);
+
 /* ---- measurement: HIP events on the context's stream bracketing the FFN
  * gate/up GEMV launch of `layer` in every output-producing decode step (the
  * step's graph is split in three around it); layer < 0 disables.
