@@ -730,6 +730,50 @@ void ensure_attrs(int device) {
         done[device] = 1;
     }
 }
+
+// The E experts of a MoE *_exps tensor ([E][rows] rows of GGUF blocks) as one QMat, laid out as
+// Model::load does: the experts stacked in the planes, expert_stride[] bytes apart.
+QMat upload_experts(int type, const void* raw, int n_expert, int rows, int K,
+                    std::vector<std::unique_ptr<DevBuf>>& keep) {
+    QMat m = upload_qmat(type, raw, n_expert * rows, K, keep);
+    m.rows = rows;
+    m.n_exp = n_expert;
+    for (int k = 0; k < plane_count(type); ++k) m.expert_stride[k] = (long long)rows * m.nb * plane_sb_bytes(type, k);
+    return m;
+}
+
+// Expert e's planes (model.cpp expert_view, before any MFMA-order copy exists).
+QMat expert_planes(const QMat& q, int e) {
+    QMat v = q;
+    for (int k = 0; k < 4; ++k)
+        if (v.p[k]) v.p[k] += e * q.expert_stride[k];
+    return v;
+}
+
+// One MFMA-order copy per expert (a pair: gate and up in one), as Model::ensure_mmq_copies lays
+// them out: expert e's copy at A.sw + e * A.sw_expert_stride.
+void swizzle_experts(QMat& A, const QMat* B, std::vector<std::unique_ptr<DevBuf>>& keep) {
+    const size_t one = mmq32_copy_bytes(A, B != nullptr);
+    keep.push_back(std::make_unique<DevBuf>(one * A.n_exp));
+    uint8_t* sw = keep.back()->as<uint8_t>();
+    for (int e = 0; e < A.n_exp; ++e) {
+        const QMat a = expert_planes(A, e), b = B ? expert_planes(*B, e) : QMat{};
+        launch_mmq32_swizzle(a, B ? &b : nullptr, sw + one * e, nullptr);
+    }
+    MI_HIP(hipDeviceSynchronize());
+    A.sw = sw;
+    A.sw_expert_stride = (long long)one;
+}
+
+// The router's picks of ntok tokens: two distinct experts of [0, n_expert) each (an expert then
+// holds at most ntok rows, the bound the grouped launches size their grids with).
+void check_picks(const int32_t* sel, int ntok, int n_expert) {
+    for (int t = 0; t < ntok; ++t) {
+        const int a = sel[2 * t], b = sel[2 * t + 1];
+        if (a < 0 || a >= n_expert || b < 0 || b >= n_expert) throw Error("op_moe: expert out of range");
+        if (a == b) throw Error("op_moe: a token's two picks must differ");
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -1035,6 +1079,221 @@ int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv,
         launch_attn_mfma(a, ntok, dout.as<float>(), nullptr);
         MI_HIP(hipDeviceSynchronize());
         MI_HIP(hipMemcpy(out, dout.p, (size_t)ntok * d * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// ---- the MoE kernels, op by op ----
+int32_t mi_op_router(int32_t device, int32_t n_embd, int32_t n_expert, int32_t ntok, const float* x, int32_t x_stride,
+                     const float* norm_w, float eps, const float* w, const float* part, int32_t* sel_out,
+                     float* selw_out, float* x_out) {
+    try {
+        if (!x || !norm_w || !w || !sel_out || !selw_out) throw Error("op_router: null argument");
+        if (ntok < 1 || ntok > UB_MAX) throw Error("op_router: 1..512 token rows");
+        if (n_embd < 1 || n_expert < 2) throw Error("op_router: bad shape");
+        if (x_stride < n_embd || x_stride % 4) throw Error("op_router: x_stride must cover n_embd, in whole float4s");
+        MI_HIP(hipSetDevice(device));
+        const size_t xn = (size_t)ntok * x_stride, pn = (size_t)2 * ntok * n_embd;
+        DevBuf dx(xn * sizeof(float)), dn((size_t)n_embd * sizeof(float)), dw((size_t)n_expert * n_embd * sizeof(float));
+        DevBuf dp(pn * sizeof(float)), dsel((size_t)ntok * 2 * sizeof(int)), dselw((size_t)ntok * 2 * sizeof(float));
+        MI_HIP(hipMemcpy(dx.p, x, xn * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dn.p, norm_w, (size_t)n_embd * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dw.p, w, (size_t)n_expert * n_embd * sizeof(float), hipMemcpyHostToDevice));
+        if (part) MI_HIP(hipMemcpy(dp.p, part, pn * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemset(dsel.p, 0x80, (size_t)ntok * 2 * sizeof(int)));
+        MI_HIP(hipMemset(dselw.p, 0xFF, (size_t)ntok * 2 * sizeof(float)));
+        RouterParams rp{dx.as<float>(), dn.as<float>(), eps, dw.as<float>(), n_embd, n_expert, 2, dsel.as<int>(),
+                        dselw.as<float>(), x_stride, part ? dp.as<float>() : nullptr, ntok};
+        launch_router_multi(rp, ntok, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        MI_HIP(hipMemcpy(sel_out, dsel.p, (size_t)ntok * 2 * sizeof(int), hipMemcpyDeviceToHost));
+        MI_HIP(hipMemcpy(selw_out, dselw.p, (size_t)ntok * 2 * sizeof(float), hipMemcpyDeviceToHost));
+        if (x_out) MI_HIP(hipMemcpy(x_out, dx.p, xn * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+int32_t mi_op_moe_group(int32_t device, const int32_t* sel, int32_t n, int32_t U, int32_t E, int32_t rows_cap,
+                        int32_t* grp_out, int32_t* rows_out, int32_t* rowsel_out, int32_t* pos_out) {
+    try {
+        if (!sel || !grp_out || !rows_out || !rowsel_out || !pos_out) throw Error("op_moe_group: null argument");
+        if (n < 1 || n > 4 * UB_MAX || U < 1 || n % U) throw Error("op_moe_group: 1..2048 picks, whole tokens");
+        if (rows_cap < 1 || rows_cap > 8 * UB_MAX) throw Error("op_moe_group: bad row capacity");
+        MI_HIP(hipSetDevice(device));
+        const int ng = 2 * std::max(E, 0) + 1;
+        DevBuf dsel((size_t)n * sizeof(int)), dgrp((size_t)ng * sizeof(int)), drows((size_t)rows_cap * sizeof(int));
+        DevBuf drs((size_t)rows_cap * sizeof(int)), dpos((size_t)n * sizeof(int));
+        MI_HIP(hipMemcpy(dsel.p, sel, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        // a sentinel (0x80808080) in everything the kernel should write
+        MI_HIP(hipMemset(dgrp.p, 0x80, (size_t)ng * sizeof(int)));
+        MI_HIP(hipMemset(drows.p, 0x80, (size_t)rows_cap * sizeof(int)));
+        MI_HIP(hipMemset(drs.p, 0x80, (size_t)rows_cap * sizeof(int)));
+        MI_HIP(hipMemset(dpos.p, 0x80, (size_t)n * sizeof(int)));
+        launch_moe_group(dsel.as<int>(), n, U, E, dgrp.as<int>(), drows.as<int>(), drs.as<int>(), dpos.as<int>(), rows_cap,
+                         nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        MI_HIP(hipMemcpy(grp_out, dgrp.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost));
+        MI_HIP(hipMemcpy(rows_out, drows.p, (size_t)rows_cap * sizeof(int), hipMemcpyDeviceToHost));
+        MI_HIP(hipMemcpy(rowsel_out, drs.p, (size_t)rows_cap * sizeof(int), hipMemcpyDeviceToHost));
+        MI_HIP(hipMemcpy(pos_out, dpos.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* raw, const void* raw_up, int32_t n_expert,
+                       int32_t rows, int32_t K, int32_t ntok, const float* x, int32_t per_pick, const int32_t* sel,
+                       float* y) {
+    try {
+        if (!raw || !x || !sel || !y) throw Error("op_moe_gemm: null argument");
+        if (mode != 0 && mode != 1) throw Error("op_moe_gemm: mode 0 (tiled) or 1 (short)");
+        if (!mmq32_supported(type)) throw Error("op_moe_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
+        if (mode == 1 && !mmqs_grouped_supported(type)) throw Error("op_moe_gemm: the short form takes Q4_K / Q5_K / Q6_K experts");
+        if (ntok < 1 || ntok > (mode == 1 ? MMQS_MAX : UB_MAX)) throw Error("op_moe_gemm: 1..512 tokens (short form: 1..64)");
+        if (n_expert < 2 || n_expert > MOE_GROUP_MAXE) throw Error("op_moe_gemm: 2..16 experts");
+        if (rows < 1 || K < 256 || K % 256) throw Error("op_moe_gemm: bad shape");
+        check_picks(sel, ntok, n_expert);
+        MI_HIP(hipSetDevice(device));
+        ensure_attrs(device);
+        const bool pair = raw_up != nullptr;
+        const int n = 2 * ntok, cap = moe_rows_cap(n, n_expert);
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        QMat A = upload_experts(type, raw, n_expert, rows, K, keep);
+        QMat B = A;
+        if (pair) B = upload_experts(type, raw_up, n_expert, rows, K, keep);
+        swizzle_experts(A, pair ? &B : nullptr, keep);
+        // the picks grouped by expert
+        DevBuf dsel((size_t)n * sizeof(int)), dgrp((size_t)(2 * n_expert + 1) * sizeof(int)), drows((size_t)cap * sizeof(int));
+        DevBuf drs((size_t)cap * sizeof(int)), dpos((size_t)n * sizeof(int));
+        MI_HIP(hipMemcpy(dsel.p, sel, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        launch_moe_group(dsel.as<int>(), n, 2, n_expert, dgrp.as<int>(), drows.as<int>(), drs.as<int>(), dpos.as<int>(), cap,
+                         nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        std::vector<int> pos(n);
+        MI_HIP(hipMemcpy(pos.data(), dpos.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i)
+            if (pos[i] < 0 || pos[i] >= cap) throw Error("op_moe_gemm: the grouping left a pick without a row");
+        // the MoE rows quantised: the tokens' rows through moe_rows (gate/up), or one row per pick,
+        // already in its compact place, through moe_rowsel (down)
+        const size_t xrows = per_pick ? cap : ntok;
+        DevBuf dx(xrows * K * sizeof(float));
+        if (per_pick) {
+            std::vector<float> hx((size_t)cap * K, 0.0f);
+            for (int i = 0; i < n; ++i) std::memcpy(&hx[(size_t)pos[i] * K], x + (size_t)i * K, (size_t)K * sizeof(float));
+            MI_HIP(hipMemcpy(dx.p, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            MI_HIP(hipMemcpy(dx.p, x, (size_t)ntok * K * sizeof(float), hipMemcpyHostToDevice));
+        }
+        DevBuf dq((size_t)cap * K), ddT((size_t)cap * (K / 32) * sizeof(float)), dbs((size_t)cap * (K / 256) * 16);
+        ActQ8 act{dq.as<int8_t>(), ddT.as<float>(), dbs.as<int8_t>(), K, cap, cap, type == T_Q8_0 ? 1 : 0};
+        launch_quant_act(dx.as<float>(), K, nullptr, 0.0f, act, nullptr, per_pick ? drs.as<int>() : drows.as<int>());
+        DevBuf dy((size_t)cap * rows * sizeof(float));
+        MI_HIP(hipMemset(dy.p, 0, (size_t)cap * rows * sizeof(float)));
+        if (mode == 0) {   // Ctx::moe_ffn_batch's launch
+            DevBuf dtp((size_t)cap * 4 * sizeof(int));
+            MI_HIP(hipMemset(dtp.p, 0, (size_t)cap * 4 * sizeof(int)));
+            GemmParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.A = A;
+            p.B = B;
+            p.pair = pair ? PAIR_AB : PAIR_ADJ;
+            p.epi = pair ? EPI_SWIGLU : EPI_STORE;
+            p.K = K;
+            p.ntok = cap;
+            p.tokpos = dtp.as<int>();
+            p.out = dy.as<float>();
+            p.out_stride = rows;
+            p.grp = dgrp.as<int>();
+            p.grp_n = n_expert;
+            p.grp_max = ntok;
+            p.grp_stride = A.sw_expert_stride;
+            launch_mmq32(p, act, nullptr, nullptr);
+            MI_HIP(hipDeviceSynchronize());
+        } else {           // Ctx::moe_ffn_short's launch, its K-parts added by part_sum
+            const int pst = pair ? 2 * rows : rows;
+            const size_t pbytes = (size_t)mmqs_parts(K) * cap * pst * sizeof(float);
+            DevBuf part(pbytes);
+            MI_HIP(hipMemset(part.p, 0, pbytes));
+            const int kp = launch_mmqs_grouped(A, pair, pair ? rows : 0, act, part.as<float>(), pst, dgrp.as<int>(), n_expert,
+                                               ntok, nullptr);
+            launch_part_sum(part.as<float>(), kp, cap, rows, pst, nullptr, 0, dy.as<float>(), rows, nullptr, pair ? rows : 0);
+            MI_HIP(hipDeviceSynchronize());
+        }
+        std::vector<float> hy((size_t)cap * rows);
+        MI_HIP(hipMemcpy(hy.data(), dy.p, hy.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) std::memcpy(y + (size_t)i * rows, &hy[(size_t)pos[i] * rows], (size_t)rows * sizeof(float));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const void* up, const void* down,
+                         int32_t n_expert, int32_t n_embd, int32_t n_ff, const float* x, const float* norm_w, float eps,
+                         const int32_t* sel, const float* selw, const float* addend, float* h_out, float* x_out) {
+    try {
+        if (!gate || !up || !down || !x || !norm_w || !sel || !selw || !h_out || !x_out) throw Error("op_moe_decode: null argument");
+        if (!is_quant(type)) throw Error("op_moe_decode: unsupported quant type");
+        if (n_expert < 1 || n_embd < 256 || n_embd % 256 || n_ff < 256 || n_ff % 256) throw Error("op_moe_decode: bad shape");
+        for (int k = 0; k < 2; ++k)
+            if (sel[k] < 0 || sel[k] >= n_expert) throw Error("op_moe_decode: expert out of range");
+        MI_HIP(hipSetDevice(device));
+        ensure_attrs(device);
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        const QMat G = upload_experts(type, gate, n_expert, n_ff, n_embd, keep);
+        const QMat Up = upload_experts(type, up, n_expert, n_ff, n_embd, keep);
+        const QMat D = upload_experts(type, down, n_expert, n_embd, n_ff, keep);
+        DevBuf dx((size_t)n_embd * sizeof(float)), dn((size_t)n_embd * sizeof(float)), dh((size_t)2 * n_ff * sizeof(float));
+        DevBuf dsel(2 * sizeof(int)), dselw(2 * sizeof(float)), dadd((size_t)n_embd * sizeof(float));
+        MI_HIP(hipMemcpy(dx.p, x, (size_t)n_embd * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dn.p, norm_w, (size_t)n_embd * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dsel.p, sel, 2 * sizeof(int), hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dselw.p, selw, 2 * sizeof(float), hipMemcpyHostToDevice));
+        if (addend) MI_HIP(hipMemcpy(dadd.p, addend, (size_t)n_embd * sizeof(float), hipMemcpyHostToDevice));
+        MI_HIP(hipMemset(dh.p, 0xFF, (size_t)2 * n_ff * sizeof(float)));
+        float* h = dh.as<float>();
+        float* h2 = h + n_ff;
+        // Ctx::gate_up_params (MoE): the two routed experts' gate/up + SwiGLU into h and h2
+        GemvParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.pro = PRO_RMSNORM;
+        p.nslots = 1;
+        p.x[0] = dx.as<float>();
+        p.norm_w = dn.as<float>();
+        p.eps = eps;
+        p.K = n_embd;
+        p.sel = dsel.as<int>();
+        p.selw = dselw.as<float>();
+        p.nseg = 2;
+        for (int k = 0; k < 2; ++k) {
+            p.seg[k] = seg_of(G, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
+            p.seg[k].B = Up;
+            p.seg[k].expA = p.seg[k].expB = k;
+        }
+        launch_gemv(p, nullptr);
+        // Ctx::down_params (MoE): x = (down[e0] h * w0 + down[e1] h2 * w1) + x [+ addend], in place
+        GemvParams d;
+        std::memset(&d, 0, sizeof(d));
+        d.pro = PRO_PLAIN;
+        d.nslots = 2;
+        d.x[0] = h;
+        d.x[1] = h2;
+        d.eps = eps;
+        d.K = n_ff;
+        d.sel = dsel.as<int>();
+        d.selw = dselw.as<float>();
+        d.nseg = 1;
+        d.seg[0] = seg_of(D, PAIR_AB, EPI_MOE_DOWN, dx.as<float>());
+        d.seg[0].expA = 0;
+        d.seg[0].expB = 1;
+        d.seg[0].actB = 1;
+        d.seg[0].resid = dx.as<float>();
+        d.seg[0].addend = addend ? dadd.as<float>() : nullptr;
+        launch_gemv(d, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        MI_HIP(hipMemcpy(h_out, dh.p, (size_t)2 * n_ff * sizeof(float), hipMemcpyDeviceToHost));
+        MI_HIP(hipMemcpy(x_out, dx.p, (size_t)n_embd * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
     MI_TRY(-1)

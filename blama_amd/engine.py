@@ -118,6 +118,13 @@ _SIGS = {
     "mi_op_gemm": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_attention_batch": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           _P, _P, _P, _P, _P, _P, _P]),
+    "mi_op_router": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P,
+                                 _P, _P, _P]),
+    "mi_op_moe_group": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mi_op_moe_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, _P, C.c_int32, _P, _P]),
+    "mi_op_moe_decode": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                     C.c_float, _P, _P, _P, _P, _P]),
 }
 
 
@@ -546,3 +553,82 @@ def op_attention_batch(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, n_head_k
     _check(lib().mi_op_attention_batch(device, n_head, n_head_kv, hd, n, ntok, _ptr(q), _ptr(k16), _ptr(v16),
                                        _ptr(cp), _ptr(tc), _ptr(tpos), _ptr(out)), "op_attention_batch")
     return out
+
+
+def moe_rows_cap(n: int, E: int) -> int:
+    """Rows of the grouped picks' buffers (kernels.h moe_rows_cap): every expert's rows padded to 32."""
+    return (n + E * 31 + 31) // 32 * 32
+
+
+def op_router(x: np.ndarray, norm_w: np.ndarray, w: np.ndarray, eps: float = 1e-5, n_embd: int | None = None,
+              part=None, device: int = 0):
+    """mi_op_router: x (ntok, x_stride) f32 rows whose first n_embd (default: norm_w's length)
+    elements are the token, w (n_expert, n_embd) f32 -> (sel (ntok, 2) i32, selw (ntok, 2) f32,
+    x after the call (ntok, x_stride)); part (2, ntok, n_embd): the split-K halves added to x first."""
+    x = np.ascontiguousarray(x, np.float32)
+    norm_w = np.ascontiguousarray(norm_w, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    ntok, x_stride = x.shape
+    n_embd = norm_w.size if n_embd is None else n_embd
+    n_expert = w.shape[0]
+    p = None if part is None else np.ascontiguousarray(part, np.float32)
+    sel = np.empty((ntok, 2), np.int32)
+    selw = np.empty((ntok, 2), np.float32)
+    x_out = np.empty_like(x)
+    _check(lib().mi_op_router(device, n_embd, n_expert, ntok, _ptr(x), x_stride, _ptr(norm_w), eps, _ptr(w),
+                              None if p is None else _ptr(p), _ptr(sel), _ptr(selw), _ptr(x_out)), "op_router")
+    return sel, selw, x_out
+
+
+def op_moe_group(sel: np.ndarray, U: int, E: int, cap: int | None = None, device: int = 0):
+    """mi_op_moe_group: the picks sel (n,) grouped by expert -> (grp (2E+1,), rows (cap,), rowsel
+    (cap,), pos (n,)); cap defaults to moe_rows_cap(n, E).  Unwritten entries hold -2139062144."""
+    sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+    n = sel.size
+    cap = moe_rows_cap(n, E) if cap is None else cap
+    grp = np.empty(2 * max(E, 0) + 1, np.int32)
+    rows = np.empty(max(cap, 1), np.int32)
+    rowsel = np.empty(max(cap, 1), np.int32)
+    pos = np.empty(n, np.int32)
+    _check(lib().mi_op_moe_group(device, _ptr(sel), n, U, E, cap, _ptr(grp), _ptr(rows), _ptr(rowsel), _ptr(pos)),
+           "op_moe_group")
+    return grp, rows, rowsel, pos
+
+
+def op_moe_gemm(mode: int, type_: int, raw: np.ndarray, n_expert: int, rows: int, K: int, x: np.ndarray,
+                sel: np.ndarray, raw_up=None, per_pick: bool = False, device: int = 0) -> np.ndarray:
+    """mi_op_moe_gemm: the grouped expert GEMM (mode 0 tiled, 1 short) of sel (ntok, 2) picks over
+    raw = n_expert matrices of rows x K; x (ntok, K), or (2 ntok, K) with per_pick -> (2 ntok, rows),
+    row i = pick i; with raw_up the gate/up SwiGLU pair."""
+    raw = np.ascontiguousarray(raw, np.uint8)
+    up = None if raw_up is None else np.ascontiguousarray(raw_up, np.uint8)
+    x = np.ascontiguousarray(x, np.float32)
+    sel = np.ascontiguousarray(sel, np.int32).reshape(-1, 2)
+    ntok = sel.shape[0]
+    if x.shape != ((2 * ntok if per_pick else ntok), K):
+        raise EngineError(f"op_moe_gemm: x has shape {x.shape}")
+    y = np.empty((2 * ntok, rows), np.float32)
+    _check(lib().mi_op_moe_gemm(device, mode, type_, _ptr(raw), None if up is None else _ptr(up), n_expert, rows, K,
+                                ntok, _ptr(x), 1 if per_pick else 0, _ptr(sel), _ptr(y)), "op_moe_gemm")
+    return y
+
+
+def op_moe_decode(type_: int, gate: np.ndarray, up: np.ndarray, down: np.ndarray, n_expert: int, n_embd: int,
+                  n_ff: int, x: np.ndarray, norm_w: np.ndarray, sel, selw, eps: float = 1e-5, addend=None,
+                  device: int = 0):
+    """mi_op_moe_decode: the decode step's gate/up and down launches for the picks sel (2,) with
+    weights selw (2,) -> (h (2, n_ff), x_out (n_embd,))."""
+    gate = np.ascontiguousarray(gate, np.uint8)
+    up = np.ascontiguousarray(up, np.uint8)
+    down = np.ascontiguousarray(down, np.uint8)
+    x = np.ascontiguousarray(x, np.float32)
+    norm_w = np.ascontiguousarray(norm_w, np.float32)
+    sel = np.ascontiguousarray(sel, np.int32)
+    selw = np.ascontiguousarray(selw, np.float32)
+    a = None if addend is None else np.ascontiguousarray(addend, np.float32)
+    h = np.empty((2, n_ff), np.float32)
+    x_out = np.empty(n_embd, np.float32)
+    _check(lib().mi_op_moe_decode(device, type_, _ptr(gate), _ptr(up), _ptr(down), n_expert, n_embd, n_ff, _ptr(x),
+                                  _ptr(norm_w), eps, _ptr(sel), _ptr(selw), None if a is None else _ptr(a), _ptr(h),
+                                  _ptr(x_out)), "op_moe_decode")
+    return h, x_out

@@ -285,6 +285,43 @@ int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv,
  * of small models).  type2/raw2/rows2: the second matrix (raw2 NULL: none). */
 int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                     int32_t type2, const void* raw_blocks2, int32_t rows2, const float* x, const float* resid, float* y);
+/* ---- the mixture-of-experts kernels, one at a time (build_moe_ffn: softmax gating, top-2) ----
+ * The router of ntok token rows x[t * x_stride] (n_embd floats each, x_stride >= n_embd, a
+ * multiple of 4): rms_norm(x, eps) * norm_w, logits against w [n_expert][n_embd] (F32), softmax,
+ * the top 2 (ties: the lower index first) and their weights normalised over the two.  part
+ * (nullable): the split-K halves [2][ntok][n_embd] of the projection that produced x, added first
+ * and written back, x = (p0 + p1) + x.  sel_out / selw_out: [ntok][2]; x_out (nullable): the
+ * [ntok][x_stride] rows after the call.  n_expert <= 64, n_embd a multiple of 256, <= 4096. */
+int32_t mi_op_router(int32_t device, int32_t n_embd, int32_t n_expert, int32_t ntok, const float* x, int32_t x_stride,
+                     const float* norm_w, float eps, const float* w, const float* part, int32_t* sel_out,
+                     float* selw_out, float* x_out);
+/* The grouping of n picks (sel[t * U + k] = expert of token t's slot k) by expert, E <= 16:
+ * grp_out[2E + 1] = {off[0..E], cnt[0..E-1]} with off[e + 1] = off[e] + cnt[e] rounded up to 32;
+ * rows_out[rows_cap] = the source token of each row (-1: padding), tokens ascending within an
+ * expert; rowsel_out[rows_cap] = r or -1; pos_out[n] = the row of each pick.  rows_cap: the
+ * capacity of rows_out / rowsel_out, at least (n + 31 E + 31) / 32 * 32 (the engine's value).
+ * Every output is pre-filled with 0x80808080, so an entry the kernel did not write shows. */
+int32_t mi_op_moe_group(int32_t device, const int32_t* sel, int32_t n, int32_t U, int32_t E, int32_t rows_cap,
+                        int32_t* grp_out, int32_t* rows_out, int32_t* rowsel_out, int32_t* pos_out);
+/* The experts' grouped GEMM of a prompt batch: raw_blocks (and raw_up) hold n_expert matrices of
+ * rows x K back to back; sel[ntok][2] are each token's two distinct experts.  The picks are grouped
+ * (mi_op_moe_group's kernel), their rows quantised to Q8_K / Q8_0 -- per_pick 0: x is [ntok][K],
+ * pick i reads token i / 2's row (the gate/up stage); per_pick 1: x is [2 ntok][K], one row per
+ * pick (the down stage) -- and multiplied by their experts' matrices: mode 0 the tiled grouped GEMM
+ * (any type of mi_op_gemm, ntok <= 512), mode 1 the short grouped GEMM (Q4_K / Q5_K / Q6_K,
+ * ntok <= 64) with its K-parts added.  raw_up non-NULL: the gate/up pair, silu(gate) * up.
+ * y[2 ntok][rows]: row i = pick i (token i / 2 through expert sel[i]). */
+int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* raw_blocks, const void* raw_up,
+                       int32_t n_expert, int32_t rows, int32_t K, int32_t ntok, const float* x, int32_t per_pick,
+                       const int32_t* sel, float* y);
+/* The decode step's two expert launches after the router, with the router's result given:
+ * h_out[k] = silu(gate[sel[k]] c) * (up[sel[k]] c), c = rms_norm(x, eps) * norm_w (k = 0, 1), then
+ * x_out = ((down[sel[0]] h0) * selw[0] + (down[sel[1]] h1) * selw[1]) + x [+ addend].  gate / up:
+ * n_expert matrices of n_ff x n_embd back to back, down: of n_embd x n_ff; addend (nullable):
+ * [n_embd].  h_out: [2][n_ff], x_out: [n_embd]. */
+int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const void* up, const void* down,
+                         int32_t n_expert, int32_t n_embd, int32_t n_ff, const float* x, const float* norm_w, float eps,
+                         const int32_t* sel, const float* selw, const float* addend, float* h_out, float* x_out);
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);

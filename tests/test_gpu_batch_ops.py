@@ -24,63 +24,10 @@ import pytest
 
 import ggml_ref as R
 from blama_amd import engine
+from gemm_ref_util import GEMM_TOL, gemm_ref, gemm_swiglu_ref
 from util import rand_matrix, rand_x
 
 pytestmark = pytest.mark.gpu
-
-GEMM_TOL = 2e-5
-
-
-def _act_blocks(t, X):
-    """Dequantised activations per quant block: (blk_elems, A[T, nblk, blk_elems] f64)."""
-    T, K = X.shape
-    if t == R.Q8_0:
-        a = [R.quantize_q8_0(x) for x in X]
-        A = np.stack([q.d[:, None].astype(np.float64) * q.qs for q in a])          # (T, K/32, 32)
-        return 32, A
-    a = [R.quantize_q8_K(x) for x in X]
-    A = np.stack([q.d[:, None].astype(np.float64) * q.qs for q in a])              # (T, K/256, 256)
-    return 256, A
-
-
-def _weight_blocks(t, raw, rows, K):
-    """(Wp, Wm): the per-block weights split into the d*scale*q part and the -dmin*m part
-    (Q4_K only; None otherwise), f64 (rows, nblk, blk_elems)."""
-    if t in (R.Q4_K, R.Q5_K):
-        d, dmin, sc, m, q = (R.unpack_q4_K if t == R.Q4_K else R.unpack_q5_K)(raw)
-        nb = K // 256
-        q = q.reshape(rows, nb, 8, 32).astype(np.float64)
-        Wp = d.reshape(rows, nb, 1, 1).astype(np.float64) * sc.reshape(rows, nb, 8, 1) * q
-        Wm = np.broadcast_to((dmin.reshape(rows, nb, 1, 1).astype(np.float64) * m.reshape(rows, nb, 8, 1)),
-                             (rows, nb, 8, 32))
-        return Wp.reshape(rows, nb, 256), -Wm.reshape(rows, nb, 256)
-    if t == R.Q6_K:
-        d, sc, q = R.unpack_q6_K(raw)
-        nb = K // 256
-        Wp = d.reshape(rows, nb, 1, 1).astype(np.float64) * sc.reshape(rows, nb, 16, 1) * \
-            q.reshape(rows, nb, 16, 16).astype(np.float64)
-        return Wp.reshape(rows, nb, 256), None
-    d, q = R.unpack_q8_0(raw)
-    nb = K // 32
-    return d.reshape(rows, nb, 1).astype(np.float64) * q.reshape(rows, nb, 32), None
-
-
-def gemm_ref(t, raw, rows, K, X):
-    """y[T, rows] and the bound sum_b |term_b| (f64), all tokens at once."""
-    _, A = _act_blocks(t, X)
-    Wp, Wm = _weight_blocks(t, raw, rows, K)
-    T = X.shape[0]
-    y = np.zeros((T, rows))
-    bound = np.zeros((T, rows))
-    for b in range(A.shape[1]):
-        yp = A[:, b] @ Wp[:, b].T
-        y += yp
-        bound += np.abs(yp)
-        if Wm is not None:
-            ym = A[:, b] @ Wm[:, b].T
-            y += ym
-            bound += np.abs(ym)
-    return y, bound
 
 
 def _check_gemm(t, rows, K, ntok, pair, seed):
@@ -95,11 +42,8 @@ def _check_gemm(t, rows, K, ntok, pair, seed):
         lim = GEMM_TOL * bg + 1e-30
     else:
         u, bu = gemm_ref(t, up, rows, K, X)
-        s = g / (1.0 + np.exp(-g))
-        ref = s * u
+        ref, lim = gemm_swiglu_ref(g, bg, u, bu)
         err = np.abs(got - ref)
-        # d(silu(g) u) <= |silu'(g)| |u| eg + |silu(g)| eu, |silu'| <= 1.1; plus the fp32 epilogue
-        lim = GEMM_TOL * (1.1 * np.abs(u) * bg + np.abs(s) * bu) + 1e-6 * np.abs(ref) + 1e-30
     bad = np.argwhere(err > lim)
     assert bad.size == 0, (R.TYPE_NAME[t], rows, K, ntok, len(bad), bad[:5].tolist(), float((err / lim).max()))
 

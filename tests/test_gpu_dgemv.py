@@ -15,18 +15,13 @@ import pytest
 
 import ggml_ref as R
 from blama_amd import engine
+from gemm_ref_util import gemv_ref as _ref, gemv_swiglu_ref
 from util import rand_matrix, rand_x
 
 pytestmark = pytest.mark.gpu
 
 GEMV_TOL = 2e-5
 ROLE_QKV, ROLE_ADD, ROLE_SWIGLU, ROLE_STORE, ROLE_ADDQ = 0, 1, 2, 3, 4
-
-
-def _ref(t, w, K, x, sel=None):
-    if sel is not None:
-        w = w.reshape(-1, R.row_bytes(t, K))[sel].reshape(-1)
-    return R.mul_mat_vec(w, t, K, x).astype(np.float64), R.mul_mat_vec_abs(w, t, K, x)
 
 
 def _sel(rows):
@@ -91,13 +86,7 @@ def test_dgemv_swiglu_pair(gpu_lib, t, rows, K):
     sel = _sel(rows)
     g, ga = _ref(t, wg, K, x, sel)
     u, ua = _ref(t, wu, K, x, sel)
-    # silu(g) * u in fp32 (ggml_vec_swiglu_f32 of b5187: silu then mul); the bound propagates
-    # the GEMV bounds of g and u through the product
-    g32, u32 = g.astype(np.float32), u.astype(np.float32)
-    ref = (g32 / (np.float32(1) + np.exp(-g32))) * u32
-    sg = 1.0 / (1.0 + np.exp(-g))
-    dsilu = np.abs(sg * (1 + g * (1 - sg)))
-    bound = (dsilu * np.abs(u) * ga + np.abs(g * sg) * ua) * GEMV_TOL + np.abs(ref) * 3e-7 + 1e-30
+    ref, bound = gemv_swiglu_ref(g, ga, u, ua, GEMV_TOL)
     got = (y if sel is None else y[sel]).astype(np.float64)
     err = np.abs(got - ref.astype(np.float64))
     assert np.all(err <= bound), (R.TYPE_NAME[t], rows, K, float((err / bound).max()))
