@@ -623,6 +623,7 @@ void mi_ctx_clear_lora(mi_ctx* c) {
 
 // ---- embeddings ----
 int32_t mi_model_pooling_type(const mi_model* m) { return m ? m->impl.hp.pooling_type : -1; }
+int32_t mi_model_causal_attn(const mi_model* m) { return m ? (m->impl.hp.arch == ARCH_BERT ? 0 : 1) : -1; }
 
 int32_t mi_ctx_set_embeddings(mi_ctx* c, int32_t on, int32_t pooling) {
     try {
@@ -661,6 +662,7 @@ int64_t mi_prof_bytes(const mi_ctx* c) { return c ? c->impl->prof_bytes : -1; }
 
 int32_t mi_decode_path(const mi_ctx* c) {
     if (!c) return -1;
+    if (c->impl->enc) return 2;
     return c->impl->sp_ok ? 1 : 0;
 }
 int32_t mi_debug_stamps(mi_ctx* c, uint64_t* out, int32_t n_launch) {
@@ -1294,6 +1296,73 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
         MI_HIP(hipDeviceSynchronize());
         MI_HIP(hipMemcpy(h_out, dh.p, (size_t)2 * n_ff * sizeof(float), hipMemcpyDeviceToHost));
         MI_HIP(hipMemcpy(x_out, dx.p, (size_t)n_embd * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// One launch of the encoder GEMM (enc.hip enc_gemm_f16_kernel): y[t][r] = sum_k f16(x[t][k]) w[r][k],
+// then the epilogue (0 none, 1 bias, 2 bias + gelu, 3 bias + resid).
+int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int32_t K, int32_t ntok, const float* x,
+                       const float* bias, const float* resid, int32_t epilogue, float* y) {
+    try {
+        if (!w_f16 || !x || !y) throw Error("op_gemm_f16: null argument");
+        if (epilogue < ENC_NONE || epilogue > ENC_RESID) throw Error("op_gemm_f16: epilogue 0 .. 3");
+        if (epilogue != ENC_NONE && !bias) throw Error("op_gemm_f16: this epilogue needs a bias");
+        if (epilogue == ENC_RESID && !resid) throw Error("op_gemm_f16: residual epilogue without resid");
+        if (rows < 32 || rows % 32 || K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_TOK)
+            throw Error("op_gemm_f16: rows % 32, K % 32, 1 <= ntok <= 512");
+        MI_HIP(hipSetDevice(device));
+        const size_t nw = (size_t)rows * K, nx = (size_t)ntok * K, ny = (size_t)ntok * rows;
+        DevBuf dw(nw * 2), dx(nx * 4), dy(ny * 4), db((size_t)rows * 4), dr(ny * 4), dt(65536 * 2);
+        MI_HIP(hipMemcpy(dw.p, w_f16, nw * 2, hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        if (epilogue != ENC_NONE) MI_HIP(hipMemcpy(db.p, bias, (size_t)rows * 4, hipMemcpyHostToDevice));
+        if (epilogue == ENC_RESID) MI_HIP(hipMemcpy(dr.p, resid, ny * 4, hipMemcpyHostToDevice));
+        if (epilogue == ENC_GELU) {
+            const std::vector<unsigned short> t = gelu_table_host();
+            MI_HIP(hipMemcpy(dt.p, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+        }
+        EncGemm g{};
+        g.m[0] = EncMat{dw.as<__half>(), epilogue != ENC_NONE ? db.as<float>() : nullptr, rows, dy.as<float>(), nullptr};
+        g.nmat = 1;
+        g.epi = epilogue;
+        g.K = K;
+        g.ntok = ntok;
+        g.x = dx.as<float>();
+        g.x_stride = K;
+        g.out_stride = rows;
+        g.resid = epilogue == ENC_RESID ? dr.as<float>() : nullptr;
+        g.gelu_tab = dt.as<unsigned short>();
+        launch_enc_gemm(g, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        MI_HIP(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// Bidirectional attention of ntok tokens over themselves (enc.hip enc_attn_kernel): q f32 [ntok][n_head *
+// head_dim], k / v f16 of the same shape -> out f32; scale 1 / sqrtf(head_dim).
+int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok, const float* q,
+                            const uint16_t* k_f16, const uint16_t* v_f16, float* out) {
+    try {
+        if (!q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc: null argument");
+        if (n_head < 1 || ntok < 1 || ntok > ENC_MAX_TOK || !enc_attn_supported(head_dim))
+            throw Error("op_attention_enc: head_dim 32 or 64, 1 <= ntok <= 512");
+        MI_HIP(hipSetDevice(device));
+        init_enc_attributes();
+        const int ne = n_head * head_dim;
+        const size_t n = (size_t)ntok * ne;
+        DevBuf dq(n * 4), dk(n * 2), dv(n * 2), dout(n * 4);
+        MI_HIP(hipMemcpy(dq.p, q, n * 4, hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dk.p, k_f16, n * 2, hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dv.p, v_f16, n * 2, hipMemcpyHostToDevice));
+        launch_enc_attn(EncAttn{dq.as<float>(), dk.as<__half>(), dv.as<__half>(), ne, ne, ne, n_head, head_dim, ntok,
+                                1.0f / std::sqrt((float)head_dim), dout.as<float>()},
+                        nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        MI_HIP(hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
         return 0;
     }
     MI_TRY(-1)

@@ -126,6 +126,11 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         g_attr_done[device] = 1;
     }
     stream = mem.stream();
+    if (hp.arch == ARCH_BERT) {   // an encoder context: no KV cache, no decode step (enc.cpp)
+        enc_init();
+        dev_chain(device).nctx++;
+        return;
+    }
     const size_t kvn = (size_t)hp.n_layer * n_ctx * kv_dim;
     kcache = mem.dev<__half>(kvn);
     vcache = mem.dev<__half>(kvn);
@@ -279,6 +284,7 @@ void Ctx::invalidate_graphs() {
 
 void Ctx::apply_cvec(const float* data, size_t len, int n_embd, int il_start, int il_end) {
     const HParams& hp = m->hp;
+    if (enc) throw Error("apply_cvec: encoder models take no control vector");
     if (data && n_embd != hp.n_embd) throw Error("apply_cvec: the control vector's n_embd differs from the model's");
     MI_HIP(hipSetDevice(device));
     sync();                 // steps in flight still read the old rows
@@ -299,6 +305,7 @@ void Ctx::apply_cvec(const float* data, size_t len, int n_embd, int il_start, in
 }
 
 long long Ctx::ffn_bytes() const {
+    if (enc) return 0;
     const Layer& L = m->layers[0];
     auto mb = [](const QMat& q) { return (long long)q.rows * q.nb * ((long long)block_bytes(q.type) * 256 / block_elems(q.type)); };
     const HParams& hp = m->hp;
@@ -740,6 +747,7 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     unsynced = true;
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 0 || tokens[i] >= m->hp.n_vocab) throw Error("decode: token id out of range");
+    if (enc) return decode_enc(tokens, n, all);
     if (n_cells + n > (int)n_ctx) return 1;   // no KV slot (llama_decode returns 1)
     if (m->hp.arch == ARCH_GPT2 && pos_max + n >= m->hp.n_ctx_train)
         throw Error("decode: gpt2 position past the learned position embeddings (n_ctx_train)");
@@ -874,6 +882,7 @@ void Ctx::set_embeddings(bool on, int pooling_type) {
     if (pooling_type == MI_POOLING_RANK)
         throw Error("set_embeddings: RANK pooling needs a classification head, which this engine does not load");
     if (pooling_type == MI_POOLING_UNSPECIFIED) pooling_type = model_pooling(m->hp);
+    if (enc && !on) throw Error("set_embeddings: encoder models have no output head (the context stays in embeddings mode)");
     MI_HIP(hipSetDevice(device));
     sync();                 // steps in flight still write the old mode's outputs
     invalidate_graphs();    // the step graphs end in the other tail
@@ -1023,6 +1032,7 @@ const float* Ctx::logits_host(int row) {
 }
 
 void Ctx::kv_clear() {
+    if (enc) return;   // no cache: every call is stateless
     n_cells = 0;
     pos_max = -1;
     out_rows = 0;      // rows of the last MI_OUT_ALL pass belong to the cleared cache
@@ -1032,6 +1042,7 @@ void Ctx::kv_clear() {
 // Remove cells with pos in [p0, p1); the survivors keep their order and are
 // compacted to the front of the cache.
 int Ctx::kv_seq_rm(int p0, int p1) {
+    if (enc) throw Error("kv_seq_rm: an encoder context has no KV cache");
     if (p0 < 0) p0 = 0;
     if (p1 < 0) p1 = INT_MAX;
     std::vector<int> keep;
@@ -1063,6 +1074,7 @@ int Ctx::kv_seq_rm(int p0, int p1) {
 // seq_add (div == 0: pos += delta) / seq_div (pos /= div) over [p0, p1):
 // positions change and cached K is re-rotated by the delta (K-shift).
 int Ctx::kv_seq_shift(int p0, int p1, int delta, int div) {
+    if (enc) throw Error("kv_seq_add / kv_seq_div: an encoder context has no KV cache");
     if (p0 < 0) p0 = 0;
     if (p1 < 0) p1 = INT_MAX;
     if (p0 == p1) return 0;
@@ -1105,12 +1117,14 @@ struct StateHdr {
 }  // namespace
 
 size_t Ctx::state_size() const {
+    if (enc) return 0;   // nothing survives an encoder call
     const HParams& hp = m->hp;
     return sizeof(StateHdr) + (size_t)n_cells * sizeof(int) +
            2 * (size_t)hp.n_layer * n_cells * kv_dim * sizeof(__half) + (size_t)hp.n_vocab * sizeof(float);
 }
 
 size_t Ctx::state_get(uint8_t* dst, size_t size) {
+    if (enc) return 0;
     const size_t need = state_size();
     if (size < need) throw Error("state_get: buffer too small");
     const HParams& hp = m->hp;
@@ -1142,6 +1156,7 @@ size_t Ctx::state_get(uint8_t* dst, size_t size) {
 }
 
 size_t Ctx::state_set(const uint8_t* src, size_t size) {
+    if (enc) return 0;
     const HParams& hp = m->hp;
     StateHdr hd;
     if (size < sizeof(hd)) throw Error("state_set: truncated state");

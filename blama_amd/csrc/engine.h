@@ -54,14 +54,16 @@ struct Gguf {
 };
 
 // --------------------------------------------------------------- model ----
+std::vector<unsigned short> gelu_table_host();   // ggml_table_gelu_f16, built on the host (model.cpp)
+
 struct HParams {
     int n_vocab = 0, n_embd = 0, n_layer = 0, n_head = 0, n_head_kv = 0, n_ff = 0, n_ctx_train = 0;
     int n_rot = 0, head_dim = 0, n_expert = 0, n_expert_used = 0;
     float eps = 1e-5f, rope_base = 10000.0f, freq_scale = 1.0f;
-    int arch = 0;                       // ARCH_LLAMA (llm_build_llama) or ARCH_GPT2 (llm_build_gpt2)
+    int arch = 0;                       // ARCH_LLAMA (llm_build_llama), ARCH_GPT2 (llm_build_gpt2) or ARCH_BERT (llm_build_bert)
     int pooling_type = -1;              // {arch}.pooling_type (llama_pooling_type), -1: the GGUF has none
 };
-enum { ARCH_LLAMA = 0, ARCH_GPT2 = 1 };
+enum { ARCH_LLAMA = 0, ARCH_GPT2 = 1, ARCH_BERT = 2 };
 
 struct Layer {
     float* attn_norm = nullptr;
@@ -78,6 +80,14 @@ struct Layer {
     // GPT-2: LayerNorm biases and the projection biases (attn_qkv is the one fused QKV group)
     float *attn_norm_b = nullptr, *ffn_norm_b = nullptr;
     float *bqkv = nullptr, *bo = nullptr, *bup = nullptr, *bdown = nullptr;
+};
+
+// A layer of an encoder model (llm_build_bert): F16 matrices [rows][K], F32 biases and LayerNorms
+struct EncLayer {
+    const __half *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *up = nullptr, *down = nullptr;
+    const float *bq = nullptr, *bk = nullptr, *bv = nullptr, *bo = nullptr, *bup = nullptr, *bdown = nullptr;
+    const float *attn_out_norm = nullptr, *attn_out_norm_b = nullptr;     // attn_output_norm
+    const float *layer_out_norm = nullptr, *layer_out_norm_b = nullptr;   // layer_output_norm
 };
 
 struct Model {
@@ -116,6 +126,10 @@ struct Model {
     unsigned short* gelu_tab = nullptr; // GPT-2: ggml_table_gelu_f16 on the device
     float* rope_freqs = nullptr;
     std::vector<Layer> layers;
+    // BERT: the token-type table (row 0 is added to every token), the embedding LayerNorm, the layers
+    QMat tok_types{};
+    const float *embd_norm = nullptr, *embd_norm_b = nullptr;
+    std::vector<EncLayer> enc_layers;
 
     ~Model();
     // data: the GGUF image (header at least; tensor data unless no_upload/vocab_only)
@@ -260,6 +274,22 @@ struct Ctx {
     // token rows r0 .. r0 + nt - 1 of embd into the pooled row (MEAN: accumulated; CLS: row 0; LAST: row n - 1)
     void embd_pool_rows(int r0, int nt);
     const float* embeddings_host(int row);
+    // Encoder models (ARCH_BERT): no KV cache; every decode call is one stateless pass over its n
+    // tokens at positions 0 .. n - 1 (enc.cpp), ending in the embedding rows.  Always in embeddings mode.
+    // Invariant: with enc set the constructor returned before any decoder buffer was allocated (kcache,
+    // cell_pos, logits, topk / gather buffers, h_logits ... are null) and `embeddings` stays true
+    // (set_embeddings refuses to turn it off), so every entry point that touches a decoder buffer
+    // must either check `embeddings` (the logits reads do) or check `enc` first.
+    bool enc = false;
+    int enc_max = 0;                    // tokens a call may hold: min(n_batch, ENC_MAX_TOK, n_ctx_train)
+    int* enc_tok = nullptr;             // [enc_max] token ids
+    int* h_enc_tok = nullptr;           // pinned ring [kEncRing][enc_max]
+    long long enc_slot = 0;
+    static constexpr int kEncRing = 16;
+    float *enc_x = nullptr, *enc_a = nullptr, *enc_x1 = nullptr, *enc_q = nullptr, *enc_o = nullptr, *enc_h = nullptr;
+    __half *enc_k = nullptr, *enc_v = nullptr;   // [enc_max][n_embd] f16 K / V of the layer
+    void enc_init();
+    int decode_enc(const int32_t* tokens, int n, bool all);
     // control vector (llama_adapter_cvec, b5187): row l is layer l's direction, added to the
     // residual stream after the layer's FFN residual add (build_cvec) in every path.  A property
     // of the context, not of its state (mi_state_get / mi_state_set leave it alone).

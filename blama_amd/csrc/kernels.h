@@ -492,4 +492,50 @@ struct EmbdPool {
 };
 void launch_embd_pool(const EmbdPool& p, hipStream_t s);
 
+// ---- encoder models (enc.hip): llm_build_bert, b5187 ----
+constexpr int ENC_MAX_TOK = 512;   // tokens of one call (llama.cpp: n_ubatch >= n_tokens for non-causal attention)
+// out[t] = pos[t] + (tok[tokens[t]] + typ[0]): the tables F16 (*_f16) or F32 rows of n_embd
+struct EncEmbed {
+    const int* tokens;     // [ntok]
+    int ntok, n_embd;
+    const void *tok, *typ, *pos;
+    int tok_f16, typ_f16, pos_f16;
+    float* out;            // [ntok][n_embd]
+};
+void launch_enc_embed(const EncEmbed& p, hipStream_t s);
+// y[t][r] = sum_k f16(x[t][k]) * W[r][k] (f32 accumulation of exact f16 products) for one to three
+// F16 matrices [rows][K] over one activation, then the epilogue: + bias[r]; gelu(. + bias[r]) by
+// ggml's f16 table; (. + bias[r]) + resid[t][r] -- each add a separate f32 operation.  rows % 32
+// == 0, K % 32 == 0, 1 <= ntok <= ENC_MAX_TOK.  A matrix writes f32 rows (out) or f16 rows (out16).
+enum EncEpi { ENC_NONE = 0, ENC_BIAS = 1, ENC_GELU = 2, ENC_RESID = 3 };
+struct EncMat {
+    const __half* w;       // [rows][K]
+    const float* bias;     // [rows] (every epilogue but ENC_NONE)
+    int rows;
+    float* out;            // [ntok][out_stride], or
+    __half* out16;         // [ntok][out_stride] f16
+};
+struct EncGemm {
+    EncMat m[3];
+    int nmat, epi, K, ntok;
+    const float* x;        // [ntok][x_stride]
+    int x_stride, out_stride;
+    const float* resid;    // ENC_RESID: [ntok][out_stride] (may alias out)
+    const unsigned short* gelu_tab;   // ENC_GELU: ggml_table_gelu_f16
+};
+void launch_enc_gemm(const EncGemm& p, hipStream_t s);
+// Bidirectional attention of ntok tokens over themselves: q f32 [ntok][q_stride], k / v f16
+// [ntok][kv_stride], head h at columns h * head_dim; out f32 [ntok][out_stride].  head_dim 32 or 64.
+struct EncAttn {
+    const float* q;
+    const __half *k, *v;
+    int q_stride, kv_stride, out_stride;
+    int n_head, head_dim, ntok;
+    float scale;
+    float* out;
+};
+bool enc_attn_supported(int head_dim);
+void init_enc_attributes();      // once per device (the attention kernel's LDS limit)
+void launch_enc_attn(const EncAttn& p, hipStream_t s);
+
 }  // namespace mi

@@ -49,7 +49,10 @@ std::shared_ptr<Lora> Lora::load(const Model* m, const uint8_t* data, size_t siz
     if (g.get_str("adapter.type", "") != "lora") throw Error("lora: adapter.type is not 'lora'");
     const std::string arch = g.get_str("general.architecture", ""), march = m->gguf.get_str("general.architecture", "");
     if (arch != march) throw Error("lora: the adapter's architecture '" + arch + "' differs from the base model's '" + march + "'");
-    if (m->hp.arch != ARCH_LLAMA) throw Error("lora: GPT-2 base models are not supported");
+    if (m->hp.arch != ARCH_LLAMA) {   // worded for any other architecture ("GPT-2" as that family is written)
+        throw Error("lora: " + (march == "gpt2" ? std::string("GPT-2") : march) +
+                    " base models are not supported: adapters are served on LLaMA-architecture base models only");
+    }
     if (m->hp.n_expert > 0) throw Error("lora: MoE base models are not supported");
     auto out = std::make_shared<Lora>();
     out->m = m;

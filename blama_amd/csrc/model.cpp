@@ -141,7 +141,6 @@ Model::~Model() {
     if (gelu_tab) hipFree(gelu_tab);
 }
 
-namespace {
 // ggml_table_gelu_f16 (ggml-cpu.c init with GGML_GELU_FP16): fp16(ggml_gelu_f32(fp32(h))) for
 // every f16 bit pattern h, ggml_gelu_f32(x) = 0.5f*x*(1.0f + tanhf(SQRT_2_OVER_PI*x*(1.0f +
 // GELU_COEF_A*x*x))), evaluated on the host with the C library's tanhf (no FMA contraction:
@@ -160,7 +159,6 @@ std::vector<unsigned short> gelu_table_host() {
     }
     return t;
 }
-}  // namespace
 
 // Expert e of a MoE tensor as a matrix of its own (planes and MFMA-order copy offset).
 QMat expert_view(const QMat& q, int e) {
@@ -232,9 +230,10 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     vocab_only = p.vocab_only != 0;
     gguf.parse(data, size);
     const std::string arch = gguf.get_str("general.architecture", "");
-    if (arch != "llama" && arch != "gpt2")
-        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama and gpt2 graphs)");
-    hp.arch = arch == "gpt2" ? ARCH_GPT2 : ARCH_LLAMA;
+    if (arch != "llama" && arch != "gpt2" && arch != "bert")
+        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama, gpt2 and bert graphs)");
+    hp.arch = arch == "gpt2" ? ARCH_GPT2 : arch == "bert" ? ARCH_BERT : ARCH_LLAMA;
+    const bool bert = hp.arch == ARCH_BERT;
     auto key = [&](const char* k) { return arch + "." + k; };
     hp.n_embd = (int)gguf.get_int(key("embedding_length"), 0);
     hp.n_layer = (int)gguf.get_int(key("block_count"), 0);
@@ -242,7 +241,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     hp.n_head = (int)gguf.get_int(key("attention.head_count"), 0);
     hp.n_head_kv = (int)gguf.get_int(key("attention.head_count_kv"), hp.n_head);
     hp.n_ctx_train = (int)gguf.get_int(key("context_length"), 2048);
-    hp.eps = (float)gguf.get_float(key(hp.arch == ARCH_GPT2 ? "attention.layer_norm_epsilon"
+    hp.eps = (float)gguf.get_float(key(hp.arch != ARCH_LLAMA ? "attention.layer_norm_epsilon"
                                                              : "attention.layer_norm_rms_epsilon"), 1e-5);
     hp.rope_base = (float)gguf.get_float(key("rope.freq_base"), 10000.0);
     // llama.cpp b5187 (llama-model.cpp load_hparams): the factor is rope.scaling.factor, else the
@@ -262,6 +261,18 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     hp.head_dim = hp.n_embd / hp.n_head;
     hp.n_rot = hp.arch == ARCH_GPT2 ? 0 : (int)gguf.get_int(key("rope.dimension_count"), hp.head_dim);
     if (hp.arch == ARCH_GPT2 && hp.n_expert) throw Error("gpt2: no MoE");
+    if (bert) {   // llm_build_bert: no RoPE, every head its own K / V, no experts, no output head
+        hp.n_rot = 0;
+        hp.n_head_kv = hp.n_head;
+        hp.n_expert = hp.n_expert_used = 0;
+        if (gguf.get_int(key("attention.causal"), 0) != 0)
+            throw Error("bert: " + key("attention.causal") + " = true is not served (the encoder pass is bidirectional)");
+        if (hp.n_ff <= 0) throw Error("GGUF: missing bert hparams");
+        if (hp.n_embd % 32) throw Error("bert: embedding_length " + std::to_string(hp.n_embd) + " is not a multiple of 32");
+        if (hp.n_ff % 32) throw Error("bert: feed_forward_length " + std::to_string(hp.n_ff) + " is not a multiple of 32");
+        if (hp.n_embd % hp.n_head || !enc_attn_supported(hp.head_dim))
+            throw Error("bert: head_dim " + std::to_string(hp.head_dim) + " is not served (32 or 64)");
+    }
 
     if (const GgufValue* tv = gguf.get("tokenizer.ggml.tokens")) tokens = tv->arr_s;
     if (const GgufValue* tt = gguf.get("tokenizer.ggml.token_type"))
@@ -347,13 +358,65 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     };
     const bool gpt2 = hp.arch == ARCH_GPT2;
     const int i_te = add("token_embd.weight", true, 1);
-    const int i_pe = gpt2 ? add("position_embd.weight", true, 1) : -1;
-    const int i_on = add("output_norm.weight", true, 1);
+    const int i_pe = gpt2 || bert ? add("position_embd.weight", true, 1) : -1;
+    const int i_on = bert ? -1 : add("output_norm.weight", true, 1);
     const int i_onb = gpt2 ? add("output_norm.bias", true, 1) : -1;
-    int i_out = add("output.weight", false, 1);
-    const int i_rf = add("rope_freqs.weight", false, 1);
+    int i_out = bert ? -1 : add("output.weight", false, 1);
+    const int i_rf = bert ? -1 : add("rope_freqs.weight", false, 1);
     std::vector<LayerIdx> li(hp.n_layer);
     const int E = hp.n_expert > 0 ? hp.n_expert : 1;
+    // llm_build_bert's tensors (LLM_ARCH_BERT): F16 matrices [rows][K] -- K = 384 of bge-small is no
+    // multiple of a k-quant's 256 -- and tables, F32 biases and LayerNorms
+    struct BertIdx {
+        int w[6], b[6], an, anb, on, onb;   // q, k, v, o, up, down
+    };
+    std::vector<BertIdx> bi(bert ? hp.n_layer : 0);
+    int i_tt = -1, i_en = -1, i_enb = -1;
+    auto bert_mat = [&](const std::string& name, int rows, int K) {
+        const int i = add(name, true, 1);
+        const GgufTensor* t = plan[i].t;
+        if (t->type != T_F16)
+            throw Error("tensor " + name + ": a BERT matrix must be F16 (ggml type " + std::to_string(t->type) + " is not served)");
+        if (t->n_dims != 2 || t->ne[0] != K || t->ne[1] != rows) throw Error("tensor " + name + ": unexpected shape");
+        return i;
+    };
+    auto bert_vec = [&](const std::string& name, int n) {
+        const int i = add(name, true, 1);
+        const GgufTensor* t = plan[i].t;
+        if (t->type != T_F32) throw Error("tensor " + name + " must be F32");
+        if (t->ne[0] != n || plan[i].rows != 1) throw Error("tensor " + name + ": unexpected shape");
+        return i;
+    };
+    if (bert) {
+        auto table = [&](int i, long long rows_min) {
+            const GgufTensor* t = plan[i].t;
+            if (t->type != T_F16 && t->type != T_F32) throw Error("tensor " + t->name + ": a BERT embedding table must be F16 or F32");
+            if (t->ne[0] != hp.n_embd || t->ne[1] < rows_min) throw Error("tensor " + t->name + ": unexpected shape");
+        };
+        table(i_te, 1);
+        table(i_pe, 1);
+        hp.n_ctx_train = (int)std::min<long long>(hp.n_ctx_train, plan[i_pe].t->ne[1]);   // the position table ends here
+        i_tt = add("token_types.weight", true, 1);
+        table(i_tt, 1);
+        i_en = bert_vec("token_embd_norm.weight", hp.n_embd);
+        i_enb = bert_vec("token_embd_norm.bias", hp.n_embd);
+        const int E_ = hp.n_embd, F = hp.n_ff;
+        const char* mats[6] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_up", "ffn_down"};
+        const int mrows[6] = {E_, E_, E_, E_, F, E_}, mK[6] = {E_, E_, E_, E_, E_, F};
+        for (int l = 0; l < hp.n_layer; ++l) {
+            const std::string b = "blk." + std::to_string(l) + ".";
+            BertIdx& x = bi[l];
+            for (int k = 0; k < 6; ++k) {
+                x.w[k] = bert_mat(b + mats[k] + ".weight", mrows[k], mK[k]);
+                x.b[k] = bert_vec(b + mats[k] + ".bias", mrows[k]);
+                weight_bytes += (long long)plan[x.w[k]].t->nbytes;
+            }
+            x.an = bert_vec(b + "attn_output_norm.weight", E_);
+            x.anb = bert_vec(b + "attn_output_norm.bias", E_);
+            x.on = bert_vec(b + "layer_output_norm.weight", E_);
+            x.onb = bert_vec(b + "layer_output_norm.bias", E_);
+        }
+    }
     for (int l = 0; l < hp.n_layer && gpt2; ++l) {   // llm_build_gpt2's tensors (LLM_ARCH_GPT2)
         const std::string b = "blk." + std::to_string(l) + ".";
         LayerIdx& x = li[l];
@@ -374,7 +437,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         x.d = add(b + "ffn_down.weight", true, 1);
         x.bd = add(b + "ffn_down.bias", true, 1);
     }
-    for (int l = 0; l < hp.n_layer && !gpt2; ++l) {
+    for (int l = 0; l < hp.n_layer && !gpt2 && !bert; ++l) {
         const std::string b = "blk." + std::to_string(l) + ".";
         LayerIdx& x = li[l];
         x.an = add(b + "attn_norm.weight", true, 1);
@@ -418,12 +481,12 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     for (const auto& pl : plan) {
         // bytes one decode step streams: an expert tensor contributes the n_expert_used experts
         // the router picks (build_moe_ffn reads only those), not all n_expert of them
-        if (pl.t->name != "token_embd.weight" && pl.t->name != "position_embd.weight")
+        if (!bert && pl.t->name != "token_embd.weight" && pl.t->name != "position_embd.weight")
             weight_bytes += pl.experts > 1 ? (long long)pl.t->nbytes / pl.experts * hp.n_expert_used
                                            : (long long)pl.t->nbytes;
         if (pl.t->type >= 0 && pl.t->type < 32) type_bytes[pl.t->type] += (long long)pl.t->nbytes;
     }
-    if (i_out < 0) weight_bytes += (long long)plan[i_te].t->nbytes;   // tied output head
+    if (i_out < 0 && !bert) weight_bytes += (long long)plan[i_te].t->nbytes;   // tied output head
 
     MI_HIP(hipSetDevice(device));
     MI_HIP(hipMalloc(&arena, arena_bytes));
@@ -479,13 +542,32 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     };
     tok_embd = qm(i_te);
     if (i_pe >= 0) pos_embd = qm(i_pe);
+    if (bert) {
+        auto f16p = [&](int idx) { return reinterpret_cast<const __half*>(arena + plan[idx].off[0]); };
+        tok_types = qm(i_tt);
+        embd_norm = f32p(i_en);
+        embd_norm_b = f32p(i_enb);
+        enc_layers.resize(hp.n_layer);
+        for (int l = 0; l < hp.n_layer; ++l) {
+            EncLayer& L = enc_layers[l];
+            const BertIdx& x = bi[l];
+            L.wq = f16p(x.w[0]); L.wk = f16p(x.w[1]); L.wv = f16p(x.w[2]);
+            L.wo = f16p(x.w[3]); L.up = f16p(x.w[4]); L.down = f16p(x.w[5]);
+            L.bq = f32p(x.b[0]); L.bk = f32p(x.b[1]); L.bv = f32p(x.b[2]);
+            L.bo = f32p(x.b[3]); L.bup = f32p(x.b[4]); L.bdown = f32p(x.b[5]);
+            L.attn_out_norm = f32p(x.an); L.attn_out_norm_b = f32p(x.anb);
+            L.layer_out_norm = f32p(x.on); L.layer_out_norm_b = f32p(x.onb);
+        }
+    }
     output_norm_b = f32p(i_onb);
-    output = i_out >= 0 ? qm(i_out) : qm(i_te);
-    if (!is_quant(output.type)) throw Error("output head must be a quantised tensor in this build");
+    if (!bert) {
+        output = i_out >= 0 ? qm(i_out) : qm(i_te);
+        if (!is_quant(output.type)) throw Error("output head must be a quantised tensor in this build");
+    }
     output_norm = f32p(i_on);
     rope_freqs = f32p(i_rf);
-    layers.resize(hp.n_layer);
-    for (int l = 0; l < hp.n_layer; ++l) {
+    layers.resize(bert ? 0 : hp.n_layer);
+    for (int l = 0; l < hp.n_layer && !bert; ++l) {
         Layer& L = layers[l];
         const LayerIdx& x = li[l];
         L.attn_norm = f32p(x.an);
@@ -527,7 +609,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             L.qkv_nk[g] = nk;
         }
     }
-    if (gpt2) {
+    if (gpt2 || bert) {
         const std::vector<unsigned short> t = gelu_table_host();
         MI_HIP(hipMalloc(&gelu_tab, t.size() * sizeof(unsigned short)));
         MI_HIP(hipMemcpy(gelu_tab, t.data(), t.size() * sizeof(unsigned short), hipMemcpyHostToDevice));

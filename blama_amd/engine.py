@@ -96,6 +96,7 @@ _SIGS = {
     "mi_ctx_rm_lora": (C.c_int32, [_P, _P]),
     "mi_ctx_clear_lora": (None, [_P]),
     "mi_model_pooling_type": (C.c_int32, [_P]),
+    "mi_model_causal_attn": (C.c_int32, [_P]),
     "mi_ctx_set_embeddings": (C.c_int32, [_P, C.c_int32, C.c_int32]),
     "mi_ctx_pooling": (C.c_int32, [_P]),
     "mi_embeddings": (C.POINTER(C.c_float), [_P, C.c_int32]),
@@ -123,6 +124,8 @@ _SIGS = {
     "mi_op_moe_group": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mi_op_moe_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, _P, C.c_int32, _P, _P]),
+    "mi_op_gemm_f16": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    "mi_op_attention_enc": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mi_op_moe_decode": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                      C.c_float, _P, _P, _P, _P, _P]),
 }
@@ -240,6 +243,19 @@ class Model:
     def pooling_type(self) -> int:
         """The GGUF's {arch}.pooling_type (llama_pooling_type), or -1 when it has none."""
         return int(lib().mi_model_pooling_type(self.h))
+
+    @property
+    def causal_attn(self) -> int:
+        """1: a causal decoder (llama, gpt2); 0: a bidirectional encoder (bert)."""
+        return int(lib().mi_model_causal_attn(self.h))
+
+    @property
+    def tokenizer(self) -> str:
+        """tokenizer.ggml.model of the GGUF ("llama", "gpt2", "bert")."""
+        n = lib().mi_model_tokenizer(self.h, None, 0)
+        b = C.create_string_buffer(n + 1)
+        lib().mi_model_tokenizer(self.h, b, n + 1)
+        return b.raw[:n].decode()
 
 
 class Lora:
@@ -423,7 +439,8 @@ class Context:
         return lib().mi_prof_ffn_bytes(self.h)
 
     def decode_path(self) -> int:
-        """1: decode steps within 512 cells run on the streaming GEMV (dgemv.hip); 0: gemv_kernel."""
+        """1: decode steps within 512 cells run on the streaming GEMV (dgemv.hip); 0: gemv_kernel;
+        2: an encoder context (bert)."""
         return int(lib().mi_decode_path(self.h))
 
     @property
@@ -632,3 +649,35 @@ def op_moe_decode(type_: int, gate: np.ndarray, up: np.ndarray, down: np.ndarray
                                   _ptr(norm_w), eps, _ptr(sel), _ptr(selw), None if a is None else _ptr(a), _ptr(h),
                                   _ptr(x_out)), "op_moe_decode")
     return h, x_out
+
+
+GEMM_F16_NONE, GEMM_F16_BIAS, GEMM_F16_GELU, GEMM_F16_RESID = 0, 1, 2, 3
+
+
+def op_gemm_f16(w16: np.ndarray, x: np.ndarray, bias=None, resid=None, epilogue: int = GEMM_F16_NONE,
+                device: int = 0) -> np.ndarray:
+    """mi_op_gemm_f16: w16 (rows, K) float16, x (ntok, K) f32 -> (ntok, rows) f32 after the epilogue
+    (0 none, 1 + bias, 2 gelu(. + bias), 3 (. + bias) + resid)."""
+    w16 = np.ascontiguousarray(w16, np.float16)
+    x = np.ascontiguousarray(x, np.float32)
+    rows, K = w16.shape
+    ntok = x.shape[0]
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    r = None if resid is None else np.ascontiguousarray(resid, np.float32)
+    y = np.empty((ntok, rows), np.float32)
+    _check(lib().mi_op_gemm_f16(device, _ptr(w16), rows, K, ntok, _ptr(x), None if b is None else _ptr(b),
+                                None if r is None else _ptr(r), epilogue, _ptr(y)), "op_gemm_f16")
+    return y
+
+
+def op_attention_enc(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, device: int = 0) -> np.ndarray:
+    """mi_op_attention_enc: q (ntok, n_head, hd) f32, k16 / v16 (ntok, n_head * hd) f16 -> (ntok, n_head,
+    hd) f32: every token over all ntok tokens."""
+    q = np.ascontiguousarray(q, np.float32)
+    ntok, n_head, hd = q.shape
+    k16 = np.ascontiguousarray(k16, np.float16)
+    v16 = np.ascontiguousarray(v16, np.float16)
+    out = np.empty((ntok, n_head, hd), np.float32)
+    _check(lib().mi_op_attention_enc(device, n_head, hd, ntok, _ptr(q), _ptr(k16), _ptr(v16), _ptr(out)),
+           "op_attention_enc")
+    return out

@@ -1,6 +1,7 @@
 // bl::llama host surface on the MI355X engine (see llama.hpp for the mirrored reference files).
 #include "llama.hpp"
 #include "unicode_cats.hpp"
+#include "unicode_wpm.hpp"
 #include <array>
 
 #include "mi_engine.h"
@@ -127,6 +128,78 @@ bool is_S(uint32_t c) {   // \s: Unicode White_Space
 }
 bool is_nl(uint32_t c) { return c == '\r' || c == '\n'; }
 uint32_t lower_ascii(uint32_t c) { return (c >= 'A' && c <= 'Z') ? c + 32 : c; }
+
+// ---- WordPiece (llm_tokenizer_wpm): the generated tables of unicode_wpm.hpp ----
+uint32_t wpm_lower(uint32_t c) {
+    const auto* e = std::end(unicode::kLower);
+    const auto* it = std::lower_bound(std::begin(unicode::kLower), e, c, [](const unicode::CpMap& m, uint32_t v) { return m.from < v; });
+    return it != e && it->from == c ? it->to : c;
+}
+uint32_t wpm_ccc(uint32_t c) {
+    const auto* e = std::end(unicode::kCcc);
+    const auto* it = std::lower_bound(std::begin(unicode::kCcc), e, c, [](const unicode::CccRange& r, uint32_t v) { return r.hi < v; });
+    return it != e && it->lo <= c ? it->ccc : 0;
+}
+// Canonical decomposition (NFD) of a code point sequence: every code point replaced by its full
+// decomposition (Hangul syllables by arithmetic), then each run of combining marks put in the
+// order of their combining classes (stable).
+std::vector<uint32_t> wpm_nfd(const std::vector<uint32_t>& in) {
+    std::vector<uint32_t> o;
+    o.reserve(in.size());
+    for (uint32_t c : in) {
+        if (c >= 0xAC00 && c <= 0xD7A3) {
+            const uint32_t s = c - 0xAC00, t = s % 28;
+            o.push_back(0x1100 + s / 588);
+            o.push_back(0x1161 + (s % 588) / 28);
+            if (t) o.push_back(0x11A7 + t);
+            continue;
+        }
+        const auto* e = std::end(unicode::kNfd);
+        const auto* it = c < 0xC0 ? e : std::lower_bound(std::begin(unicode::kNfd), e, c, [](const unicode::NfdEntry& n, uint32_t v) { return n.cp < v; });
+        if (it != e && it->cp == c) o.insert(o.end(), unicode::kNfdData + it->off, unicode::kNfdData + it->off + it->len);
+        else o.push_back(c);
+    }
+    for (size_t i = 0; i < o.size();) {
+        if (wpm_ccc(o[i]) == 0) { ++i; continue; }
+        size_t j = i;
+        while (j < o.size() && wpm_ccc(o[j]) != 0) ++j;
+        std::stable_sort(o.begin() + i, o.begin() + j, [](uint32_t a, uint32_t b) { return wpm_ccc(a) < wpm_ccc(b); });
+        i = j;
+    }
+    return o;
+}
+bool wpm_is_cjk(uint32_t c) {   // llm_tokenizer_wpm_session::is_chinese_char
+    return (c >= 0x4E00 && c <= 0x9FFF) || (c >= 0x3400 && c <= 0x4DBF) || (c >= 0x20000 && c <= 0x2A6DF) ||
+           (c >= 0x2A700 && c <= 0x2B73F) || (c >= 0x2B740 && c <= 0x2B81F) || (c >= 0x2B920 && c <= 0x2CEAF) ||
+           (c >= 0xF900 && c <= 0xFAFF) || (c >= 0x2F800 && c <= 0x2FA1F);
+}
+// llm_tokenizer_wpm_session::preprocess: NFD, then white space ends a word; 0, U+FFFD and control
+// characters (Cc, Cf) are dropped; the rest is lowercased; punctuation, an ASCII symbol or a CJK
+// ideograph is a word of its own.
+std::vector<std::string> wpm_words(std::string_view text) {
+    std::vector<uint32_t> cp;
+    std::vector<size_t> off;
+    cps_of(text, cp, off);
+    std::vector<std::string> words(1);
+    for (uint32_t c : wpm_nfd(cp)) {
+        if (in_ranges(unicode::kWhite, c)) {
+            if (!words.back().empty()) words.emplace_back();
+            continue;
+        }
+        if (c == 0 || c == 0xFFFD || in_ranges(unicode::kControl, c)) continue;
+        std::string s;
+        put_utf8(s, wpm_lower(c));
+        if (in_ranges(unicode::kPunct, c) || (c < 0x7F && in_ranges(unicode::kSymbol, c)) || wpm_is_cjk(c)) {
+            if (!words.back().empty()) words.emplace_back();
+            words.back() = s;
+            words.emplace_back();
+        } else {
+            words.back() += s;
+        }
+    }
+    if (words.back().empty()) words.pop_back();
+    return words;
+}
 
 // Length (code points) of the pre-token starting at i: the first alternative of the regex that
 // matches there, with the regex's greedy / backtracking semantics (unicode.cpp's hand-written
@@ -312,6 +385,16 @@ void Vocab::load() {
     mi_model_tokenizer(m, tk, sizeof tk);
     m_spm = std::string(tk) == "llama";
     m_bpe = std::string(tk) == "gpt2";
+    m_wpm = std::string(tk) == "bert";
+    if (m_wpm) {   // llama_vocab::impl::load, LLAMA_VOCAB_TYPE_WPM: the defaults are BERT's ids
+        auto id_or = [&](Token id, Token def) { return id >= 0 ? id : (def < n ? def : -1); };
+        m_cls = id_or(meta_id({"tokenizer.ggml.cls_token_id", "tokenizer.ggml.bos_token_id"}), 101);
+        m_sep = id_or(meta_id({"tokenizer.ggml.seperator_token_id"}), 102);
+        m_unk = id_or(meta_id({"tokenizer.ggml.unknown_token_id"}), 100);
+        m_pad = id_or(meta_id({"tokenizer.ggml.padding_token_id"}), 0);
+        if (m_unk < 0) BL_THROW("tokenizer: the WordPiece vocabulary has no unknown token");
+        for (const std::string& t : m_text) m_maxTokenLen = std::max(m_maxTokenLen, t.size());
+    }
     if (m_bpe) {
         // llama_vocab::impl::load: tokenizer.ggml.pre picks the pre-tokenizer; the Llama-3 family
         // also takes a whole pre-token from the vocabulary before merging (ignore_merges)
@@ -360,6 +443,8 @@ std::string Vocab::tokenToString(Token token, bool special) const {
         }
         return o;
     }
+    if (m_wpm && m_type[token] == kTypeNormal)   // a word start's U+2581 is its space; a continuation has none
+        return t.rfind(kSpace, 0) == 0 ? " " + t.substr(kSpace.size()) : t;
     switch (m_type[token]) {
     case kTypeNormal: return unescape_whitespace(t);
     case kTypeUnknown: return "\xe2\x96\x85";   // U+2585, what llama_token_to_piece prints
@@ -429,10 +514,42 @@ void Vocab::bpeWord(std::string_view word, std::vector<Token>& out) const {
     }
 }
 
+// One raw fragment on a WordPiece vocabulary (llm_tokenizer_wpm_session::tokenize): each word, with
+// U+2581 in front, is cut greedily into the longest vocabulary entries from the left -- the window
+// at byte i is at most max-token-length + 1 bytes and shrinks from its long end; a word with a
+// position that nothing matches becomes the one unknown token, nothing of it kept.
+void Vocab::wpmFragment(std::string_view text, std::vector<Token>& out) const {
+    for (const std::string& word : wpm_words(text)) {
+        const std::string w = kSpace + word;
+        const size_t n = w.size(), first = out.size();
+        for (size_t i = 0; i < n;) {
+            size_t j = std::min(n, i + m_maxTokenLen + 1);
+            for (; j > i; --j) {
+                auto it = m_index.find(w.substr(i, j - i));
+                if (it != m_index.end()) {
+                    out.push_back(it->second);
+                    break;
+                }
+            }
+            if (j == i) {   // no entry starts here: discard the word's pieces
+                out.resize(first);
+                break;
+            }
+            i = j;
+        }
+        if (out.size() == first) out.push_back(m_unk);
+    }
+}
+
 std::vector<Token> Vocab::tokenize(std::string_view text, bool addSpecial, bool parseSpecial) const {
-    if (!m_spm && !m_bpe) BL_THROW("tokenizer: only SentencePiece (llama) and byte-level BPE (gpt2) vocabularies are served");
+    if (!m_spm && !m_bpe && !m_wpm)
+        BL_THROW("tokenizer: only SentencePiece (llama), byte-level BPE (gpt2) and WordPiece (bert) vocabularies are served");
     std::vector<Token> out;
-    if (addSpecial && m_model.shouldAddBosToken() && m_bos >= 0) out.push_back(m_bos);
+    if (m_wpm) {
+        if (addSpecial && m_cls >= 0) out.push_back(m_cls);
+    } else if (addSpecial && m_model.shouldAddBosToken() && m_bos >= 0) {
+        out.push_back(m_bos);
+    }
 
     // 1. split the text at special-token texts (control tokens only when parseSpecial), longest first
     struct Frag { bool tok; Token id; std::string_view s; };
@@ -461,6 +578,14 @@ std::vector<Token> Vocab::tokenize(std::string_view text, bool addSpecial, bool 
         frags.swap(next);
     }
 
+    if (m_wpm) {   // 2''. WordPiece over each raw fragment, [SEP] at the end
+        for (const Frag& f : frags) {
+            if (f.tok) out.push_back(f.id);
+            else wpmFragment(f.s, out);
+        }
+        if (addSpecial && m_sep >= 0) out.push_back(m_sep);
+        return out;
+    }
     if (m_bpe) {   // 2'. byte-level BPE: pre-tokenize each raw fragment, then merge each pre-token
         std::vector<uint32_t> cp;
         std::vector<size_t> off;

@@ -67,7 +67,9 @@ public:
     explicit Vocab(const Model& model);
     // Tokenisation of `text` (llama_tokenize): SentencePiece (llm_tokenizer_spm) for "llama"
     // vocabularies, byte-level BPE with the GPT-2 or Llama-3 pre-tokenizer (llm_tokenizer_bpe)
-    // for "gpt2" ones; addSpecial prepends BOS when the model asks for it, parseSpecial matches
+    // for "gpt2" ones, WordPiece (llm_tokenizer_wpm: NFD, lowercase, punctuation / CJK splits, greedy
+    // longest match, a word with an unmatched tail -> [UNK]) for "bert" ones, where addSpecial puts
+    // [CLS] in front and [SEP] at the end; addSpecial prepends BOS when the model asks for it, parseSpecial matches
     // control-token texts (e.g. "<s>", "<|begin_of_text|>") as single tokens.
     std::vector<Token> tokenize(std::string_view text, bool addSpecial, bool parseSpecial) const;
     Token decoderStartToken() const noexcept;
@@ -79,6 +81,11 @@ public:
     // end-of-turn token (llama_vocab::token_eot): the GGUF's eot id, else a known end-of-turn
     // text found in the vocabulary, else -1 (LLAMA_TOKEN_NULL)
     Token eot() const noexcept { return m_eot; }
+    // WordPiece vocabularies: [CLS], [SEP], [UNK], [PAD] (-1 on the others)
+    Token cls() const noexcept { return m_cls; }
+    Token sep() const noexcept { return m_sep; }
+    Token unk() const noexcept { return m_wpm ? m_unk : -1; }
+    Token pad() const noexcept { return m_pad; }
     // fill-in-the-middle tokens (llama_vocab_fim_pre/suf/mid, used by Session::pushPrompt for a
     // postfix, Session.cpp:142-159): tokenizer.ggml.fim_{pre,suf,mid}_token_id (or the older
     // prefix/suffix/middle keys), else a known FIM text in the vocabulary, else -1
@@ -102,6 +109,12 @@ private:
     bool m_ignoreMerges = false;             // Llama-3: a pre-token found whole in the vocab is one token
     std::unordered_map<std::string, int> m_rank;   // "left right" -> merge rank
     void bpeWord(std::string_view word, std::vector<Token>& out) const;
+    // WordPiece (tokenizer.ggml.model "bert"): tokenizer.ggml.cls_token_id (else bos_token_id, else
+    // 101), seperator_token_id (sic; else 102), unknown_token_id (else 100), padding_token_id (else 0)
+    bool m_wpm = false;
+    Token m_cls = -1, m_sep = -1, m_pad = -1;
+    size_t m_maxTokenLen = 0;                // bytes of the longest vocabulary entry
+    void wpmFragment(std::string_view text, std::vector<Token>& out) const;
     bool m_loaded = false;
     friend class Model;
 };
@@ -367,8 +380,9 @@ private:
 
 // The embeddings instance (InstanceEmbedding.hpp:22-49, InstanceEmbedding.cpp): a context of its own
 // in embeddings mode (llama_context_params.embeddings = true) with the pooling type left
-// unspecified, i.e. the model's {arch}.pooling_type or NONE.  Decoder models only; encoder models
-// (BERT) are not served.
+// unspecified, i.e. the model's {arch}.pooling_type or NONE.  Decoder models (LLaMA, Mixtral, GPT-2)
+// and BERT-architecture encoder models (the bge family, F16); on an encoder model the context holds
+// no KV cache and every call is one stateless pass (mi_engine.h, the embeddings block).
 class InstanceEmbedding {
 public:
     struct InitParams {

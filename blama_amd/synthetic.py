@@ -658,3 +658,165 @@ def write_lora_gguf(dst, cfg: LlamaConfig, targets=LORA_TARGETS, rank: int = 4, 
         with open(dst, "wb") as f:
             f.write(img.tobytes())
     return img
+
+
+# ---- BERT encoder models (llm_build_bert: the bge family's shape, F16) ----
+
+@dataclass(frozen=True)
+class BertConfig:
+    name: str
+    n_vocab: int
+    n_embd: int
+    n_layer: int
+    n_head: int
+    n_ff: int
+    n_ctx_train: int
+    eps: float = 1e-12
+    pooling_type: int = -1            # >= 0: written as bert.pooling_type (bge: 2, CLS)
+    n_token_types: int = 2
+
+    @property
+    def head_dim(self):
+        return self.n_embd // self.n_head
+
+
+BERT_CONFIGS = {
+    # bge-small-en-v1.5's widths (384 / 12 heads of 32 / 1536) at 2 layers, CLS pooling as bge
+    "bert-s": BertConfig("bert-s", 512, 384, 2, 12, 1536, 128, pooling_type=2),
+    # head_dim 64, an n_ff that is no multiple of 128 (a partial workgroup of row tiles), no pooling key
+    "bert-w": BertConfig("bert-w", 300, 128, 3, 2, 320, 64),
+}
+
+BERT_SPECIALS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]")
+
+
+def bert_vocab(n_vocab: int, words=()) -> dict:
+    """A WordPiece vocabulary as convert_hf_to_gguf.py writes BERT's: [PAD] [UNK] [CLS] [SEP], then
+    word starts (U+2581 + piece) and bare continuations -- `words` first (a "##x" entry is the
+    continuation x, anything else a word start), then punctuation, letters, digits and syllables
+    until n_vocab entries."""
+    toks = list(BERT_SPECIALS)
+    seen = set(toks)
+
+    def put(t):
+        if t not in seen and len(toks) < n_vocab:
+            seen.add(t)
+            toks.append(t)
+
+    for w in words:
+        put(w[2:] if w.startswith("##") else "▁" + w)
+    for c in ".,!?-'\"()$+":
+        put("▁" + c)
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    for c in letters + "0123456789":
+        put("▁" + c)
+        put(c)
+    put("▁中")
+    put("▁文")
+    cons, vows = "bcdfghjklmnprstvw", "aeiou"
+    for a in cons:
+        for b in vows:
+            put("▁" + a + b)
+            put(a + b)
+    for a in cons:
+        for b in vows:
+            for c in "nrst":
+                put("▁" + a + b + c)
+                put(a + b + c)
+    assert len(toks) == n_vocab, (len(toks), n_vocab)
+    types = [3] * len(BERT_SPECIALS) + [1] * (n_vocab - len(BERT_SPECIALS))
+    return dict(tokens=toks, types=types, pad=0, unk=1, cls=2, sep=3)
+
+
+def bert_tensor_shapes(cfg: BertConfig) -> dict:
+    d, f = cfg.n_embd, cfg.n_ff
+    s = {"token_embd.weight": (d, cfg.n_vocab), "token_types.weight": (d, cfg.n_token_types),
+         "position_embd.weight": (d, cfg.n_ctx_train), "token_embd_norm.weight": (d,), "token_embd_norm.bias": (d,)}
+    for i in range(cfg.n_layer):
+        p = f"blk.{i}."
+        for n in ("attn_q", "attn_k", "attn_v", "attn_output"):
+            s[p + n + ".weight"] = (d, d)
+            s[p + n + ".bias"] = (d,)
+        s[p + "attn_output_norm.weight"] = (d,)
+        s[p + "attn_output_norm.bias"] = (d,)
+        s[p + "ffn_up.weight"] = (d, f)
+        s[p + "ffn_up.bias"] = (f,)
+        s[p + "ffn_down.weight"] = (f, d)
+        s[p + "ffn_down.bias"] = (d,)
+        s[p + "layer_output_norm.weight"] = (d,)
+        s[p + "layer_output_norm.bias"] = (d,)
+    return s
+
+
+def _bert_std(cfg: BertConfig, name: str) -> float:
+    """Scales that keep every LayerNorm input well away from zero variance and no softmax one-hot:
+    the LayerNorm'd stream has unit variance, so q and k rows get std 0.6 (scores of std 0.36 after
+    the 1 / sqrt(head_dim) scale, as the attention op tests draw them), v, attn_output and ffn_up
+    unit-variance outputs, ffn_down an output of the size of its GELU input."""
+    d, f = cfg.n_embd, cfg.n_ff
+    if name == "token_embd.weight":
+        return 0.5
+    if name == "token_types.weight":
+        return 0.1
+    if name == "position_embd.weight":
+        return 0.2
+    if name.endswith(("attn_q.weight", "attn_k.weight")):
+        return 0.6 / np.sqrt(d)
+    if name.endswith("ffn_down.weight"):
+        return 1.0 / np.sqrt(f)
+    return 1.0 / np.sqrt(d)
+
+
+def build_bert_gguf(cfg: BertConfig, seed: int = 0, vocab: dict | None = None, header_only: bool = False,
+                    types: dict | None = None, drop=(), causal=None) -> np.ndarray:
+    """A synthetic BERT encoder GGUF (general.architecture "bert", llama.cpp b5187's keys and tensor
+    names): F16 matrices and tables, F32 biases and LayerNorms, the WordPiece vocabulary of
+    bert_vocab() unless one is given.  types: {tensor name: ggml type} overrides (F32 only, for the
+    loader's refusals); drop: tensor names left out; causal: written as bert.attention.causal."""
+    vocab = bert_vocab(cfg.n_vocab) if vocab is None else vocab
+    assert len(vocab["tokens"]) == cfg.n_vocab
+    w = gguf.GGUFWriter()
+    w.add_str("general.architecture", "bert")
+    w.add_str("general.name", f"synthetic {cfg.name} F16")
+    w.add_u32("general.file_type", 1)
+    w.add_u32("bert.context_length", cfg.n_ctx_train)
+    w.add_u32("bert.embedding_length", cfg.n_embd)
+    w.add_u32("bert.block_count", cfg.n_layer)
+    w.add_u32("bert.feed_forward_length", cfg.n_ff)
+    w.add_u32("bert.attention.head_count", cfg.n_head)
+    w.add_f32("bert.attention.layer_norm_epsilon", cfg.eps)
+    if causal is not None:
+        w.add_bool("bert.attention.causal", causal)
+    if cfg.pooling_type >= 0:
+        w.add_u32("bert.pooling_type", cfg.pooling_type)
+    w.add_str("tokenizer.ggml.model", "bert")
+    w.add_array("tokenizer.ggml.tokens", gguf.T_STRING, vocab["tokens"])
+    w.add_array("tokenizer.ggml.token_type", gguf.T_INT32, vocab["types"])
+    w.add_u32("tokenizer.ggml.token_type_count", cfg.n_token_types)
+    w.add_u32("tokenizer.ggml.cls_token_id", vocab["cls"])
+    w.add_u32("tokenizer.ggml.seperator_token_id", vocab["sep"])
+    w.add_u32("tokenizer.ggml.unknown_token_id", vocab["unk"])
+    w.add_u32("tokenizer.ggml.padding_token_id", vocab["pad"])
+    shapes = bert_tensor_shapes(cfg)
+    ttypes = {n: (F16 if len(s) == 2 else F32) for n, s in shapes.items()}
+    ttypes.update(types or {})
+    for name, shape in shapes.items():
+        if name not in drop:
+            w.add_tensor(name, ttypes[name], shape)
+    if header_only:
+        return np.frombuffer(w.header_bytes()[0], np.uint8).copy()
+
+    def fill(name, t, shape, view):
+        rng = _rng(seed, name)
+        n = int(np.prod(shape))
+        if name.endswith("norm.weight"):
+            v = rng.uniform(0.8, 1.2, n)
+        elif name.endswith("norm.bias"):
+            v = rng.standard_normal(n) * 0.05
+        elif name.endswith(".bias"):
+            v = rng.standard_normal(n) * 0.05
+        else:
+            v = rng.standard_normal(n) * _bert_std(cfg, name)
+        view[:] = v.astype(np.float16 if t == F16 else np.float32).view(np.uint8)
+
+    return w.to_bytes(fill=fill)

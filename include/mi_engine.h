@@ -197,7 +197,20 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * (llama_pooling_type) reduces the rows of the tokens of ONE mi_decode call (n <= n_batch) to one
  * row: MEAN = sum_t row_t * (1.0f / n) in f32 in token order, CLS = the first token's row, LAST =
  * the last token's; NONE keeps a row per output token.  RANK needs a classification head the engine
- * does not load and is refused.  Encoder models (BERT) are not served. */
+ * does not load and is refused.
+ *
+ * Encoder models (general.architecture "bert": BERT-architecture F16 models such as the bge family,
+ * head_dim 32 or 64; llm_build_bert).  A context on one holds no KV cache and is ALWAYS in
+ * embeddings mode, created with the model's pooling type (NONE when the key is absent).  Every
+ * mi_decode call is one stateless bidirectional pass: its n tokens take positions 0 .. n - 1, use
+ * token type 0 and attend to each other only; n <= min(n_batch, 512, n_ctx_train), more is refused
+ * (< 0, with a message), as are token ids outside the vocabulary.  out_mode, pooling and the rows of
+ * mi_embeddings are as above.  On such a context: mi_ctx_set_embeddings(ctx, 0, ..) < 0 (no output
+ * head); mi_kv_pos_max is -1 and mi_kv_n_cells 0 always; mi_kv_clear is a no-op; mi_kv_seq_* and
+ * mi_ctx_apply_cvec < 0; mi_state_size / mi_state_get / mi_state_set return 0; mi_logits NULL,
+ * mi_topk / mi_gather / mi_gather_rows < 0; mi_lora_load on the model is refused.  Not served:
+ * quantised or F32 BERT matrices, the nomic / jina variants (RoPE, gated FFN, attention-norm
+ * tensors), RANK pooling, token types other than 0, several sequences in one call. */
 #define MI_POOLING_UNSPECIFIED (-1)
 #define MI_POOLING_NONE 0
 #define MI_POOLING_MEAN 1
@@ -207,6 +220,9 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
 /* The model's {arch}.pooling_type key (read for every architecture), or -1 when the GGUF has none
  * or the model is NULL. */
 int32_t mi_model_pooling_type(const mi_model* model);
+/* llama_model / hparams.causal_attn: 1 for llama and gpt2 (a causal decoder with a KV cache), 0 for
+ * bert (a bidirectional encoder), -1 for NULL. */
+int32_t mi_model_causal_attn(const mi_model* model);
 /* llama_set_embeddings + pooling_type (InstanceEmbedding.cpp:24-32).  on != 0: every mi_decode from
  * the next one ends in the embedding rows and runs no output head -- mi_logits then returns NULL and
  * mi_topk / mi_gather / mi_gather_rows < 0, mi_last_error() saying that the context is in
@@ -239,7 +255,8 @@ int64_t mi_prof_ffn_bytes(const mi_ctx* ctx);
 int64_t mi_prof_bytes(const mi_ctx* ctx);
 /* Diagnostics: the form the context's decode steps take: 1 the streaming GEMV
  * launches (dgemv.hip; MoE: the attention half, the experts on gemv_kernel), 0 the gemv_kernel graph
- * (GPT-2); -1 for a null context. */
+ * (GPT-2), 2 an encoder context (bert: no decode step, one stateless pass per call on the kernels
+ * of enc.hip); -1 for a null context. */
 int32_t mi_decode_path(const mi_ctx* ctx);
 /* Diagnostics: copies the per-workgroup s_memrealtime stamps (100 MHz) of the
  * first n_launch launches of the last decode step, [launch][512][8] uint64, to
@@ -322,6 +339,17 @@ int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* r
 int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const void* up, const void* down,
                          int32_t n_expert, int32_t n_embd, int32_t n_ff, const float* x, const float* norm_w, float eps,
                          const int32_t* sel, const float* selw, const float* addend, float* h_out, float* x_out);
+/* The encoder pass's dense F16 GEMM (enc.hip, v_mfma_f32_32x32x16_f16): y[t][r] = sum_k f16(x[t][k]) *
+ * w[r][k] in f32, then the epilogue -- 0 none, 1 + bias[r], 2 gelu(. + bias[r]) by ggml's f16 table,
+ * 3 (. + bias[r]) + resid[t][r].  w: [rows][K] f16 bits, x: [ntok][K], resid / y: [ntok][rows];
+ * rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 512. */
+int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int32_t K, int32_t ntok,
+                       const float* x, const float* bias, const float* resid, int32_t epilogue, float* y);
+/* The encoder pass's bidirectional attention (enc.hip): every token over all ntok <= 512 tokens, no
+ * mask, scale 1 / sqrtf(head_dim); q / out: f32 [ntok][n_head * head_dim], k / v: f16 bits of the same
+ * shape; head_dim 32 or 64. */
+int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok,
+                            const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);
