@@ -48,6 +48,28 @@ GemmParams Ctx::gemm_base(int l, int nt, bool vdot4) const {
     return p;
 }
 
+GemmParams mmq32_params(const QMat& A, const QMat* B, int ntok, const int* tokpos, float* out, int out_stride,
+                        const int* grp, int grp_max) {
+    GemmParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.A = A;
+    if (B) p.B = *B;
+    p.pair = B ? PAIR_AB : PAIR_ADJ;
+    p.epi = B ? EPI_SWIGLU : EPI_STORE;
+    p.K = A.K;
+    p.ntok = ntok;
+    p.tokpos = tokpos;
+    p.out = out;
+    p.out_stride = out_stride;
+    if (grp) {
+        p.grp = grp;
+        p.grp_n = A.n_exp;
+        p.grp_max = grp_max;
+        p.grp_stride = A.sw_expert_stride;
+    }
+    return p;
+}
+
 // Q, K or V projection (+ RoPE, KV append) into qb
 GemmParams Ctx::bqkv_params(int l, int nt, bool vdot4, int i, const float* pre) const {
     const Layer& L = m->layers[l];
@@ -117,7 +139,7 @@ AttnParams Ctx::battn_params(int l) const {
 Ctx::QkvGroups Ctx::qkv_type_groups(const Layer& L) {
     const QMat* mats[3] = {&L.wq, &L.wk, &L.wv};
     QkvGroups G{};
-    for (const QMat* q : mats) G.fmt |= q->type == T_Q8_0 ? 2 : 1;
+    G.fmt = act_fmt({L.wq.type, L.wk.type, L.wv.type});
     for (int i = 0; i < 3; ++i) {   // (7B: Q/K/V, or Q/K plus a Q6_K V)
         bool first = true;
         for (int j = 0; j < i; ++j) first = first && mats[j]->type != mats[i]->type;
@@ -216,38 +238,14 @@ void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
     const HParams& hp = m->hp;
     const Layer& L = m->layers[l];
     const int cap = moe_route(l, nt, pend);
-    GemmParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.ntok = cap;
-    p.tokpos = tokpos_b;
-    p.grp = moe_grp;
-    p.grp_n = hp.n_expert;
-    p.grp_max = nt;
     // gate/up + SwiGLU: rms_norm(x) * ffn_norm of each row's token
     const ActQ8 act = moe_act(hp.n_embd, cap, L.gate.type == T_Q8_0);
     launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
-    p.A = L.gate;
-    p.B = L.up;
-    p.pair = PAIR_AB;
-    p.epi = EPI_SWIGLU;
-    p.K = hp.n_embd;
-    p.out = hb;
-    p.out_stride = hp.n_ff;
-    p.grp_stride = L.gate.sw_expert_stride;
-    launch_mmq32(p, act, ub_rope, stream);
+    launch_mmq32(mmq32_params(L.gate, &L.up, cap, tokpos_b, hb, hp.n_ff, moe_grp, nt), act, ub_rope, stream);
     // down: every row of the FFN output, stored (weighted and summed by the combine)
     const ActQ8 a2 = moe_act(hp.n_ff, cap, L.down.type == T_Q8_0);
     launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel);
-    GemmParams d = p;
-    d.A = L.down;
-    std::memset(&d.B, 0, sizeof(d.B));
-    d.pair = PAIR_ADJ;
-    d.epi = EPI_STORE;
-    d.K = hp.n_ff;
-    d.out = yb;
-    d.out_stride = hp.n_embd;
-    d.grp_stride = L.down.sw_expert_stride;
-    launch_mmq32(d, a2, ub_rope, stream);
+    launch_mmq32(mmq32_params(L.down, nullptr, cap, tokpos_b, yb, hp.n_embd, moe_grp, nt), a2, ub_rope, stream);
     launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
 }
 

@@ -68,6 +68,9 @@ struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 
 void set_last_error(const std::string& s);
 const char* last_error();
+// closes the try block of an extern "C" entry point: the error is kept for mi_last_error()
+#define MI_TRY(fail) catch (const std::exception& e) { ::mi::set_last_error(e.what()); return fail; } \
+                     catch (...) { ::mi::set_last_error("unknown error"); return fail; }
 
 #define MI_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     throw ::mi::Error(std::string("HIP error ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + std::to_string(__LINE__)); } while (0)

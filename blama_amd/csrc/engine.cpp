@@ -24,8 +24,6 @@ namespace mi {
 
 // =============================================================== context ===
 namespace {
-std::vector<int> g_attr_done(64, 0);
-
 struct DevChain {
     std::mutex mu;
     std::atomic<int> nctx{0};  // live contexts on the device (attention co-residency budget)
@@ -38,12 +36,6 @@ DevChain& dev_chain(int device) {
     if (!c) c.reset(new DevChain());
     return *c;
 }
-// activation formats a set of matrices reads: bit 0 Q8_K (k-quants), bit 1 Q8_0
-int act_fmt(std::initializer_list<int> types) {
-    int f = 0;
-    for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
-    return f;
-}
 const char* const kEmbdMode = "the context is in embeddings mode: no logits (mi_ctx_set_embeddings)";
 // unspecified pooling: the model's {arch}.pooling_type when it names a type served here, else NONE
 int model_pooling(const HParams& hp) {
@@ -51,6 +43,25 @@ int model_pooling(const HParams& hp) {
 }
 }  // namespace
 int dev_chain_contexts(int device) { return dev_chain(device).nctx.load(); }
+
+int act_fmt(std::initializer_list<int> types) {
+    int f = 0;
+    for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
+    return f;
+}
+
+void ensure_kernel_attributes(int device) {
+    static std::vector<int> done(64, 0);
+    if (device >= 0 && device < (int)done.size() && !done[device]) {
+        init_kernel_attributes();
+        done[device] = 1;
+    }
+}
+
+int mmqs_token_limit() {
+    const char* e = getenv("MI_MMQS_MAX");
+    return e ? std::min(MMQS_MAX, std::max(0, atoi(e))) : MMQS_MAX;
+}
 
 GemvSeg seg_of(const QMat& A, int pair, int epi, float* out) {
     GemvSeg g;
@@ -62,6 +73,33 @@ GemvSeg seg_of(const QMat& A, int pair, int epi, float* out) {
     g.expA = g.expB = -1;
     g.out = out;
     return g;
+}
+
+void moe_gate_up_segs(GemvParams& p, const QMat& gate, const QMat& up, const int* sel, const float* selw, float* h,
+                      float* h2) {
+    p.sel = sel;   // expert ids/weights: only MoE launches wait for them
+    p.selw = selw;
+    p.nseg = 2;
+    for (int k = 0; k < 2; ++k) {
+        p.seg[k] = seg_of(gate, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
+        p.seg[k].B = up;
+        p.seg[k].expA = p.seg[k].expB = k;
+    }
+}
+
+void moe_down_seg(GemvParams& p, const QMat& down, const int* sel, const float* selw, const float* h2, float* x,
+                  const float* addend) {
+    p.sel = sel;
+    p.selw = selw;
+    p.nslots = 2;
+    p.x[1] = h2;
+    p.nseg = 1;
+    p.seg[0] = seg_of(down, PAIR_AB, EPI_MOE_DOWN, x);
+    p.seg[0].expA = 0;
+    p.seg[0].expB = 1;
+    p.seg[0].actB = 1;
+    p.seg[0].resid = x;
+    p.seg[0].addend = addend;
 }
 
 // ---- CtxMem ----
@@ -121,10 +159,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
     const HParams& hp = m->hp;
     kv_dim = hp.n_head_kv * hp.head_dim;
     pooling = model_pooling(hp);
-    if (device < (int)g_attr_done.size() && !g_attr_done[device]) {
-        init_kernel_attributes();
-        g_attr_done[device] = 1;
-    }
+    ensure_kernel_attributes(device);
     stream = mem.stream();
     if (hp.arch == ARCH_BERT) {   // an encoder context: no KV cache, no decode step (enc.cpp)
         enc_init();
@@ -211,7 +246,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
             ub_rope = mem.dev<float2>((size_t)UB_MAX * std::max(1, hp.n_rot / 2));
             // split-K partials of the residual GEMMs (WO, FFN down) of dense models
             if (mmq2_active()) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
-            mmqs_max = getenv("MI_MMQS_MAX") ? std::min(MMQS_MAX, std::max(0, atoi(getenv("MI_MMQS_MAX")))) : MMQS_MAX;
+            mmqs_max = mmqs_token_limit();
             // MoE: short batches when every expert matrix has the grouped form (k-quants)
             moe_short = hp.n_expert > 0;
             for (const Layer& L : m->layers)
@@ -455,21 +490,17 @@ GemvParams Ctx::gate_up_params(int l, ActSrc src) const {
         p.seg[0].bias = L.bup;
         return p;
     }
-    const bool moe = hp.n_expert > 0;
-    if (moe) {   // expert ids/weights: only MoE launches wait for them
-        p.sel = sel;
-        p.selw = selw;
+    if (hp.n_expert > 0) {
+        moe_gate_up_segs(p, L.gate, L.up, sel, selw, h, h2);
+        return p;
     }
-    p.nseg = moe ? 2 : 1;
-    for (int k = 0; k < p.nseg; ++k) {
-        p.seg[k] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, k == 0 ? h : h2);
-        p.seg[k].B = L.up;
-        if (moe) p.seg[k].expA = p.seg[k].expB = k;
-        else if (src != ACT_PRO) p.seg[k].lora = lora_fold(l, 2);   // ranges gate, up
-        else if (lora_group(l, 2)) {
-            p.seg[k].pre = lora_pre;   // [gate rows | up rows]
-            p.seg[k].pre_up = hp.n_ff;
-        }
+    p.nseg = 1;
+    p.seg[0] = seg_of(L.gate, PAIR_AB, EPI_SWIGLU, h);
+    p.seg[0].B = L.up;
+    if (src != ACT_PRO) p.seg[0].lora = lora_fold(l, 2);   // ranges gate, up
+    else if (lora_group(l, 2)) {
+        p.seg[0].pre = lora_pre;   // [gate rows | up rows]
+        p.seg[0].pre_up = hp.n_ff;
     }
     return p;
 }
@@ -481,22 +512,15 @@ GemvParams Ctx::down_params(int l, ActSrc src) const {
     GemvParams p = gemv_base();
     p.K = hp.n_ff;
     set_act(p, src, 3, src == ACT_PRO ? 0 : sp[l].fD, h, nullptr, nullptr);
-    p.nseg = 1;
     if (hp.n_expert > 0) {
-        p.sel = sel;
-        p.selw = selw;
-        p.nslots = 2;
-        p.x[1] = h2;
-        p.seg[0] = seg_of(L.down, PAIR_AB, EPI_MOE_DOWN, x);
-        p.seg[0].expA = 0;
-        p.seg[0].expB = 1;
-        p.seg[0].actB = 1;
-    } else {
-        p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
-        p.seg[0].bias = L.bdown;
-        if (src != ACT_PRO) p.seg[0].lora = lora_fold(l, 3);
-        else if (lora_group(l, 3)) p.seg[0].pre = lora_pre;
+        moe_down_seg(p, L.down, sel, selw, h2, x, cvec_for(l));
+        return p;
     }
+    p.nseg = 1;
+    p.seg[0] = seg_of(L.down, PAIR_ADJ, EPI_ADD, x);
+    p.seg[0].bias = L.bdown;
+    if (src != ACT_PRO) p.seg[0].lora = lora_fold(l, 3);
+    else if (lora_group(l, 3)) p.seg[0].pre = lora_pre;
     p.seg[0].resid = x;
     p.seg[0].addend = cvec_for(l);   // build_cvec: after the FFN residual add
     return p;

@@ -1,6 +1,8 @@
 // Engine internals: GGUF parsing and the device-resident model (model.cpp), the decode context
 // (engine.cpp: buffers, the decode step, graphs, sampling reads, KV cache, state; batch.cpp: the
-// prompt-batch paths; lora.cpp: adapters).  The public surface is the C ABI in include/mi_engine.h.
+// prompt-batch paths; lora.cpp: adapters).  The public surface is the C ABI in include/mi_engine.h:
+// capi.cpp implements the product's entry points, ops.cpp the op-level ones (mi_op_*) the tests
+// reach single kernels through.
 #pragma once
 #include <mutex>
 #include <cmath>
@@ -137,6 +139,15 @@ struct Model {
     const QMat* find_qmat(const std::string& name) const;
 };
 
+// m's planes hold n_exp matrices of equal rows, stacked (a MoE *_exps tensor; dense: 1): rows,
+// n_exp and expert_stride[] become one expert's
+void split_experts(QMat& m, int n_exp);
+// Expert e of a MoE tensor as a matrix of its own (planes and MFMA-order copy offset).
+QMat expert_view(const QMat& q, int e);
+// One MFMA-order copy per expert of A (B set: gate and up in one) into dst, expert e's
+// mmq32_copy_bytes at dst + e * A.sw_expert_stride; enqueued, not synchronised
+void build_mmq_copies(QMat& A, const QMat* B, uint8_t* dst);
+
 // ---------------------------------------------------------------- LoRA ----
 // A LoRA adapter file (llama_adapter_lora_init, src/llama-adapter.cpp b5187), parsed and validated
 // against its base model (lora.cpp).  It keeps the pairs as they stand in the file; a context that
@@ -162,6 +173,22 @@ int dev_chain_contexts(int device);   // live contexts on the device
 
 // A decode launch's segment of one matrix (dense: no experts, no bias, no residual yet)
 GemvSeg seg_of(const QMat& A, int pair, int epi, float* out);
+// The routed experts' two decode launches on gemv_kernel, over plain arguments (the caller sets
+// the activation).  Gate/up: experts sel[0] and sel[1] of the pair + SwiGLU into h and h2.  Down:
+// x = (down[sel[0]] h * selw[0] + down[sel[1]] h2 * selw[1]) + x [+ addend], in place.
+void moe_gate_up_segs(GemvParams& p, const QMat& gate, const QMat& up, const int* sel, const float* selw, float* h,
+                      float* h2);
+void moe_down_seg(GemvParams& p, const QMat& down, const int* sel, const float* selw, const float* h2, float* x,
+                  const float* addend);
+// mmq32's launch of A (B set: the gate/up pair + SwiGLU, else a store) over ntok activation rows
+// into out [ntok][out_stride] (batch.cpp).  grp set: launch_moe_group's table, the rows grouped by
+// A's experts, at most grp_max rows each.
+GemmParams mmq32_params(const QMat& A, const QMat* B, int ntok, const int* tokpos, float* out, int out_stride,
+                        const int* grp = nullptr, int grp_max = 0);
+// activation formats a set of matrices reads: bit 0 Q8_K (k-quants), bit 1 Q8_0
+int act_fmt(std::initializer_list<int> types);
+void ensure_kernel_attributes(int device);   // init_kernel_attributes, once per device
+int mmqs_token_limit();                      // short batches: MMQS_MAX tokens, or MI_MMQS_MAX below it (0: off)
 
 // Owner of a context's device buffers, pinned host buffers, stream and events: one hipMalloc /
 // hipHostMalloc per buffer, every one recorded and released by the destructor -- which, as Ctx's

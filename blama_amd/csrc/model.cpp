@@ -160,13 +160,28 @@ std::vector<unsigned short> gelu_table_host() {
     return t;
 }
 
-// Expert e of a MoE tensor as a matrix of its own (planes and MFMA-order copy offset).
+void split_experts(QMat& m, int n_exp) {
+    m.rows /= n_exp;
+    m.n_exp = n_exp;
+    for (int k = 0; k < plane_count(m.type); ++k) m.expert_stride[k] = (long long)m.rows * m.nb * plane_sb_bytes(m.type, k);
+}
+
 QMat expert_view(const QMat& q, int e) {
     QMat v = q;
     for (int k = 0; k < 4; ++k)
         if (v.p[k]) v.p[k] += e * q.expert_stride[k];
     if (v.sw) v.sw += e * q.sw_expert_stride;
     return v;
+}
+
+void build_mmq_copies(QMat& A, const QMat* B, uint8_t* dst) {
+    const size_t one = mmq32_copy_bytes(A, B != nullptr);
+    for (int e = 0; e < std::max(1, A.n_exp); ++e) {   // expert e's planes -> its own copy
+        const QMat a = expert_view(A, e), b = B ? expert_view(*B, e) : QMat{};
+        launch_mmq32_swizzle(a, B ? &b : nullptr, dst + one * e, nullptr);
+    }
+    A.sw = dst;
+    A.sw_expert_stride = (long long)one;
 }
 
 bool Model::ensure_mmq_copies() {
@@ -197,16 +212,7 @@ bool Model::ensure_mmq_copies() {
         return false;
     }
     mmq_bytes = total;
-    for (size_t i = 0; i < todo.size(); ++i) {
-        QMat& A = *todo[i].first;
-        const size_t one = mmq32_copy_bytes(A, todo[i].second != nullptr);
-        for (int e = 0; e < experts(A); ++e) {   // expert e's planes -> its own copy
-            QMat a = expert_view(A, e), b = todo[i].second ? expert_view(*todo[i].second, e) : QMat{};
-            launch_mmq32_swizzle(a, todo[i].second ? &b : nullptr, mmq_arena + offs[i] + one * e, nullptr);
-        }
-        A.sw = mmq_arena + offs[i];
-        A.sw_expert_stride = (long long)one;
-    }
+    for (size_t i = 0; i < todo.size(); ++i) build_mmq_copies(*todo[i].first, todo[i].second, mmq_arena + offs[i]);
     MI_HIP(hipDeviceSynchronize());
     return true;
 }
@@ -523,16 +529,9 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         m.type = pl.t->type;
         m.K = pl.K;
         m.nb = pl.K / 256;
-        m.rows = (int)(pl.rows / pl.experts);
-        m.n_exp = pl.experts;
-        if (is_quant(m.type)) {
-            for (int k = 0; k < plane_count(m.type); ++k) {
-                m.p[k] = arena + pl.off[k];
-                m.expert_stride[k] = (long long)m.rows * m.nb * plane_sb_bytes(m.type, k);
-            }
-        } else {
-            m.p[0] = arena + pl.off[0];
-        }
+        m.rows = (int)pl.rows;
+        for (int k = 0; k < std::max(1, plane_count(m.type)); ++k) m.p[k] = arena + pl.off[k];   // (not quantised: the raw copy)
+        split_experts(m, pl.experts);
         return m;
     };
     auto f32p = [&](int idx) -> float* {

@@ -53,6 +53,15 @@ def test_dgemv_residual_add(gpu_lib, t, rows, K):
     assert np.all(err <= bound), (R.TYPE_NAME[t], rows, K, float((err / bound).max()))
 
 
+# the residual roles without a residual: refused with the other argument checks, before any device work
+@pytest.mark.parametrize("role", [ROLE_ADD, ROLE_ADDQ])
+def test_dgemv_residual_role_needs_resid(gpu_lib, role):
+    rows, K = 64, 256
+    w = rand_matrix(R.Q4_K, rows, K, seed=rows + K)
+    with pytest.raises(engine.EngineError, match="op_dgemv: residual role needs resid"):
+        engine.op_dgemv(role, R.Q4_K, w, rows, K, rand_x(K, seed=K + 3), resid=None)
+
+
 # DV_ADDQ runs dv_quant_kernel's no-norm arithmetic per 256-block in each workgroup: same bits
 @pytest.mark.parametrize("t", [R.Q4_K, R.Q5_K, R.Q6_K, R.Q8_0])
 @pytest.mark.parametrize("rows,K", [(64, 256), (2048, 5632), (512, 8192), (4096, 11008), (1024, 14336)])
