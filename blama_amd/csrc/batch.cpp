@@ -462,7 +462,8 @@ int Ctx::ubatch_layers_short(int nt) {
                     cell_pos, tokpos_b, ub_rope, hp.n_rot, hp.head_dim};
         launch_qkv_finish(F, stream);
         AttnParams a = battn_params(l);
-        // within ATTN_SHORT cells the decode step's fused kernel, one workgroup per (kv head, token)
+        // within ATTN_SHORT cells the decode step's kernel (attn_plan's ATTN_BATCH_QUANT /
+        // ATTN_BATCH_FUSED), one grid row per token
         // (20-token verify 3.52 -> 3.30 ms against the MFMA kernel's 32-token tiles; 64 tokens
         // equal, same box)
         const ActQ8 act_wo = ub_act(hp.n_embd, nt, L.wo.type);
@@ -470,7 +471,7 @@ int Ctx::ubatch_layers_short(int nt) {
         if (attn_mfma && n_cells > ATTN_SHORT) {
             launch_attn_mfma(a, nt, attnb, stream);
             launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
-        } else if (qattn) {   // the fused kernel also quantises each token's output for W_o
+        } else if (qattn) {   // the launch also quantises each token's output for W_o
             a.act_q8 = act_wo;
             launch_attn_multi(a, nt, attnb, stream);
         } else {

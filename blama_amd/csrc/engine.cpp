@@ -428,10 +428,11 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
     return n;
 }
 
-// Attention over the layer's cache.  Up to ATTN_SHORT cells one fused launch, which for the
-// streaming step (quant_out) also quantises its output for WO; past that the split kernels --
-// LLaMA: with the exchange of the single-launch attn_long_kernel -- whose partials the WO prologue
-// (r04 step) or attn_combine_quant (streaming step) adds in split order.
+// Attention over the layer's cache (attn.hip; attn_plan chooses the kernel from what is set here).
+// Up to ATTN_SHORT cells one launch, which for the streaming step (quant_out) also quantises its
+// output for WO; past that the split kernels -- LLaMA: with the exchange of the single-launch
+// attn_long_kernel -- whose partials the WO prologue (r04 step) or attn_combine_quant (streaming
+// step) adds in split order.
 AttnParams Ctx::attn_params(int l, bool quant_out) const {
     const HParams& hp = m->hp;
     AttnParams a{q, k_layer(l), v_layer(l), tokpos, cell_pos, attn_scores, attn_smax, part_o, hp.n_head, hp.n_head_kv,
@@ -578,7 +579,7 @@ bool Ctx::sp_setup() {
     if (hp.arch != ARCH_LLAMA) return false;
     const bool moe = hp.n_expert > 0;   // MoE: the attention half streams, the experts keep gemv_kernel
     if (hp.n_embd % 256 || hp.n_ff % 256 || hp.n_head * hp.head_dim != hp.n_embd) return false;
-    if (!attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim)) return false;
+    if (!attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim)) return false;   // (the launch's own plan)
     const int nl = hp.n_layer;
     sp.assign(nl, SpLayer{});
     sp_fH = act_fmt({m->output.type});

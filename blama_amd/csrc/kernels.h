@@ -1,4 +1,4 @@
-// Kernel parameter blocks and host-side launchers (implemented in kernels.hip).
+// Kernel parameter blocks and host-side launchers (implemented in the .hip files).
 #pragma once
 #include "common.h"
 #include <vector>
@@ -230,9 +230,12 @@ void launch_embed(const EmbedParams& p, hipStream_t s);
 // per 256-block)
 void launch_dv_quant(const float* x, const ActOut& a, hipStream_t s);
 
-// ---- attention over the f16 cache: KQ -> soft_max -> KQV, split over cells ----
-// Two launches, grid (n_head_kv, ATTN_SMAX) each; the WO GEMV's PRO_ATTN
-// prologue adds the splits' partials.
+// ---- attention over the f16 cache: KQ -> soft_max -> KQV (attn.hip) ----
+// Up to ATTN_SHORT cells, one launch: attn_dec_kernel where the output is also quantised for the
+// WO launch and a group serves one q head of head_dim 64 / 128, else attn_fused_kernel.  Past
+// that, split over cells, grid (heads, ATTN_SMAX): attn_long_kernel in one launch where its splits
+// are co-resident, else attn_scores_kernel + attn_pv_kernel; the WO GEMV's PRO_ATTN prologue or
+// a combine launch adds the splits' partials.  attn_plan (below) chooses.
 struct AttnParams {
     const float* q;            // [n_head*hd] (roped)
     const __half* kcache;      // [n_ctx][kv_dim]
@@ -247,7 +250,8 @@ struct AttnParams {
     unsigned long long* stamps;    // diagnostics (MI_STAMPS builds): scores / pv launches
     unsigned long long* stamps2;
     int fused;                     // 1: the single-launch kernel (the context has <= ATTN_SHORT cells)
-    int qsplit;                    // fused kernel: 0 = a workgroup per kv head; R = a workgroup per q head
+    int qsplit;                    // 0 = a workgroup per kv head; R = a workgroup per q head (the launchers
+                                   // set it from the plan)
     // contexts past ATTN_SHORT cells in ONE launch (attn_long_kernel): the splits of a q head
     // exchange their maxima and partial sums through these (null: the two-launch split kernels)
     unsigned* xflags;              // [n_head][ATTN_SMAX][32]: the exchange's flag lines
@@ -261,13 +265,29 @@ struct AttnParams {
     // that many grids of n_head * ATTN_SMAX workgroups are co-resident (occupancy x CUs)
     int long_share;
     int long_off;                  // 1: never the single launch (an exchange timed out before)
-    ActOut act_out;                // fused kernel, decode (act_out.act set): the output also quantised
-                                   // (a workgroup serves whole 256-blocks of it: 256 / (R * hd) kv heads)
+    ActOut act_out;                // decode within ATTN_SHORT cells (act_out.act set): the output also
+                                   // quantised (a workgroup serves whole 256-blocks of it)
     float* out_f32;                // attn_dec_kernel, optional: the fp32 output too, [n_head * hd] (a LoRA
                                    // adapter on attn_output reads it; the other kernels leave it in part_o)
-    ActQ8 act_q8;                  // fused kernel, a short batch (act_q8.q set; launch_attn_multi): each
-                                   // token's output quantised in the batch GEMMs' format, same blocks
+    ActQ8 act_q8;                  // a short batch (act_q8.q set; launch_attn_multi): each token's output
+                                   // quantised in the batch GEMMs' format, same blocks
 };
+// Which kernel serves a launch, and how: the mode is what the caller asks for (launch_attn: fused
+// with / without act_out, or past ATTN_SHORT cells; launch_attn_multi: with / without act_q8), the
+// plan everything the launch needs besides its pointers.  A pure host function: no device.
+enum AttnMode { ATTN_DECODE_QUANT, ATTN_DECODE_FUSED, ATTN_DECODE_SPLIT, ATTN_BATCH_QUANT, ATTN_BATCH_FUSED };
+enum AttnKernel { AK_NONE, AK_DEC, AK_FUSED, AK_LONG, AK_SCORES_PV };
+struct AttnPlan {
+    AttnKernel kernel;         // AK_NONE: no kernel serves the geometry in this mode
+    int R, LPC, HG, NWV;       // q heads per group, head_dim / 8, groups per workgroup, waves per group
+    int grid_x, grid_y, block;
+    size_t lds;                // dynamic LDS bytes (attn_long_kernel's scores)
+    int qsplit;
+};
+// long_ok (ATTN_DECODE_SPLIT): the single launch may be used (the exchange's buffers are there and
+// no exchange timed out); launch_attn still falls back to the two launches where its workgroups
+// are not co-resident
+AttnPlan attn_plan(AttnMode mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int ntok, bool long_ok);
 void launch_attn(const AttnParams& p, hipStream_t s);
 // a decode attention launch can also quantise its output (AttnParams::act_out) for this geometry
 bool attn_quant_supported(int n_head, int n_head_kv, int head_dim);

@@ -318,6 +318,18 @@ int32_t mi_op_attention(int32_t device, int32_t n_head, int32_t n_head_kv, int32
     MI_TRY(-1)
 }
 
+int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_ctx, int32_t ntok,
+                        int32_t long_ok, int32_t* out) {
+    try {
+        if (mode < ATTN_DECODE_QUANT || mode > ATTN_BATCH_FUSED) throw Error("attn_plan: bad mode");
+        const AttnPlan k = attn_plan((AttnMode)mode, n_head, n_head_kv, head_dim, n_ctx, ntok, long_ok != 0);
+        const int v[10] = {k.kernel, k.R, k.LPC, k.HG, k.NWV, k.grid_x, k.grid_y, k.block, (int)k.lds, k.qsplit};
+        std::copy(v, v + 10, out);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
 int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
                    int32_t ntok, const float* x, float* y) {
     try {

@@ -466,7 +466,7 @@ __device__ __forceinline__ void dv_quant_block(const ActOut& t, int b, const flo
 // activation, quantised as quantize_row_q8_K_ref (a.q80 = 0) or the x86 quantize_row_q8_0 (a.q80
 // = 1) and stored in the batch GEMMs' format (ActQ8: MFMA A fragments, token-minor d, byte-split
 // 32-element bsums) -- the arithmetic and layout of quant_act_kernel, shared with the attention
-// kernel that quantises a short batch's output itself.
+// kernels that quantise a short batch's output themselves (attn.hip: attn_dec_kernel, attn_fused_kernel).
 __device__ __forceinline__ void quant_actq8_block(const ActQ8& a, int t, int blk, const float v[4], int lane) {
     const int nb = a.K >> 8;
     const int tile = t >> 5, tr = t & 31;

@@ -114,6 +114,7 @@ _SIGS = {
     "mi_op_topk": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                     C.c_int32, _P]),
+    "mi_op_attn_plan": (C.c_int32, [C.c_int32] * 7 + [_P]),
     "mi_op_gemv_bench": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_float)]),
     "mi_op_gemm": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
@@ -537,6 +538,18 @@ def op_attention(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, n_head_kv: int
     _check(lib().mi_op_attention(device, n_head, n_head_kv, hd, n, _ptr(q), _ptr(k16), _ptr(v16), _ptr(cp), pos,
                                  _ptr(out)), "op_attention")
     return out.reshape(n_head, hd)
+
+
+ATTN_PLAN_FIELDS = ("kernel", "R", "LPC", "HG", "NWV", "grid_x", "grid_y", "block", "lds", "qsplit")
+
+
+def op_attn_plan(mode: int, n_head: int, n_head_kv: int, hd: int, n_ctx: int = 512, ntok: int = 1,
+                 long_ok: bool = False) -> dict:
+    """mi_op_attn_plan: the kernel, template arguments and launch shape a cache-attention launch of
+    this mode and head geometry would use, by ATTN_PLAN_FIELDS (needs no GPU)."""
+    out = np.zeros(len(ATTN_PLAN_FIELDS), np.int32)
+    _check(lib().mi_op_attn_plan(mode, n_head, n_head_kv, hd, n_ctx, ntok, int(long_ok), _ptr(out)), "op_attn_plan")
+    return dict(zip(ATTN_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def op_gemm(type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, raw_up=None,

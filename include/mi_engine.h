@@ -279,6 +279,13 @@ int32_t mi_op_topk(int32_t device, const float* logits, int32_t n, int32_t k, in
 int32_t mi_op_attention(int32_t device, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_cells,
                         const float* q, const uint16_t* k_f16, const uint16_t* v_f16, const int32_t* cell_pos,
                         int32_t pos, float* out);
+/* Which cache-attention kernel a launch of this head geometry would run (no device is touched).
+ * mode: 0 a decode step within 512 cells that also quantises its output, 1 one that does not,
+ * 2 a decode step past 512 cells (long_ok: the single launch may be used), 3 / 4 a short batch of
+ * ntok tokens with / without the quantised output.  out[10]: kernel (0 none, 1 decode, 2 fused,
+ * 3 long, 4 scores + pv), R, LPC, HG, NWV, grid_x, grid_y, block, dynamic LDS bytes, qsplit. */
+int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_ctx,
+                        int32_t ntok, int32_t long_ok, int32_t* out);
 /* The prompt-batch GEMM (Session.cpp:381-392's n_ubatch physical batches; ntok <= MI_MMQS_MAX,
  * default 64: the short-batch GEMM mmqs, otherwise the tiled int8-MFMA GEMM mmq32) of
  * ntok <= 512 token rows x[ntok][K] against a rows x K Q4_K / Q5_K / Q6_K / Q8_0 matrix: each row's
