@@ -396,6 +396,93 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
     logits_valid = !embeddings;
 }
 
+// ================================================== unquantised F16 models ===
+void Ctx::f16_gemm(const QMat* const* mats, float* const* outs, int n, const float* x, int nt, int out_stride,
+                   const float* resid) {
+    EncGemm g;
+    std::memset(&g, 0, sizeof(g));
+    for (int i = 0; i < n; ++i) {
+        g.m[i].w = reinterpret_cast<const __half*>(mats[i]->p[0]);
+        g.m[i].rows = mats[i]->rows;
+        g.m[i].out = outs[i];
+    }
+    g.nmat = n;
+    g.epi = resid ? ENC_ADD : ENC_NONE;
+    g.K = mats[0]->K;
+    g.ntok = nt;
+    g.x = x;
+    g.x_stride = g.K;
+    g.out_stride = out_stride;
+    g.resid = resid;
+    launch_enc_gemm(g, stream);
+}
+
+// Prompt ingestion / batched verification of an F16 model in physical batches of up to kBatchRows
+// tokens on the F16 MFMA GEMM (enc.hip): the layer of llm_build_llama with every matrix streamed
+// once per batch.  Per layer: norm rows, Q | K | V raw rows in one launch, RoPE + KV append
+// (qkv_finish, one part), causal attention, WO + residual, norm rows, gate | up raw rows, SwiGLU,
+// down + residual (the control vector's row by a pass of its own).  `all`: the head over every
+// token (rows of logits_all), else over the last one.
+void Ctx::decode_f16_batch(const int32_t* tokens, int n, bool all) {
+    const HParams& hp = m->hp;
+    const int ne = hp.n_embd, nff = hp.n_ff;
+    for (int c0 = 0; c0 < n; c0 += kBatchRows) {
+        const int nt = std::min((int)kBatchRows, n - c0);
+        upload_batch(tokens + c0, nt);
+        EmbedParams ep{m->tok_embd, tokpos_b, xb, ne};
+        launch_embed_multi(ep, nt, stream);
+        launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale(), hp.freq_scale, m->rope_freqs, ub_rope, stream);
+        for (int l = 0; l < hp.n_layer; ++l) {
+            const Layer& L = m->layers[l];
+            f16_norm(xb, nt, L.attn_norm, fb_xn);
+            {
+                const QMat* ms[3] = {&L.wq, &L.wk, &L.wv};
+                float* os[3] = {fb_t, fb_t + ne, fb_t + ne + kv_dim};
+                f16_gemm(ms, os, 3, fb_xn, nt, fb_t_stride, nullptr);
+            }
+            QkvFinish F{fb_t, fb_t_stride, 1, nt, L.wq.rows, L.wk.rows, L.wv.rows, qb, ne, k_layer(l), v_layer(l), kv_dim,
+                        cell_pos, tokpos_b, ub_rope, hp.n_rot, hp.head_dim};
+            launch_qkv_finish(F, stream);
+            if (attn_mfma) launch_attn_mfma(battn_params(l), nt, attnb, stream);
+            else launch_attn_multi(battn_params(l), nt, attnb, stream);
+            {
+                const QMat* ms[1] = {&L.wo};
+                float* os[1] = {xb};
+                f16_gemm(ms, os, 1, attnb, nt, ne, xb);
+            }
+            f16_norm(xb, nt, L.ffn_norm, fb_xn);
+            {
+                const QMat* ms[2] = {&L.gate, &L.up};
+                float* os[2] = {fb_t, fb_t + nff};
+                f16_gemm(ms, os, 2, fb_xn, nt, fb_t_stride, nullptr);
+            }
+            launch_part_sum(fb_t, 1, nt, nff, fb_t_stride, nullptr, 0, hb, nff, stream, nff);   // silu(gate) * up
+            {
+                const QMat* ms[1] = {&L.down};
+                float* os[1] = {xb};
+                f16_gemm(ms, os, 1, hb, nt, ne, xb);
+            }
+            if (const float* cv = cvec_for(l))   // build_cvec: after the FFN residual add
+                launch_part_sum(xb, 1, nt, ne, ne, cv, 0, xb, ne, stream);
+        }
+        const bool last = c0 + nt == n;
+        if (embeddings) {
+            embd_tail(xb, nt, c0);
+        } else if (all) {   // final norm + output head over every token of the batch
+            f16_norm(xb, nt, m->output_norm, fb_xn);
+            const QMat* ms[1] = {&m->output};
+            float* os[1] = {logits_all + (size_t)c0 * hp.n_vocab};
+            f16_gemm(ms, os, 1, fb_xn, nt, hp.n_vocab, nullptr);
+            finish_logits_all(c0, nt, last);
+        } else if (last) {   // the last token's row through the decode step's head
+            f16_norm(xb + (size_t)(nt - 1) * ne, 1, m->output_norm, f_xn);
+            launch_fgemv(fhead_params(), stream);
+            run_topk(logits);
+        }
+    }
+    logits_valid = !embeddings;
+}
+
 // One short physical batch (tokens uploaded to tokpos_b): embedding, the rope table, the layers on
 // mmqs, then the output -- every token's logits rows (`all`, rows c0.. of logits_all; the last
 // chunk's last row also feeds `logits` and the top-k) or the last token's through the decode head;

@@ -660,6 +660,7 @@ int64_t mi_prof_bytes(const mi_ctx* c) { return c ? c->impl->prof_bytes : -1; }
 int32_t mi_decode_path(const mi_ctx* c) {
     if (!c) return -1;
     if (c->impl->enc) return 2;
+    if (c->impl->m->f16) return 3;
     return c->impl->sp_ok ? 1 : 0;
 }
 int32_t mi_debug_stamps(mi_ctx* c, uint64_t* out, int32_t n_launch) {

@@ -11,7 +11,7 @@ namespace mi {
 
 // ggml_type ids (llama.cpp b5187 ggml.h) -- the GGUF tensor type field.
 enum GgmlType : int {
-    T_F32 = 0, T_F16 = 1, T_Q8_0 = 8, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
+    T_F32 = 0, T_F16 = 1, T_Q8_0 = 8, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15, T_BF16 = 30,
 };
 
 constexpr int QK_K = 256;

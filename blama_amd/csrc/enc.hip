@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64 * GW) void enc_gemm_f16_kernel(const EncGemm P) 
     for (int q = 0; q < 4; ++q) {
         const int row = r0 + 8 * q + 4 * h;
         float y[4] = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-        if (EPI != ENC_NONE) {   // ggml_add of the bias, a separate f32 operation
+        if (EPI != ENC_NONE && EPI != ENC_ADD) {   // ggml_add of the bias, a separate f32 operation
             const float4 b = *reinterpret_cast<const float4*>(bias + row);
             y[0] = y[0] + b.x;
             y[1] = y[1] + b.y;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(64 * GW) void enc_gemm_f16_kernel(const EncGemm P) 
                 y[e] = v <= -10.0f ? 0.0f : (v >= 10.0f ? v : t);
             }
         }
-        if (EPI == ENC_RESID) {  // the residual, after the bias
+        if (EPI == ENC_RESID || EPI == ENC_ADD) {  // the residual, after the bias
             const float4 r = *reinterpret_cast<const float4*>(P.resid + (long long)tok * P.out_stride + row);
             y[0] = y[0] + r.x;
             y[1] = y[1] + r.y;
@@ -309,18 +309,19 @@ void launch_enc_gemm(const EncGemm& p, hipStream_t s) {
         const EncMat& m = p.m[i];
         if (m.rows < 32 || m.rows % 32 || !m.w || (!m.out && !m.out16)) throw Error("enc gemm: rows must be a multiple of 32");
         if (m.rows > p.out_stride) throw Error("enc gemm: rows past the output stride");
-        if (p.epi != ENC_NONE && !m.bias) throw Error("enc gemm: this epilogue needs a bias");
+        if (p.epi != ENC_NONE && p.epi != ENC_ADD && !m.bias) throw Error("enc gemm: this epilogue needs a bias");
         tiles += m.rows / 32;
     }
     if (p.epi == ENC_GELU && !p.gelu_tab) throw Error("enc gemm: the GELU epilogue needs the table");
-    if (p.epi == ENC_RESID && !p.resid) throw Error("enc gemm: residual epilogue without resid");
+    if ((p.epi == ENC_RESID || p.epi == ENC_ADD) && !p.resid) throw Error("enc gemm: residual epilogue without resid");
     const dim3 grid((tiles + enc::GW - 1) / enc::GW, (p.ntok + 31) / 32), block(64 * enc::GW);
     switch (p.epi) {
     case ENC_NONE: hipLaunchKernelGGL(enc::enc_gemm_f16_kernel<ENC_NONE>, grid, block, 0, s, p); break;
     case ENC_BIAS: hipLaunchKernelGGL(enc::enc_gemm_f16_kernel<ENC_BIAS>, grid, block, 0, s, p); break;
     case ENC_GELU: hipLaunchKernelGGL(enc::enc_gemm_f16_kernel<ENC_GELU>, grid, block, 0, s, p); break;
     case ENC_RESID: hipLaunchKernelGGL(enc::enc_gemm_f16_kernel<ENC_RESID>, grid, block, 0, s, p); break;
-    default: throw Error("enc gemm: epilogue 0 .. 3");
+    case ENC_ADD: hipLaunchKernelGGL(enc::enc_gemm_f16_kernel<ENC_ADD>, grid, block, 0, s, p); break;
+    default: throw Error("enc gemm: epilogue 0 .. 4");
     }
     MI_HIP(hipGetLastError());
 }

@@ -270,6 +270,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         // MoE prompts need the MFMA path (the v_dot4 GEMM has no routed-expert form)
         if (hp.n_expert > 0 && !mmq_ok) batch_ok = false;
     }
+    if (m->f16) f16_init();
     attn_smax = mem.dev<float>((size_t)ATTN_SMAX * hp.n_head);
     attn_scores = mem.dev<float>((size_t)hp.n_head * n_ctx);
     attn_xflags = mem.dev<unsigned>((size_t)hp.n_head * ATTN_SMAX * 32, true);
@@ -342,7 +343,10 @@ void Ctx::apply_cvec(const float* data, size_t len, int n_embd, int il_start, in
 long long Ctx::ffn_bytes() const {
     if (enc) return 0;
     const Layer& L = m->layers[0];
-    auto mb = [](const QMat& q) { return (long long)q.rows * q.nb * ((long long)block_bytes(q.type) * 256 / block_elems(q.type)); };
+    auto mb = [](const QMat& q) {
+        if (q.type == T_F16) return (long long)q.rows * q.K * 2;
+        return (long long)q.rows * q.nb * ((long long)block_bytes(q.type) * 256 / block_elems(q.type));
+    };
     const HParams& hp = m->hp;
     const long long w = hp.n_expert > 0 ? 2 * (mb(L.gate) + mb(L.up)) : mb(L.gate) + mb(L.up);
     if (sp_ok)   // streaming path: x and the norm weight read (by every workgroup, L2-served), h written
@@ -576,7 +580,7 @@ void Ctx::enqueue_moe_ffn(int l) {
 // the step has a compiled variant (GPT-2 keeps the gemv_kernel graph; MoE experts run on it).
 bool Ctx::sp_setup() {
     const HParams& hp = m->hp;
-    if (hp.arch != ARCH_LLAMA) return false;
+    if (hp.arch != ARCH_LLAMA || m->f16) return false;   // (an F16 model: enqueue_step_f16)
     const bool moe = hp.n_expert > 0;   // MoE: the attention half streams, the experts keep gemv_kernel
     if (hp.n_embd % 256 || hp.n_ff % 256 || hp.n_head * hp.head_dim != hp.n_embd) return false;
     if (!attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim)) return false;   // (the launch's own plan)
@@ -688,6 +692,124 @@ void Ctx::enqueue_step_sp(bool with_logits) {
     }
 }
 
+// ================================================== unquantised F16 models ===
+void Ctx::f16_init() {
+    const HParams& hp = m->hp;
+    f_xn = mem.dev<float>(hp.n_embd);
+    attn_mfma = attn_mfma_supported(hp.head_dim);
+    if (!batch_ok) return;
+    fb_xn = mem.dev<float>((size_t)kBatchRows * hp.n_embd);
+    fb_t_stride = std::max(hp.n_embd + 2 * kv_dim, 2 * hp.n_ff);
+    fb_t = mem.dev<float>((size_t)kBatchRows * fb_t_stride);
+    ub_rope = mem.dev<float2>((size_t)UB_MAX * std::max(1, hp.n_rot / 2));
+}
+
+// rms_norm(x) * w of nt rows to f32 rows (the matrix launch that reads them rounds to f16)
+void Ctx::f16_norm(const float* xrows, int nt, const float* w, float* out) {
+    const HParams& hp = m->hp;
+    launch_embd_norm(EmbdNorm{xrows, hp.n_embd, nt, hp.n_embd, w, nullptr, hp.eps, out, hp.n_embd}, stream);
+}
+
+namespace {
+FgemvParams fgemv_of(int role, const QMat& A, const float* x, float* out) {
+    FgemvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.role = role;
+    p.w[0] = reinterpret_cast<const __half*>(A.p[0]);
+    p.rows[0] = A.rows;
+    p.nmat = 1;
+    p.K = A.K;
+    p.x = x;
+    p.out = out;
+    return p;
+}
+}  // namespace
+
+// Q/K/V of the normed row + RoPE + KV append: the three matrices in one launch
+FgemvParams Ctx::fqkv_params(int l) const {
+    const HParams& hp = m->hp;
+    const Layer& L = m->layers[l];
+    FgemvParams p = fgemv_of(FG_QKV, L.wq, f_xn, q);
+    p.w[1] = reinterpret_cast<const __half*>(L.wk.p[0]);
+    p.rows[1] = L.wk.rows;
+    p.w[2] = reinterpret_cast<const __half*>(L.wv.p[0]);
+    p.rows[2] = L.wv.rows;
+    p.nmat = 3;
+    p.nq = L.wq.rows;
+    p.nk = L.wk.rows;
+    p.tokpos = tokpos;
+    p.cell_pos = cell_pos;
+    p.theta_scale = theta_scale();
+    p.freq_scale = hp.freq_scale;
+    p.n_rot = hp.n_rot;
+    p.head_dim = hp.head_dim;
+    p.freq_factors = m->rope_freqs;
+    p.kcache = k_layer(l);
+    p.vcache = v_layer(l);
+    p.kv_dim = kv_dim;
+    return p;
+}
+
+// output projection of the attention output (the fused launch's one split in part_o, else the
+// splits' sum in attn) + residual, in place
+FgemvParams Ctx::fwo_params(int l) const {
+    FgemvParams p = fgemv_of(FG_ADD, m->layers[l].wo, attn_fused ? part_o : attn, x);
+    p.resid = x;
+    return p;
+}
+
+FgemvParams Ctx::fgate_up_params(int l) const {
+    const Layer& L = m->layers[l];
+    FgemvParams p = fgemv_of(FG_SWIGLU, L.gate, f_xn, h);
+    p.w[1] = reinterpret_cast<const __half*>(L.up.p[0]);
+    p.rows[1] = L.up.rows;
+    p.nmat = 2;
+    return p;
+}
+
+// FFN down + residual, in place, then the control vector's row (build_cvec)
+FgemvParams Ctx::fdown_params(int l) const {
+    FgemvParams p = fgemv_of(FG_ADD, m->layers[l].down, h, x);
+    p.resid = x;
+    p.addend = cvec_for(l);
+    return p;
+}
+
+FgemvParams Ctx::fhead_params() const { return fgemv_of(FG_STORE, m->output, f_xn, logits); }
+
+// (the gate/up launch of prof_layer: segment 1 on its own, with the event pair -- as run_gemv)
+void Ctx::run_fgemv(const FgemvParams& p, int l, bool gate_up) {
+    const bool prof = gate_up && l == prof_layer;
+    if (prof) enq_seg = 1;
+    const bool timed = prof && seg_filter == 1;
+    if (seg_on()) launch_fgemv(p, stream, timed ? prof_ev[0] : nullptr, timed ? prof_ev[1] : nullptr);
+    if (prof) enq_seg = 2;
+}
+
+// The layers and the tail of one batch-1 decode step of an F16 model (the embedding row is in x)
+void Ctx::enqueue_step_f16(bool with_logits) {
+    const HParams& hp = m->hp;
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const Layer& L = m->layers[l];
+        if (seg_on()) f16_norm(x, 1, L.attn_norm, f_xn);
+        run_fgemv(fqkv_params(l));
+        run_attn(attn_params(l, false));
+        if (!attn_fused && seg_on()) launch_attn_combine(AttnPartials{part_o, hp.n_head, hp.head_dim}, tokpos, attn, stream);
+        run_fgemv(fwo_params(l));
+        if (seg_on()) f16_norm(x, 1, L.ffn_norm, f_xn);
+        run_fgemv(fgate_up_params(l), l, true);
+        run_fgemv(fdown_params(l));
+    }
+    if (!with_logits || !seg_on()) return;
+    if (embeddings) {   // embeddings mode: result_norm of this token, no head
+        enqueue_embd_norm(x, 1, embd_step());
+        return;
+    }
+    f16_norm(x, 1, m->output_norm, f_xn);
+    launch_fgemv(fhead_params(), stream);
+    run_topk(logits);
+}
+
 // One decode step for the token in tokpos (batch 1): the llm_build_llama / llm_build_gpt2 graph,
 // on the streaming kernels (sp_ok) or on gemv_kernel.
 void Ctx::enqueue_step(bool with_logits) {
@@ -696,6 +818,10 @@ void Ctx::enqueue_step(bool with_logits) {
     enq_launch = 0;
     EmbedParams ep{m->tok_embd, tokpos, x, hp.n_embd, m->pos_embd, hp.arch == ARCH_GPT2 ? 1 : 0, step_ctr};
     if (seg_on()) launch_embed(ep, stream);
+    if (m->f16) {
+        enqueue_step_f16(with_logits);
+        return;
+    }
     if (sp_ok) {
         enqueue_step_sp(with_logits);
     } else {
@@ -797,9 +923,16 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
         logits_all = mem.dev<float>((size_t)n_batch * m->hp.n_vocab);
         logits_all_cap = (int)n_batch;
     }
+    // an F16 model: any call of two tokens or more on the F16 MFMA GEMM (the MFMA attention over any
+    // number of cells; head sizes it does not serve: the fused form within ATTN_SHORT cells)
+    if (m->f16 && n >= 2 && batch_ok && prof_layer < 0 && (attn_mfma || n_cells + n <= ATTN_SHORT)) {
+        decode_f16_batch(tokens, n, all);
+        if (all && !embeddings) out_rows = n;
+        return 0;
+    }
     // prompt ingestion through the batched GEMM when the context stays within the fused
     // attention's reach (dense models; MI_NO_BATCH=1 forces token-by-token decode)
-    const bool fits = n >= 2 && batch_ok && hp_dense() && n_cells + n <= ATTN_SHORT && prof_layer < 0;
+    const bool fits = n >= 2 && batch_ok && !m->f16 && hp_dense() && n_cells + n <= ATTN_SHORT && prof_layer < 0;
     // the MFMA batch path attends over any number of cells with the MFMA attention kernel
     const bool ub = n >= 2 && batch_ok && mmq_ok && prof_layer < 0 && (attn_mfma || n_cells + n <= ATTN_SHORT);
     if (ub && (!all || out_mmq || embeddings)) {

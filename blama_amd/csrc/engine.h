@@ -104,6 +104,18 @@ struct Model {
     bool add_bos = true;
     int device = 0;
     bool vocab_only = false;
+    // An unquantised model: a dense LLaMA graph (n_expert == 0) whose matrices -- token_embd, output
+    // (absent: the head is token_embd, a tied model) and the seven per layer -- are all F16; norm
+    // weights and rope_freqs F32.  The matrices stay plain [rows][K] f16 rows in the arena (QMat::p[0],
+    // type T_F16): no planes, no MFMA-order copy (ensure_mmq_copies has nothing to do).
+    // Shape rules (check_f16, refused with a message otherwise): n_embd = n_head x head_dim, n_head a
+    // multiple of n_head_kv; n_embd and n_ff multiples of 32, at most 16384 (fgemv.hip: K);
+    // n_head_kv x head_dim and n_vocab multiples of 32 (the batch GEMM's 32-row tiles); n_rot even.
+    // Refused: BF16 or F32 matrices, F16 mixed with quantised matrices, F16 MoE, F16 GPT-2.  LoRA
+    // adapters on an F16 model are out of scope: Lora::load refuses it.
+    bool f16 = false;
+    bool check_f16() const;
+    void account(const GgufTensor& t, int experts);   // weight_bytes, type_bytes
 
     uint8_t* arena = nullptr;
     size_t arena_bytes = 0;
@@ -440,6 +452,30 @@ struct Ctx {
     char* sp_act[5] = {};               // QKV, WO, gate/up, down, head inputs
     bool sp_setup();
     void enqueue_step_sp(bool with_logits);
+
+    // ---- unquantised F16 models (Model::f16): the decode step on fgemv.hip (engine.cpp), prompt
+    // batches of up to kBatchRows rows on enc.hip's F16 MFMA GEMM (batch.cpp).  Every matrix launch
+    // reads an f32 activation row and rounds it to f16 itself; the normed rows come from a small
+    // launch of their own (embd.hip's norm kernel).  Per layer: norm, Q/K/V (+ RoPE, KV append),
+    // attention (+ the splits' combine past ATTN_SHORT cells), WO + residual, norm, gate/up + SwiGLU,
+    // down + residual (+ the control vector's row).
+    float* f_xn = nullptr;              // [n_embd]: the normed row of the step
+    float* fb_xn = nullptr;             // batches: [kBatchRows][n_embd] normed rows
+    float* fb_t = nullptr;              // batches: [kBatchRows][max(n_embd + 2 kv_dim, 2 n_ff)], a GEMM's raw rows
+    int fb_t_stride = 0;
+    void f16_init();
+    void f16_norm(const float* xrows, int nt, const float* w, float* out);
+    FgemvParams fqkv_params(int l) const;
+    FgemvParams fwo_params(int l) const;
+    FgemvParams fgate_up_params(int l) const;
+    FgemvParams fdown_params(int l) const;
+    FgemvParams fhead_params() const;
+    void run_fgemv(const FgemvParams& p, int l = -1, bool gate_up = false);
+    void enqueue_step_f16(bool with_logits);
+    // one F16 GEMM of a physical batch: 1-3 matrices over x [nt][K] into out [nt][out_stride] (+ resid)
+    void f16_gemm(const QMat* const* mats, float* const* outs, int n, const float* x, int nt, int out_stride,
+                  const float* resid);
+    void decode_f16_batch(const int32_t* tokens, int n, bool all);
 
     // ---- the parameter block of each decode launch, built in one place (engine.cpp) ----
     // How a GEMV's activation arrives:

@@ -163,6 +163,42 @@ bool gemv_pair_supported(int t1, int t2);
 int gemv_grid(const GemvParams& p);
 void init_gemm_attributes();     // the batch GEMMs' LDS limits (kernels.hip)
 
+// ---- decode GEMV over unquantised F16 matrices [rows][K] (fgemv.hip) ----
+// y[r] = sum_k f16(x[k]) * W[r][k]: the f32 activation rounded to f16 once (RNE), exact f32
+// products, f32 accumulation in an order K alone fixes (bit-reproducible, whatever the grid), then
+// the role's epilogue -- dgemv.hip's four.  K % 32 == 0, 32 <= K <= FGEMV_MAX_K.
+constexpr int FGEMV_MAX_K = 16384;
+enum FgRole {
+    FG_QKV = 0,       // 1-3 matrices laid end to end (even row counts): rows < nq -> RoPE NORM -> out (f32
+                      // q); rows < nq + nk -> RoPE -> f16 K cache row of the token's cell (+ cell_pos);
+                      // the rest -> f16 V cache row
+    FG_ADD = 1,       // out[r] = (y + resid[r]) [+ addend[r]]
+    FG_SWIGLU = 2,    // w[0] = gate, w[1] = up: out[r] = silu(gate . x) * (up . x)
+    FG_STORE = 3,     // out[r] = y
+};
+struct FgemvParams {
+    int role;
+    const __half* w[3];
+    int rows[3];
+    int nmat, K;
+    int nq, nk;               // FG_QKV
+    const float* x;           // [K] f32
+    float* out;
+    const float* resid;       // FG_ADD (may alias out)
+    const float* addend;      // FG_ADD, optional (a control vector's layer row)
+    // RoPE / KV cache (FG_QKV), as GemvParams'
+    const int* tokpos;
+    int* cell_pos;
+    float theta_scale, freq_scale;
+    int n_rot, head_dim;
+    const float* freq_factors;
+    __half* kcache;
+    __half* vcache;
+    int kv_dim;
+};
+bool fgemv_supported(int K);
+void launch_fgemv(const FgemvParams& p, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
 struct AttnParams;
 
 // ---- batched quantised GEMM over up to GEMM_NT tokens (prompt ingestion) ----
@@ -527,10 +563,11 @@ void launch_enc_embed(const EncEmbed& p, hipStream_t s);
 // F16 matrices [rows][K] over one activation, then the epilogue: + bias[r]; gelu(. + bias[r]) by
 // ggml's f16 table; (. + bias[r]) + resid[t][r] -- each add a separate f32 operation.  rows % 32
 // == 0, K % 32 == 0, 1 <= ntok <= ENC_MAX_TOK.  A matrix writes f32 rows (out) or f16 rows (out16).
-enum EncEpi { ENC_NONE = 0, ENC_BIAS = 1, ENC_GELU = 2, ENC_RESID = 3 };
+// ENC_ADD: y + resid[t][r] with no bias (the bias-free projections of an F16 LLaMA model's prompt batches)
+enum EncEpi { ENC_NONE = 0, ENC_BIAS = 1, ENC_GELU = 2, ENC_RESID = 3, ENC_ADD = 4 };
 struct EncMat {
     const __half* w;       // [rows][K]
-    const float* bias;     // [rows] (every epilogue but ENC_NONE)
+    const float* bias;     // [rows] (every epilogue but ENC_NONE / ENC_ADD)
     int rows;
     float* out;            // [ntok][out_stride], or
     __half* out16;         // [ntok][out_stride] f16
@@ -540,7 +577,7 @@ struct EncGemm {
     int nmat, epi, K, ntok;
     const float* x;        // [ntok][x_stride]
     int x_stride, out_stride;
-    const float* resid;    // ENC_RESID: [ntok][out_stride] (may alias out)
+    const float* resid;    // ENC_RESID / ENC_ADD: [ntok][out_stride] (may alias out)
     const unsigned short* gelu_tab;   // ENC_GELU: ggml_table_gelu_f16
 };
 void launch_enc_gemm(const EncGemm& p, hipStream_t s);

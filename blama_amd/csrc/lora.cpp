@@ -43,6 +43,7 @@ bool parse_base(const std::string& name, int n_layer, int& layer, int& target) {
 std::shared_ptr<Lora> Lora::load(const Model* m, const uint8_t* data, size_t size) {
     if (!m) throw Error("lora: null model");
     if (!data) throw Error("lora: null image");
+    if (m->f16) throw Error("lora: adapters on an unquantised F16 base model are not supported");
     Gguf g;
     g.parse(data, size);
     if (g.get_str("general.type", "") != "adapter") throw Error("lora: general.type is not 'adapter'");
@@ -165,6 +166,7 @@ void put_elems(uint8_t* dst, bool to_f16, const uint8_t* src, int type, size_t n
 void Ctx::set_lora(const std::shared_ptr<Lora>& a, float scale) {
     if (!a) throw Error("set_lora: null adapter");
     if (a->m != m) throw Error("set_lora: the adapter belongs to another model");
+    if (m->f16) throw Error("set_lora: adapters on an unquantised F16 base model are not supported");
     std::vector<LoraSet> next = loras;
     auto it = std::find_if(next.begin(), next.end(), [&](const LoraSet& s) { return s.a == a; });
     if (it != next.end()) it->scale = scale;

@@ -134,6 +134,85 @@ const GgufTensor* Gguf::tensor(const std::string& name) const {
 }
 
 // ================================================================= model ===
+// One tensor into the model's byte counts: the bytes a decode step streams (not the embedding
+// tables; an expert tensor contributes the n_expert_used experts the router picks -- build_moe_ffn
+// reads only those -- not all n_expert of them; a BERT model counts its matrices itself) and the
+// type histogram.
+void Model::account(const GgufTensor& t, int experts) {
+    if (hp.arch != ARCH_BERT && t.name != "token_embd.weight" && t.name != "position_embd.weight")
+        weight_bytes += experts > 1 ? (long long)t.nbytes / experts * hp.n_expert_used : (long long)t.nbytes;
+    if (t.type >= 0 && t.type < 32) type_bytes[t.type] += (long long)t.nbytes;
+}
+
+// Whether the file is an all-F16 dense LLaMA model (engine.h, Model::f16): false for a file whose
+// layer matrices and output head are all quantised (its token_embd may be of any served type, as
+// before); otherwise every matrix must be F16 and the shape rules must hold, or the load is
+// refused with the tensor and the reason.  Reads the header only.
+bool Model::check_f16() const {
+    std::vector<std::string> names = {"output.weight"};
+    const char* dense[] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down",
+                           "ffn_gate_exps", "ffn_up_exps", "ffn_down_exps", "attn_qkv"};
+    for (int l = 0; l < hp.n_layer; ++l)
+        for (const char* d : dense) names.push_back("blk." + std::to_string(l) + "." + d + ".weight");
+    std::vector<const GgufTensor*> mats;
+    bool plain = false;   // a layer matrix or the head is not quantised
+    for (const std::string& n : names)
+        if (const GgufTensor* t = gguf.tensor(n)) {
+            mats.push_back(t);
+            plain = plain || !is_quant(t->type);
+        }
+    if (!plain) return false;
+    if (const GgufTensor* t = gguf.tensor("token_embd.weight")) mats.push_back(t);
+    const GgufTensor* first_f16 = nullptr;
+    for (const GgufTensor* t : mats)
+        if (t->type == T_F16 && !first_f16) first_f16 = t;
+    for (const GgufTensor* t : mats) {
+        if (t->type == T_BF16)
+            throw Error("tensor " + t->name + ": BF16 matrices are not served (convert the model to F16, or quantise it)");
+        if (t->type == T_F32)
+            throw Error("tensor " + t->name + ": F32 matrices are not served (convert the model to F16, or quantise it)");
+        if (is_quant(t->type) && first_f16)
+            throw Error("tensor " + t->name + ": the file mixes F16 (" + first_f16->name +
+                        ") and quantised matrices; an unquantised model must be F16 throughout");
+        if (t->type != T_F16) throw Error("tensor " + t->name + ": unsupported ggml type " + std::to_string(t->type) + " for a matrix");
+    }
+    if (hp.arch == ARCH_GPT2)
+        throw Error("tensor " + mats[0]->name + ": F16 GPT-2 models are not served (the gpt2 graph takes quantised matrices only)");
+    if (hp.n_expert > 0)
+        throw Error("tensor " + mats[0]->name + ": F16 MoE models are not served (the expert kernels take quantised matrices only)");
+    // shape rules of the F16 kernels (engine.h)
+    const int kv = hp.n_head_kv * hp.head_dim;
+    auto rule = [](bool ok, const std::string& what) {
+        if (!ok) throw Error("F16 model: " + what);
+    };
+    rule(hp.n_head * hp.head_dim == hp.n_embd && hp.n_head_kv > 0 && hp.n_head % hp.n_head_kv == 0,
+         "embedding_length must be head_count x head_dim, head_count a multiple of head_count_kv");
+    rule(hp.n_embd % 32 == 0 && hp.n_embd <= FGEMV_MAX_K, "embedding_length " + std::to_string(hp.n_embd) + " must be a multiple of 32, at most 16384");
+    rule(hp.n_ff > 0 && hp.n_ff % 32 == 0 && hp.n_ff <= FGEMV_MAX_K, "feed_forward_length " + std::to_string(hp.n_ff) + " must be a multiple of 32, at most 16384");
+    rule(kv % 32 == 0, "head_count_kv x head_dim = " + std::to_string(kv) + " must be a multiple of 32");
+    rule(hp.n_vocab > 0 && hp.n_vocab % 32 == 0, "vocabulary size " + std::to_string(hp.n_vocab) + " must be a multiple of 32");
+    rule(hp.n_rot % 2 == 0 && hp.n_rot <= hp.head_dim, "rope.dimension_count must be even and at most head_dim");
+    auto shape = [&](const std::string& n, long long rows, long long K) {
+        const GgufTensor* t = gguf.tensor(n);
+        if (!t) throw Error("GGUF: missing tensor " + n);
+        if (t->n_dims != 2 || t->ne[0] != K || t->ne[1] != rows)
+            throw Error("tensor " + n + ": expected " + std::to_string(rows) + " x " + std::to_string(K) + " (rows x K)");
+    };
+    shape("token_embd.weight", hp.n_vocab, hp.n_embd);
+    if (gguf.tensor("output.weight")) shape("output.weight", hp.n_vocab, hp.n_embd);
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const std::string b = "blk." + std::to_string(l) + ".";
+        shape(b + "attn_q.weight", hp.n_embd, hp.n_embd);
+        shape(b + "attn_k.weight", kv, hp.n_embd);
+        shape(b + "attn_v.weight", kv, hp.n_embd);
+        shape(b + "attn_output.weight", hp.n_embd, hp.n_embd);
+        shape(b + "ffn_gate.weight", hp.n_ff, hp.n_embd);
+        shape(b + "ffn_up.weight", hp.n_ff, hp.n_embd);
+        shape(b + "ffn_down.weight", hp.n_embd, hp.n_ff);
+    }
+    return true;
+}
+
 Model::~Model() {
     if (arena || mmq_arena || gelu_tab) hipSetDevice(device);
     if (arena) hipFree(arena);
@@ -293,7 +372,15 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     eos = (int)gguf.get_int("tokenizer.ggml.eos_token_id", 2);
     eot = (int)gguf.get_int("tokenizer.ggml.eot_token_id", -1);
     add_bos = gguf.get_int("tokenizer.ggml.add_bos_token", 1) != 0;
-    if (vocab_only) return;
+    if (!bert) f16 = check_f16();
+    if (vocab_only) {
+        // an F16 model's weight bytes and type histogram are known from the header alone
+        if (f16) {
+            for (const GgufTensor& t : gguf.tensors) account(t, 1);
+            if (!gguf.tensor("output.weight")) weight_bytes += (long long)gguf.tensor("token_embd.weight")->nbytes;   // tied head
+        }
+        return;
+    }
     if (p.cpu_only) throw Error("cpu_only models are served by the CPU reference path, not this engine");
 
     // ---- plan the arena ----
@@ -337,6 +424,10 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         }
         const int type = ts[0]->type;
         const int K = (int)ts[0]->ne[0];
+        if (f16) {   // plain [rows][K] rows, one raw copy each
+            for (const auto& n : names) idx.push_back(add(n, true, 1));
+            return;
+        }
         if (!is_quant(type) || K % 256) throw Error("tensor " + names[0] + ": not a quantised matrix with K % 256 == 0");
         const size_t first = plan.size();
         for (const GgufTensor* t : ts) {
@@ -484,14 +575,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     if (hp.n_expert > 0 && hp.n_expert_used != 2)
         throw Error("MoE: this build serves top-2 routing (expert_used_count=2)");
     arena_bytes = off;
-    for (const auto& pl : plan) {
-        // bytes one decode step streams: an expert tensor contributes the n_expert_used experts
-        // the router picks (build_moe_ffn reads only those), not all n_expert of them
-        if (!bert && pl.t->name != "token_embd.weight" && pl.t->name != "position_embd.weight")
-            weight_bytes += pl.experts > 1 ? (long long)pl.t->nbytes / pl.experts * hp.n_expert_used
-                                           : (long long)pl.t->nbytes;
-        if (pl.t->type >= 0 && pl.t->type < 32) type_bytes[pl.t->type] += (long long)pl.t->nbytes;
-    }
+    for (const auto& pl : plan) account(*pl.t, pl.experts);
     if (i_out < 0 && !bert) weight_bytes += (long long)plan[i_te].t->nbytes;   // tied output head
 
     MI_HIP(hipSetDevice(device));
@@ -561,7 +645,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     output_norm_b = f32p(i_onb);
     if (!bert) {
         output = i_out >= 0 ? qm(i_out) : qm(i_te);
-        if (!is_quant(output.type)) throw Error("output head must be a quantised tensor in this build");
+        if (!f16 && !is_quant(output.type)) throw Error("output head must be a quantised tensor in this build");
     }
     output_norm = f32p(i_on);
     rope_freqs = f32p(i_rf);
@@ -581,7 +665,8 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         L.bup = f32p(x.bu);
         L.bdown = f32p(x.bd);
         for (const QMat* m : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down})
-            if (!is_quant(m->type)) throw Error("layer weights must be quantised (Q4_K/Q5_K/Q6_K/Q8_0)");
+            if (!f16 && !is_quant(m->type)) throw Error("layer weights must be quantised (Q4_K/Q5_K/Q6_K/Q8_0)");
+        if (f16) continue;   // Q, K and V stay three matrices (wq, wk, wv): no row groups
         if (gpt2) {   // the fused QKV rows: n_embd Q rows, n_embd K rows, n_embd V rows
             L.n_qkv = 1;
             L.qkv[0] = qm(x.qkv_groups[0][0]);

@@ -183,6 +183,122 @@ int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw,
     MI_TRY(-1)
 }
 
+// The F16 decode step's streaming GEMV (fgemv.hip) for one launch of a given role, mi_op_dgemv's
+// roles 0-3: role 0 without RoPE, every row a Q row (a second matrix: further rows).
+int32_t mi_op_fgemv(int32_t device, int32_t role, const uint16_t* w, int32_t rows, int32_t K, const uint16_t* w2,
+                    int32_t rows2, const float* x, const float* resid, float* y) {
+    try {
+        if (role < 0 || role > 3) throw Error("op_fgemv: role");
+        if (!w || !x || !y || rows < 1) throw Error("op_fgemv: null argument");
+        if (!fgemv_supported(K)) throw Error("op_fgemv: K must be a multiple of 32, 32 .. 16384");
+        const bool two = w2 && rows2 > 0;
+        if (role == 2 && (!two || rows2 != rows)) throw Error("op_fgemv: SwiGLU needs a pair");
+        if ((role == 1 || role == 3) && two) throw Error("op_fgemv: one matrix for this role");
+        if (role == 1 && !resid) throw Error("op_fgemv: residual role needs resid");
+        MI_HIP(hipSetDevice(device));
+        const int out_rows = role == 0 ? rows + (two ? rows2 : 0) : rows;
+        Dev<uint16_t> da((size_t)rows * K, w), db(two ? (size_t)rows2 * K : 8, two ? w2 : nullptr);
+        Dev<float> dx(K, x), dy(out_rows), dr(out_rows, role == 1 ? resid : nullptr);
+        Dev<int> dtp(4);
+        dtp.fill(0);
+        FgemvParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.role = role;
+        p.w[0] = f16(da.p);
+        p.rows[0] = rows;
+        p.nmat = 1;
+        if (two) {
+            p.w[1] = f16(db.p);
+            p.rows[1] = rows2;
+            p.nmat = 2;
+        }
+        p.K = K;
+        p.nq = out_rows;   // Q/K/V: every row a Q row, n_rot 0 (no rotation)
+        p.x = dx.p;
+        p.out = dy.p;
+        p.resid = role == 1 ? dr.p : nullptr;
+        p.tokpos = dtp.p;
+        p.head_dim = 128;
+        launch_fgemv(p, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dy.download(y);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// Median time of one fgemv launch of `role` over rows x K F16 matrices (role 0: one matrix, every
+// row a Q row; role 2: a gate/up pair of rows each), from events recorded at the kernel's own start
+// and end, after a warm-up; consecutive launches read different copies so that they stream from
+// HBM, not from the Infinity Cache.  bytes_out: the matrix bytes one launch reads.
+int32_t mi_op_fgemv_bench(int32_t device, int32_t role, int32_t rows, int32_t K, int32_t iters, float* median_us,
+                          int64_t* bytes_out) {
+    try {
+        if (role < 0 || role > 3 || rows < 2 || (rows & 1) || iters < 1 || !median_us) throw Error("op_fgemv_bench: arguments");
+        if (!fgemv_supported(K)) throw Error("op_fgemv_bench: K must be a multiple of 32, 32 .. 16384");
+        MI_HIP(hipSetDevice(device));
+        const int nmat = role == 2 ? 2 : 1;
+        const size_t one = (size_t)rows * K * nmat;   // halves of one copy
+        const int copies = (int)std::min<size_t>(64, std::max<size_t>(1, (768ull << 20) / (one * 2) + 1));
+        // random f16 weights of the models' scale: a 1 Mi-element block tiled over the copies
+        std::vector<uint16_t> blk(1 << 20);
+        unsigned long long st = 0x9E3779B97F4A7C15ull;
+        for (uint16_t& v : blk) {
+            st = st * 6364136223846793005ull + 1442695040888963407ull;
+            const _Float16 h = (_Float16)(((float)((st >> 40) & 0xFFFF) / 65536.0f - 0.5f) * 0.1f);
+            std::memcpy(&v, &h, 2);
+        }
+        Dev<uint16_t> w(one * copies);
+        for (size_t o = 0; o < one * copies; o += blk.size())
+            MI_HIP(hipMemcpy(w.p + o, blk.data(), std::min(blk.size(), one * copies - o) * 2, hipMemcpyHostToDevice));
+        std::vector<float> hx(K);
+        for (int i = 0; i < K; ++i) hx[i] = 0.5f - 0.01f * (float)(i % 97);
+        Dev<float> dx(K, hx.data()), dy(rows), dr(rows);
+        dr.fill(0);
+        Dev<int> dtp(4);
+        dtp.fill(0);
+        auto params = [&](int c) {
+            FgemvParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.role = role;
+            p.w[0] = f16(w.p + (size_t)c * one);
+            p.rows[0] = rows;
+            p.nmat = nmat;
+            if (nmat == 2) {
+                p.w[1] = p.w[0] + (size_t)rows * K;
+                p.rows[1] = rows;
+            }
+            p.K = K;
+            p.nq = rows;
+            p.x = dx.p;
+            p.out = dy.p;
+            p.resid = role == 1 ? dr.p : nullptr;
+            p.tokpos = dtp.p;
+            p.head_dim = 128;
+            return p;
+        };
+        hipEvent_t a, b;
+        MI_HIP(hipEventCreate(&a));
+        MI_HIP(hipEventCreate(&b));
+        std::vector<float> t;
+        for (int i = 0; i < copies + 4; ++i) launch_fgemv(params(i % copies), nullptr);
+        for (int i = 0; i < iters; ++i) {
+            launch_fgemv(params(i % copies), nullptr, a, b);
+            MI_HIP(hipEventSynchronize(b));
+            float ms = 0;
+            MI_HIP(hipEventElapsedTime(&ms, a, b));
+            t.push_back(ms * 1000.0f);
+        }
+        hipEventDestroy(a);
+        hipEventDestroy(b);
+        std::sort(t.begin(), t.end());
+        *median_us = t[t.size() / 2];
+        if (bytes_out) *bytes_out = (int64_t)one * 2;
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t iters,
                          float* median_us) {
     try {

@@ -106,6 +106,10 @@ _SIGS = {
     "mi_decode_path": (C.c_int32, [_P]),
     "mi_op_dgemv": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_op_fgemv": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_op_fgemv_bench": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                      C.POINTER(C.c_int64)]),
     "mi_prof_bytes": (C.c_int64, [_P]),
     "mi_debug_stamps": (C.c_int32, [_P, _P, C.c_int32]),
     "mi_op_gemv": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
@@ -490,6 +494,29 @@ def op_dgemv(role: int, type_: int, raw: np.ndarray, rows: int, K: int, x: np.nd
                            _ptr(x), _ptr(r) if r is not None else None, _ptr(y))
     _check(rc, "op_dgemv")
     return y
+
+
+def op_fgemv(role: int, w: np.ndarray, x: np.ndarray, w2=None, resid=None, device: int = 0) -> np.ndarray:
+    """mi_op_fgemv: the F16 decode step's streaming GEMV launch of `role` (0 Q/K/V rows without RoPE,
+    1 residual add, 2 SwiGLU pair, 3 store) over float16 matrices w [rows][K] (and w2)."""
+    w = np.ascontiguousarray(w, dtype=np.float16)
+    rows, K = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w2 = None if w2 is None else np.ascontiguousarray(w2, dtype=np.float16)
+    rows2 = 0 if w2 is None else w2.shape[0]
+    y = np.empty(rows + (rows2 if role == 0 else 0), np.float32)
+    r = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
+    rc = lib().mi_op_fgemv(device, role, w.ctypes.data, rows, K, w2.ctypes.data if w2 is not None else None, rows2,
+                           _ptr(x), _ptr(r) if r is not None else None, _ptr(y))
+    _check(rc, "op_fgemv")
+    return y
+
+
+def op_fgemv_bench(role: int, rows: int, K: int, iters: int = 100, device: int = 0):
+    """(median microseconds, matrix bytes) of one fgemv launch of `role` over rows x K F16 matrices."""
+    us, nb = C.c_float(), C.c_int64()
+    _check(lib().mi_op_fgemv_bench(device, role, rows, K, iters, C.byref(us), C.byref(nb)), "op_fgemv_bench")
+    return us.value, nb.value
 
 
 def op_gemv_bench(type_: int, raw: np.ndarray, rows: int, K: int, iters: int = 100, device: int = 0) -> float:

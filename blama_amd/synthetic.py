@@ -49,6 +49,7 @@ class LlamaConfig:
     rope_freqs: bool = False          # an F32 rope_freqs.weight of n_rot/2 frequency factors (Llama-3.1)
     init: str = ""                    # _init_params overrides of this config, "key=value,..." as BLAMA_SYNTH_INIT
     pooling_type: int = -1            # >= 0: written as {arch}.pooling_type (llama_pooling_type)
+    tied_head: bool = False           # ftype "F16": no output.weight, the head is token_embd (Llama-3.2)
 
     @property
     def head_dim(self):
@@ -103,6 +104,20 @@ CONFIGS = {
                                   arch="gpt2"),
 }
 
+# Unquantised F16 files (every matrix F16; a table of their own: CONFIGS' "tiny-" names are the
+# quantised decode paths): GQA 2 with heads of 64; heads of 128 with a tied output head (no
+# output.weight); rope_freqs + linear scaling + partial rotary with O(1) scores
+F16_CONFIGS = {
+    "tiny-f16": LlamaConfig("tiny-f16", 512, 256, 2, 4, 2, 768, 1024, 10000.0, 1e-5, "F16"),
+    "tiny-f16-hd128": LlamaConfig("tiny-f16-hd128", 384, 512, 2, 4, 4, 1024, 1024, 10000.0, 1e-5, "F16",
+                                  tied_head=True),
+    "tiny-rf-f16": LlamaConfig("tiny-rf-f16", 512, 256, 2, 4, 2, 768, 1024, 10000.0, 1e-5, "F16",
+                               n_rot=32, rope_scale=4.0, rope_freqs=True, init="qk=0.3"),
+    # benchmark shapes (scripts/f16_bench.py)
+    "tinyllama-1.1b-f16": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "F16"),
+    "llama2-7b-f16": LlamaConfig("Llama-2-7B", 32000, 4096, 32, 32, 32, 11008, 4096, 10000.0, 1e-5, "F16"),
+}
+
 
 def use_more_bits(i: int, n: int) -> bool:
     # llama-quant.cpp use_more_bits
@@ -149,9 +164,12 @@ def _gpt2_shapes(cfg) -> dict:
 def tensor_types(cfg: LlamaConfig) -> dict:
     """name -> ggml type for every weight (the Q*_K_M mixes of llama_tensor_get_type)."""
     base = {"Q4_K_M": Q4_K, "Q5_K_M": Q5_K, "Q6_K": Q6_K, "Q8_0": Q8_0, "Q4_K": Q4_K,
-            "Q5_K": Q5_K}[cfg.ftype]
+            "Q5_K": Q5_K, "F16": F16}[cfg.ftype]
     if cfg.arch == "gpt2":
         return _gpt2_types(cfg, base)
+    if base == F16:   # the unquantised file convert_hf_to_gguf writes: every matrix F16, the rest F32
+        t = {n: (F32 if len(sh) == 1 or n.endswith("ffn_gate_inp.weight") else F16) for n, sh in tensor_shapes(cfg).items()}
+        return t
     mixed = cfg.ftype in ("Q4_K_M", "Q5_K_M")
     t = {"token_embd.weight": base, "output_norm.weight": F32,
          "output.weight": Q8_0 if base == Q8_0 else Q6_K}
@@ -193,6 +211,8 @@ def tensor_shapes(cfg: LlamaConfig) -> dict:
     d, kv = cfg.n_embd, cfg.n_head_kv * cfg.head_dim
     s = {"token_embd.weight": (d, cfg.n_vocab), "output_norm.weight": (d,),
          "output.weight": (d, cfg.n_vocab)}
+    if cfg.tied_head:
+        del s["output.weight"]
     if cfg.rope_freqs:
         s["rope_freqs.weight"] = (cfg.rot_dim // 2,)
     for i in range(cfg.n_layer):
@@ -406,7 +426,7 @@ def _init_params(cfg):
     env = dict(kv.split("=") for kv in (cfg.init + "," + os.environ.get("BLAMA_SYNTH_INIT", "")).split(",") if kv)
     p = {"base": 0.03, "qk": 0.01, "resid": 0.03 / np.sqrt(2.0 * cfg.n_layer), "embd": 8.0,
          "alpha": 0.01, "nsucc": 10}
-    if cfg.arch == "gpt2":
+    if cfg.arch == "gpt2" or cfg.tied_head:
         p["embd"] = 1.0   # the embedding is also the (tied) output head: logits O(sqrt(d))
     for k, v in env.items():
         p[k] = float(v)
@@ -508,16 +528,19 @@ def bpe_vocab(n_vocab: int, n_merges_vocab: int = 800) -> dict:
                 eot=base + 2, tokenizer=tok)
 
 
-def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab: dict | None = None) -> np.ndarray:
+def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab: dict | None = None,
+               types_override: dict | None = None) -> np.ndarray:
     """The whole synthetic GGUF file as one uint8 array (header_only: just the
     metadata + tensor table, enough for a vocab-only or no_upload replica load).
-    vocab: a byte-level BPE vocabulary from bpe_vocab() instead of the SPM one."""
+    vocab: a byte-level BPE vocabulary from bpe_vocab() instead of the SPM one.
+    types_override (header_only): name -> ggml type written in place of tensor_types' (files a
+    loader must refuse)."""
     w = gguf.GGUFWriter()
     arch = cfg.arch
     w.add_str("general.architecture", arch)
     w.add_str("general.name", f"synthetic {cfg.name} {cfg.ftype}")
     w.add_u32("general.file_type", {"Q8_0": 7, "Q4_K_M": 15, "Q5_K_M": 17, "Q6_K": 18,
-                                    "Q4_K": 15, "Q5_K": 17}[cfg.ftype])
+                                    "Q4_K": 15, "Q5_K": 17, "F16": 1}[cfg.ftype])
     w.add_u32(f"{arch}.context_length", cfg.n_ctx_train)
     w.add_u32(f"{arch}.embedding_length", cfg.n_embd)
     w.add_u32(f"{arch}.block_count", cfg.n_layer)
@@ -564,6 +587,9 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     w.add_bool("tokenizer.ggml.add_bos_token", arch != "gpt2")
     types = tensor_types(cfg)
     shapes = tensor_shapes(cfg)
+    if types_override:
+        assert header_only
+        types.update(types_override)
     for name in types:
         w.add_tensor(name, types[name], shapes[name])
 

@@ -39,6 +39,17 @@ const char* mi_last_error(void);
 
 /* ---- model: replaces llama_model_load_from_file / llama_model_free
  *      (Model.cpp:52, Model.hpp:55) ---- */
+/* Weight types served: quantised models (layer matrices and output head Q4_K / Q5_K / Q6_K / Q8_0),
+ * BERT encoders (F16), and unquantised dense LLaMA-graph models (general.architecture "llama",
+ * no experts) whose matrices -- token_embd, output and the seven per layer -- are all F16 with F32
+ * norm weights and rope_freqs; without output.weight the head is token_embd (tied models such as
+ * Llama-3.2).  Shape rules of an F16 model: embedding_length = head_count x head_dim, head_count a
+ * multiple of head_count_kv; embedding_length and feed_forward_length multiples of 32, at most
+ * 16384; head_count_kv x head_dim and the vocabulary size multiples of 32; rope.dimension_count
+ * even.  Refused at load (vocab_only included), each with a message naming the tensor and the
+ * reason: BF16 matrices, F32 matrices, a file mixing F16 and quantised matrices, F16 MoE, F16
+ * GPT-2, a shape outside the rules.  mi_lora_load and mi_ctx_set_lora refuse an F16 base model:
+ * LoRA on unquantised models is not implemented. */
 mi_model* mi_model_load(const char* gguf_path, const mi_model_params* params);
 /* Same, from a GGUF image in host memory (with no_upload/vocab_only only the
  * header -- metadata and tensor infos -- needs to be present). */
@@ -76,8 +87,9 @@ int32_t mi_model_meta_str(const mi_model* model, const char* key, char* buf, int
  * mi_model_merge returns the length of merge i ("left right") or < 0. */
 int32_t mi_model_n_merges(const mi_model* model);
 int32_t mi_model_merge(const mi_model* model, int32_t i, char* buf, int32_t size);
-/* Bytes of quantised weights a decode step streams (all tensors but tok_embd; of an MoE expert
- * tensor only the n_expert_used experts a token is routed to). */
+/* Bytes of weights a decode step streams (all tensors but tok_embd -- included when it is also the
+ * output head; of an MoE expert tensor only the n_expert_used experts a token is routed to); for
+ * an F16 model the F16 bytes. */
 int64_t mi_model_weight_bytes(const mi_model* model);
 /* The device weight arena (one allocation) -- for the replica broadcast. */
 int32_t mi_model_arena(const mi_model* model, void** dev_ptr, size_t* bytes);
@@ -256,7 +268,8 @@ int64_t mi_prof_bytes(const mi_ctx* ctx);
 /* Diagnostics: the form the context's decode steps take: 1 the streaming GEMV
  * launches (dgemv.hip; MoE: the attention half, the experts on gemv_kernel), 0 the gemv_kernel graph
  * (GPT-2), 2 an encoder context (bert: no decode step, one stateless pass per call on the kernels
- * of enc.hip); -1 for a null context. */
+ * of enc.hip), 3 an unquantised F16 LLaMA model (the F16 streaming GEMV launches of fgemv.hip; prompt
+ * batches on the F16 MFMA GEMM of enc.hip); -1 for a null context. */
 int32_t mi_decode_path(const mi_ctx* ctx);
 /* Diagnostics: copies the per-workgroup s_memrealtime stamps (100 MHz) of the
  * first n_launch launches of the last decode step, [launch][512][8] uint64, to
@@ -309,6 +322,19 @@ int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv,
  * of small models).  type2/raw2/rows2: the second matrix (raw2 NULL: none). */
 int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                     int32_t type2, const void* raw_blocks2, int32_t rows2, const float* x, const float* resid, float* y);
+/* The F16 decode step's streaming GEMV (fgemv.hip), one launch over F16 matrices [rows][K] (K a
+ * multiple of 32, 32 .. 16384): y[r] = sum_k f16(x[k]) * W[r][k] in f32, then the role's epilogue --
+ * 0 Q/K/V rows without RoPE, every row a Q row (a second matrix = further rows; y = [A x | B x],
+ * both row counts even), 1 y = A x + resid, 2 y = silu(A x) * (B x) (gate/up pair, rows2 == rows),
+ * 3 y = A x.  w2_f16 NULL: no second matrix. */
+int32_t mi_op_fgemv(int32_t device, int32_t role, const uint16_t* w_f16, int32_t rows, int32_t K,
+                    const uint16_t* w2_f16, int32_t rows2, const float* x, const float* resid, float* y);
+/* Median microseconds of one fgemv launch of `role` over rows x K F16 matrices (role 2: a gate/up
+ * pair of rows each), timed at the kernel's own start and end over `iters` launches after a warm-up,
+ * each reading another copy of the weights (HBM, not the Infinity Cache).  bytes (nullable): the
+ * matrix bytes one launch reads.  rows even. */
+int32_t mi_op_fgemv_bench(int32_t device, int32_t role, int32_t rows, int32_t K, int32_t iters, float* median_us,
+                          int64_t* bytes);
 /* ---- the mixture-of-experts kernels, one at a time (build_moe_ffn: softmax gating, top-2) ----
  * The router of ntok token rows x[t * x_stride] (n_embd floats each, x_stride >= n_embd, a
  * multiple of 4): rms_norm(x, eps) * norm_w, logits against w [n_expert][n_embd] (F32), softmax,
