@@ -239,11 +239,11 @@ void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
     const Layer& L = m->layers[l];
     const int cap = moe_route(l, nt, pend);
     // gate/up + SwiGLU: rms_norm(x) * ffn_norm of each row's token
-    const ActQ8 act = moe_act(hp.n_embd, cap, L.gate.type == T_Q8_0);
+    const ActQ8 act = moe_act(hp.n_embd, cap, takes_q80(L.gate.type));
     launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
     launch_mmq32(mmq32_params(L.gate, &L.up, cap, tokpos_b, hb, hp.n_ff, moe_grp, nt), act, ub_rope, stream);
     // down: every row of the FFN output, stored (weighted and summed by the combine)
-    const ActQ8 a2 = moe_act(hp.n_ff, cap, L.down.type == T_Q8_0);
+    const ActQ8 a2 = moe_act(hp.n_ff, cap, takes_q80(L.down.type));
     launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel);
     launch_mmq32(mmq32_params(L.down, nullptr, cap, tokpos_b, yb, hp.n_embd, moe_grp, nt), a2, ub_rope, stream);
     launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
@@ -271,7 +271,7 @@ void Ctx::moe_ffn_short(int l, int nt) {
 }
 
 ActQ8 Ctx::ub_act(int K, int ntok, int type) const {
-    const bool q80 = type == T_Q8_0;
+    const bool q80 = takes_q80(type);
     const bool second = q80 && !ub_q80 && ub_q0;   // the Q8_0 set of a mixed model
     ActQ8 a;
     a.q = second ? ub_q0 : ub_q;

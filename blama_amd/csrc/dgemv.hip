@@ -334,11 +334,15 @@ DvFn dv_fn_t1(int t1, int c) {
 }
 template <int ROLE, bool LORA>
 DvFn dv_fn_role(int t0, int t1, int c) {
+    constexpr int RW = (dv_base(ROLE) == DV_QKV || dv_base(ROLE) == DV_SWIGLU) ? 2 : 1;
     switch (t0) {
     case T_Q4_K: return dv_fn_t1<T_Q4_K, ROLE, LORA>(t1, c);
     case T_Q5_K: return dv_fn_t1<T_Q5_K, ROLE, LORA>(t1, c);
     case T_Q6_K: return t1 == T_Q6_K ? nullptr : dv_fn_t1<T_Q6_K, ROLE, LORA>(t1, c);
     case T_Q8_0: return t1 >= 0 ? nullptr : dv_fn_t1<T_Q8_0, ROLE, LORA>(t1, c);
+    // Q4_0 / Q5_0: one type per launch (llama-quantize gives Q, K and V one type)
+    case T_Q4_0: return t1 >= 0 ? nullptr : dv_fn_c<T_Q4_0, -1, RW, ROLE, LORA>(c);
+    case T_Q5_0: return t1 >= 0 ? nullptr : dv_fn_c<T_Q5_0, -1, RW, ROLE, LORA>(c);
     default: return nullptr;
     }
 }

@@ -46,7 +46,7 @@ int dev_chain_contexts(int device) { return dev_chain(device).nctx.load(); }
 
 int act_fmt(std::initializer_list<int> types) {
     int f = 0;
-    for (int t : types) f |= t == T_Q8_0 ? 2 : 1;
+    for (int t : types) f |= takes_q80(t) ? 2 : 1;
     return f;
 }
 
@@ -197,7 +197,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
         for (const Layer& L : m->layers)
             for (const QMat* q : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down}) {
                 mmq_ok = mmq_ok && mmq32_supported(q->type);
-                (q->type == T_Q8_0 ? any_0 : any_k) = true;
+                (takes_q80(q->type) ? any_0 : any_k) = true;
             }
         // the gate/up pair shares one MFMA-order copy (16 gate + 16 up rows per tile)
         for (const Layer& L : m->layers)

@@ -115,6 +115,13 @@ struct Model {
     // adapters on an F16 model are out of scope: Lora::load refuses it.
     bool f16 = false;
     bool check_f16() const;
+    // Q4_0 / Q5_0 matrices (32-weight blocks, f16 scale, Q8_0 activations as Q8_0's): served in a
+    // dense LLaMA graph, alone (llama-quantize's Q4_0 / Q5_0 files, head Q6_K) or inside a k-quant
+    // file.  check_types reads the header only: true when a matrix has one of the two types; refuses,
+    // with the tensor and the type's name, such a matrix in a MoE, GPT-2 or BERT model and a matrix of
+    // a quantised type no kernel here reads (Q4_1, Q5_1 -- Q8_1 activations --, Q2_K, Q3_K, IQ*, TQ*).
+    bool legacy = false;
+    bool check_types() const;
     void account(const GgufTensor& t, int experts);   // weight_bytes, type_bytes
 
     uint8_t* arena = nullptr;

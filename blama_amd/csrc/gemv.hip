@@ -157,14 +157,26 @@ template <> struct GvAct<T_Q8_0> {
         return r;
     }
 };
+template <> struct GvAct<T_Q4_0> {
+    __device__ static Kq<T_Q4_0>::AR get(const char* s, const GvLds& L, int sb, int j) {
+        const char* ab = s + L.q80 + sb * GV_ASTR + 32 * j;
+        return ar_q80s(*reinterpret_cast<const i32x4*>(ab), *reinterpret_cast<const i32x4*>(ab + 16),
+                       reinterpret_cast<const float*>(s + L.d0)[sb * 8 + j]);
+    }
+};
+template <> struct GvAct<T_Q5_0> {
+    __device__ static Kq<T_Q5_0>::AR get(const char* s, const GvLds& L, int sb, int j) {
+        return GvAct<T_Q4_0>::get(s, L, sb, j);
+    }
+};
 
 // Which activation formats a workgroup of segment types (T0, T1) must build.
-template <int T> __host__ __device__ constexpr bool gv_q80() { return T == T_Q8_0; }
+template <int T> __host__ __device__ constexpr bool gv_q80() { return T == T_Q8_0 || T == T_Q4_0 || T == T_Q5_0; }
 
 // Loads of one ring item row (Kq<T>::bload): the persistent prefill waits for everything but
 // these (vmcnt counts loads and stores in issue order).
 template <int T> __host__ __device__ constexpr int gv_nl() {
-    return T == T_Q4_K ? 2 : T == T_Q5_K ? 3 : T == T_Q6_K ? 4 : 3;
+    return T == T_Q4_K || T == T_Q4_0 ? 2 : T == T_Q5_K ? 3 : T == T_Q6_K ? 4 : 3;
 }
 template <int N> __device__ __forceinline__ void wait_vm() {   // s_waitcnt vmcnt(N) only
     static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
@@ -932,9 +944,24 @@ GvFn gv_fn_pair(int t1, int kb, int tag) {
     default: return nullptr;
     }
 }
+// Q4_0 / Q5_0: one segment or two of the same type (llama-quantize gives Q, K and V one type; a
+// mixed-type Q/K/V of these runs as one launch per type group)
+template <int T0, int RW>
+GvFn gv_fn_same(int t1, int kb, int tag) {
+    switch (t1) {
+    case -1: return tag == 2 ? nullptr
+                  : tag == 4 ? (RW == 2 ? gv_fn_kb<T0, -1, RW, 4>(kb) : gv_fn_kb<T0, -1, RW, 3>(kb))
+                  : tag == 3 ? gv_fn_kb<T0, -1, RW, 3>(kb)
+                  : tag && RW == 2 ? gv_fn_kb<T0, -1, RW, 1>(kb) : gv_fn_kb<T0, -1, RW, 0>(kb);
+    case -2: return tag >= 3 ? gv_fn_kb<T0, -2, RW, 3>(kb) : gv_fn_kb<T0, -2, RW, 0>(kb);
+    default: return nullptr;
+    }
+}
 template <int RW>
 GvFn gv_fn_rw(int t0, int t1, int kb, int tag) {
     switch (t0) {
+    case T_Q4_0: return gv_fn_same<T_Q4_0, RW>(t1, kb, tag);
+    case T_Q5_0: return gv_fn_same<T_Q5_0, RW>(t1, kb, tag);
     case T_Q4_K: return gv_fn_pair<T_Q4_K, RW>(t1, kb, tag);
     case T_Q5_K: return gv_fn_pair<T_Q5_K, RW>(t1, kb, tag);
     case T_Q6_K: return t1 == T_Q6_K ? nullptr : gv_fn_pair<T_Q6_K, RW>(t1, kb, tag);
@@ -993,7 +1020,7 @@ int gemv_grid(const GemvParams& p) {
 
 void init_kernel_attributes() {
     init_gemm_attributes();
-    const int types[4] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0};
+    const int types[6] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0};
     for (int rw = 1; rw <= 2; ++rw)
         for (int kb : {1, 2, 4})
             for (int t0 : types)

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
 typedef void (*GemmFn)(const GemmParams);
 static GemmFn gemm_fn(int type, bool pre);
 void init_gemm_attributes() {
-    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
+    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0})
         for (bool pre : {false, true})
             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t, pre)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -259,6 +259,8 @@ static GemmFn gemm_fn(int type, bool pre) {
     case T_Q5_K: return pre ? gemm_t<T_Q5_K, 4, true> : gemm_t<T_Q5_K, 4, false>;
     case T_Q6_K: return pre ? gemm_t<T_Q6_K, 4, true> : gemm_t<T_Q6_K, 4, false>;
     case T_Q8_0: return pre ? gemm_t<T_Q8_0, 4, true> : gemm_t<T_Q8_0, 4, false>;
+    case T_Q4_0: return pre ? gemm_t<T_Q4_0, 4, true> : gemm_t<T_Q4_0, 4, false>;
+    case T_Q5_0: return pre ? gemm_t<T_Q5_0, 4, true> : gemm_t<T_Q5_0, 4, false>;
     default: return nullptr;
     }
 }
@@ -274,8 +276,8 @@ void launch_gemm(const GemmParams& p_in, hipStream_t s) {
     if (p.ntok < 1 || p.ntok > GEMM_NT) throw Error("gemm: 1..GEMM_NT tokens per launch");
     if (p.pair == PAIR_AB && p.B.type != p.A.type) throw Error("gemm: a pair must share its quant type");
     if (p.epi == EPI_MOE_DOWN) throw Error("gemm: MoE launches are served token by token");
-    p.need_q8k = p.A.type != T_Q8_0;
-    p.need_q80 = p.A.type == T_Q8_0;
+    p.need_q8k = !takes_q80(p.A.type);
+    p.need_q80 = takes_q80(p.A.type);
     const int g = (p.units + 7) / 8;
     p.grid = g < 1 ? 1 : (g > 256 ? 256 : g);
     if ((long long)p.units * p.grid * 8 >= (1LL << 32)) throw Error("gemm: too many units");
@@ -338,6 +340,20 @@ __device__ float dequant_elem(const QMat& M, long long row, int col) {
         const int8_t q = reinterpret_cast<const int8_t*>(M.p[0] + sbi * 256)[i];
         const uint8_t* dp = M.p[1] + sbi * 16 + (i >> 5) * 2;
         return (float)q * h2f(dp[0] | (dp[1] << 8));
+    }
+    case T_Q4_0:
+    case T_Q5_0: {   // dequantize_row_q4_0 / _q5_0: element l of block blk, (q - 8 or 16) * d
+        const bool q5 = M.type == T_Q5_0;
+        const int blk = i >> 5, l = i & 31;
+        const uint8_t b = M.p[0][sbi * 128 + blk * 16 + (l & 15)];
+        int q = l < 16 ? (b & 0xF) : (b >> 4);
+        if (q5) {
+            const uint8_t* h = M.p[1] + sbi * 32 + blk * 4;
+            const unsigned qh = h[0] | (h[1] << 8) | (h[2] << 16) | ((unsigned)h[3] << 24);
+            q |= (int)((qh >> l) & 1u) << 4;
+        }
+        const uint8_t* dp = M.p[q5 ? 2 : 1] + sbi * 16 + blk * 2;
+        return (float)(q - (q5 ? 16 : 8)) * h2f(dp[0] | (dp[1] << 8));
     }
     case T_F32:
         return reinterpret_cast<const float*>(M.p[0])[row * M.K + col];
@@ -760,6 +776,21 @@ __global__ void repack_kernel(const uint8_t* raw, int type, long long nsb, uint8
                 p1[i * 16 + blk * 2] = b[blk * 34];
                 p1[i * 16 + blk * 2 + 1] = b[blk * 34 + 1];
                 for (int k = 0; k < 32; ++k) p0[i * 256 + blk * 32 + k] = b[blk * 34 + 2 + k];
+            }
+        } else if (type == T_Q4_0) {
+            const uint8_t* b = raw + i * 144;   // 8 blocks of 18: f16 d, qs[16]
+            for (int blk = 0; blk < 8; ++blk) {
+                p1[i * 16 + blk * 2] = b[blk * 18];
+                p1[i * 16 + blk * 2 + 1] = b[blk * 18 + 1];
+                for (int k = 0; k < 16; ++k) p0[i * 128 + blk * 16 + k] = b[blk * 18 + 2 + k];
+            }
+        } else if (type == T_Q5_0) {
+            const uint8_t* b = raw + i * 176;   // 8 blocks of 22: f16 d, qh[4], qs[16]
+            for (int blk = 0; blk < 8; ++blk) {
+                p2[i * 16 + blk * 2] = b[blk * 22];
+                p2[i * 16 + blk * 2 + 1] = b[blk * 22 + 1];
+                for (int k = 0; k < 4; ++k) p1[i * 32 + blk * 4 + k] = b[blk * 22 + 2 + k];
+                for (int k = 0; k < 16; ++k) p0[i * 128 + blk * 16 + k] = b[blk * 22 + 6 + k];
             }
         }
     }

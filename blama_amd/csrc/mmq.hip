@@ -299,9 +299,15 @@ __device__ __forceinline__ void q4k_scales(const u32x4 hd, int sc[8], int mn[8])
 //         folded into the operand, one MFMA per span and operand carries the exact integer sum)
 //   Q8_0  [j 8][lane 64][16] qs bytes 32j + 16h.. | [c 32][8 f16] d                            8704 B
 //   Q5_K  as Q4_K, plus [lane 64][16] qh bytes 16h..: [p 4][lane][16] qs | qh | [c 32][16] header 5632 B
+//   Q4_0 / Q5_0  the Q8_0 tile of the same blocks: every block is the Q8_0 block with the same d and
+//         qs[i] = the signed weight (q - 8, q - 16), expanded to int8 once when the copy is built, so
+//         the GEMMs below run their Q8_0 form on it (mmq_op_type) with the same exact int32 sums    8704 B
 __host__ __device__ constexpr int mmq32_tile_bytes_d(int type) {
-    return type == T_Q4_K ? 4608 : type == T_Q5_K ? 5632 : type == T_Q6_K ? 16448 : type == T_Q8_0 ? 8704 : 0;
+    return type == T_Q4_K ? 4608 : type == T_Q5_K ? 5632 : type == T_Q6_K ? 16448
+         : (type == T_Q8_0 || type == T_Q4_0 || type == T_Q5_0) ? 8704 : 0;
 }
+// the operand format of a type's MFMA-order copy: the kernels' template type
+__host__ __device__ constexpr int mmq_op_type(int type) { return (type == T_Q4_0 || type == T_Q5_0) ? (int)T_Q8_0 : type; }
 
 __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* dst) {
     const int nb = A.nb;
@@ -311,7 +317,27 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
     uint8_t* o = dst + tile * TB;
     for (int off = threadIdx.x; off < TB; off += blockDim.x) {
         int plane, c, byte;
-        if (A.type == T_Q8_0) {
+        if (A.type == T_Q4_0 || A.type == T_Q5_0) {
+            const bool q5 = A.type == T_Q5_0;
+            if (off < 8192) {   // element l = 16h + e of block jj as int8: the nibble (| the qh bit) - 8 (16)
+                const int jj = off >> 10, ln = (off >> 4) & 63, e = off & 15;
+                const int cc = ln & 31, l = 16 * (ln >> 5) + e;
+                const QMat& M = (pair && cc >= 16) ? B : A;
+                long long row = pair ? 16LL * rt + (cc & 15) : 32LL * rt + cc;
+                if (row >= M.rows) row = M.rows - 1;
+                const long long b = row * nb + sb;
+                const uint8_t qb = M.p[0][b * 128 + jj * 16 + (l & 15)];
+                int q = l < 16 ? (qb & 0xF) : (qb >> 4);
+                if (q5) {
+                    const uint8_t* hp = M.p[1] + b * 32 + jj * 4;
+                    const unsigned qh = hp[0] | (hp[1] << 8) | (hp[2] << 16) | ((unsigned)hp[3] << 24);
+                    q |= (int)((qh >> l) & 1u) << 4;
+                }
+                o[off] = (uint8_t)(int8_t)(q - (q5 ? 16 : 8));
+                continue;
+            }
+            plane = q5 ? 2 : 1; c = (off - 8192) >> 4; byte = (off - 8192) & 15;
+        } else if (A.type == T_Q8_0) {
             if (off < 8192) {
                 const int jj = off >> 10, ln = (off >> 4) & 63, e = off & 15;
                 plane = 0; c = ln & 31; byte = 32 * jj + 16 * (ln >> 5) + e;
@@ -357,7 +383,8 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
         const QMat& M = (pair && c >= 16) ? B : A;
         long long row = pair ? 16LL * rt + (c & 15) : 32LL * rt + c;
         if (row >= M.rows) row = M.rows - 1;
-        const int pb = A.type == T_Q8_0 ? (plane == 0 ? 256 : 16)
+        const int pb = (A.type == T_Q4_0 || A.type == T_Q5_0) ? 16
+                     : A.type == T_Q8_0 ? (plane == 0 ? 256 : 16)
                      : A.type == T_Q4_K ? (plane == 0 ? 128 : 16)
                      : A.type == T_Q5_K ? (plane == 0 ? 128 : plane == 1 ? 32 : 16)
                                         : (plane == 0 ? 128 : plane == 1 ? 64 : plane == 2 ? 16 : 2);
@@ -1445,7 +1472,9 @@ void launch_rope_table(const int* tokpos, int ntok, int n_rot, float theta_scale
     MI_HIP(hipGetLastError());
 }
 
-bool mmq32_supported(int type) { return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0; }
+bool mmq32_supported(int type) {
+    return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0 || is_legacy_quant(type);
+}
 
 int mmq32_tile_bytes(int type) { return mmq::mmq32_tile_bytes_d(type); }
 
@@ -1468,7 +1497,7 @@ bool mmq2_enabled() { return true; }
 // one mmq2 launch over the segments S (all of p.A's type; one segment unless launch_mmq32_multi)
 void launch_mmq2(const GemmParams& p, const mmq::MmqSegs& S, const ActQ8& act, const float2* rope, hipStream_t s) {
     const bool ab = p.pair == PAIR_AB;
-    const int T = p.A.type;
+    const int T = mmq::mmq_op_type(p.A.type);
     const int RT = mmq::M2<T_Q4_K>::RT;
     const int NWv = 4 * RT;
     int nrb = 0;
@@ -1534,7 +1563,7 @@ void launch_mmq32_multi(const GemmParams* ps, int n, const ActQ8& act, const flo
             throw Error("mmq32 multi: the segments share one output buffer");
     }
     if (!mmq32_supported(ps[0].A.type)) throw Error("mmq32: Q4_K / Q5_K / Q6_K / Q8_0 only");
-    if ((ps[0].A.type == T_Q8_0) != (act.q80 != 0)) throw Error("mmq32: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
+    if (takes_q80(ps[0].A.type) != (act.q80 != 0)) throw Error("mmq32: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
     if (act.K != ps[0].K) throw Error("mmq32: activation length differs from K");
     if (act.ntok < 1 || act.npad % 32 || act.npad > UB_MAX) throw Error("mmq32: bad token count");
     mmq::MmqSegs S{};
@@ -1554,7 +1583,7 @@ bool mmq2_active() { return mmq2_enabled(); }
 
 void launch_mmq32(const GemmParams& p, const ActQ8& act, const float2* rope, hipStream_t s) {
     if (!mmq32_supported(p.A.type)) throw Error("mmq32: Q4_K / Q5_K / Q6_K / Q8_0 only");
-    if ((p.A.type == T_Q8_0) != (act.q80 != 0)) throw Error("mmq32: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
+    if (takes_q80(p.A.type) != (act.q80 != 0)) throw Error("mmq32: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
     if (act.K != p.K || p.A.K != p.K) throw Error("mmq32: activation length differs from K");
     const bool ab = p.pair == PAIR_AB;
     if (ab && (p.B.type != p.A.type || p.B.rows != p.A.rows || p.epi != EPI_SWIGLU))
@@ -1582,8 +1611,8 @@ int mmqs_parts(int K) { return (K / 256 + mmq::MS_SBW - 1) / mmq::MS_SBW; }
 int launch_mmqs(const QMat* const* mats, const int* prow, int n, bool pair, int nff, const ActQ8& act, float* part,
                 int pstride, hipStream_t s) {
     if (n < 1 || n > mmq::MMQ_SEGS || (pair && n != 1)) throw Error("mmqs: 1..3 matrices (a pair: one)");
-    const int T = mats[0]->type;
-    if (!mmq32_supported(T)) throw Error("mmqs: Q4_K / Q5_K / Q6_K / Q8_0 only");
+    const int T = mmq::mmq_op_type(mats[0]->type);   // Q4_0 / Q5_0: their copies are Q8_0 tiles
+    if (!mmq32_supported(mats[0]->type)) throw Error("mmqs: Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
     if ((T == T_Q8_0) != (act.q80 != 0)) throw Error("mmqs: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
     if (act.ntok < 1 || act.ntok > MMQS_MAX || (act.npad != 32 && act.npad != 64) || act.npad < act.ntok)
         throw Error("mmqs: 1..64 tokens");
@@ -1592,7 +1621,7 @@ int launch_mmqs(const QMat* const* mats, const int* prow, int n, bool pair, int 
     M.n = n;
     for (int i = 0; i < n; ++i) {
         const QMat& A = *mats[i];
-        if (A.type != T || A.K != act.K || !A.sw) throw Error("mmqs: the matrices share type and K, with MFMA-order copies");
+        if (A.type != mats[0]->type || A.K != act.K || !A.sw) throw Error("mmqs: the matrices share type and K, with MFMA-order copies");
         M.sw[i] = A.sw;
         M.rows[i] = A.rows;
         M.nrt[i] = pair ? (A.rows + 15) / 16 : (A.rows + 31) / 32;

@@ -213,6 +213,37 @@ bool Model::check_f16() const {
     return true;
 }
 
+bool Model::check_types() const {
+    bool any = false;
+    // (a MoE model: its expert tensors first, so that the message names one of them)
+    std::vector<const GgufTensor*> order;
+    for (const GgufTensor& t : gguf.tensors)
+        if (t.name.find("_exps.") != std::string::npos) order.push_back(&t);
+    for (const GgufTensor& t : gguf.tensors)
+        if (t.name.find("_exps.") == std::string::npos) order.push_back(&t);
+    for (const GgufTensor* tp : order) {
+        const GgufTensor& t = *tp;
+        if (t.n_dims < 2) continue;   // matrices: the tables, the head, the layers' projections
+        const int ty = t.type;
+        if (is_legacy_quant(ty)) {
+            any = true;
+            const char* why = hp.arch == ARCH_GPT2 ? "a GPT-2 model" : hp.arch == ARCH_BERT ? "a BERT model"
+                            : hp.n_expert > 0 ? "a MoE model" : nullptr;
+            if (why)
+                throw Error("tensor " + t.name + ": " + type_name(ty) + " matrices are not served in " + why +
+                            " (Q4_0 / Q5_0 are read by the dense LLaMA kernels only)");
+            if (t.ne[0] % 256)
+                throw Error("tensor " + t.name + ": a " + type_name(ty) + " matrix needs a row length that is a multiple of 256");
+        } else if (ty != T_F32 && ty != T_F16 && ty != T_BF16 && !is_quant(ty) && block_bytes(ty) == 0) {
+            const bool q81 = ty == 3 || ty == 7;   // Q4_1, Q5_1
+            throw Error("tensor " + t.name + ": " + type_name(ty) + " matrices are not served" +
+                        (q81 ? " (they take Q8_1 activations; requantise to Q4_0, Q5_0, Q8_0 or a k-quant)"
+                             : " (served: Q4_0, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K, or F16 throughout)"));
+        }
+    }
+    return any;
+}
+
 Model::~Model() {
     if (arena || mmq_arena || gelu_tab) hipSetDevice(device);
     if (arena) hipFree(arena);
@@ -372,10 +403,12 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     eos = (int)gguf.get_int("tokenizer.ggml.eos_token_id", 2);
     eot = (int)gguf.get_int("tokenizer.ggml.eot_token_id", -1);
     add_bos = gguf.get_int("tokenizer.ggml.add_bos_token", 1) != 0;
+    legacy = check_types();
     if (!bert) f16 = check_f16();
     if (vocab_only) {
-        // an F16 model's weight bytes and type histogram are known from the header alone
-        if (f16) {
+        // an F16 model's weight bytes and type histogram are known from the header alone, and so
+        // are those of a file with Q4_0 / Q5_0 matrices (dense: every tensor streams whole)
+        if (f16 || legacy) {
             for (const GgufTensor& t : gguf.tensors) account(t, 1);
             if (!gguf.tensor("output.weight")) weight_bytes += (long long)gguf.tensor("token_embd.weight")->nbytes;   // tied head
         }
@@ -408,7 +441,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             pl.off[0] = off;
             off = align256(off + t->nbytes);
         } else {
-            throw Error("tensor " + name + ": unsupported ggml type " + std::to_string(t->type));
+            throw Error("tensor " + name + ": unsupported ggml type " + std::to_string(t->type) + " (" + type_name(t->type) + ")");
         }
         plan.push_back(pl);
         return (int)plan.size() - 1;

@@ -449,7 +449,7 @@ int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t
 int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
                    int32_t ntok, const float* x, float* y) {
     try {
-        if (!mmq32_supported(type)) throw Error("op_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
+        if (!mmq32_supported(type)) throw Error("op_gemm: Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
         if (ntok < 1 || ntok > UB_MAX) throw Error("op_gemm: 1..512 token rows");
         if (rows < 1 || K < 256 || K % 256) throw Error("op_gemm: bad shape");
         MI_HIP(hipSetDevice(device));
@@ -465,7 +465,7 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
         Dev<int8_t> dq(npad * K), dbs(npad * (K / 256) * 16);
         Dev<int> dtp((size_t)ntok * 4);
         dtp.fill(0);
-        ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, type == T_Q8_0 ? 1 : 0};
+        ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, takes_q80(type) ? 1 : 0};
         launch_quant_act(dx.p, K, nullptr, 0.0f, act, nullptr);
         // up to the short-batch limit: the short-batch GEMM (K-part sums, added by part_sum) as the
         // engine's verification batches take it; MI_MMQS_MAX=0: the tiled GEMM for every count
@@ -572,7 +572,7 @@ int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* r
     try {
         if (!raw || !x || !sel || !y) throw Error("op_moe_gemm: null argument");
         if (mode != 0 && mode != 1) throw Error("op_moe_gemm: mode 0 (tiled) or 1 (short)");
-        if (!mmq32_supported(type)) throw Error("op_moe_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
+        if (!mmq32_supported(type) || is_legacy_quant(type)) throw Error("op_moe_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
         if (mode == 1 && !mmqs_grouped_supported(type)) throw Error("op_moe_gemm: the short form takes Q4_K / Q5_K / Q6_K experts");
         if (ntok < 1 || ntok > (mode == 1 ? MMQS_MAX : UB_MAX)) throw Error("op_moe_gemm: 1..512 tokens (short form: 1..64)");
         if (n_expert < 2 || n_expert > MOE_GROUP_MAXE) throw Error("op_moe_gemm: 2..16 experts");
@@ -634,7 +634,7 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
                          const int32_t* sel, const float* selw, const float* addend, float* h_out, float* x_out) {
     try {
         if (!gate || !up || !down || !x || !norm_w || !sel || !selw || !h_out || !x_out) throw Error("op_moe_decode: null argument");
-        if (!is_quant(type)) throw Error("op_moe_decode: unsupported quant type");
+        if (!is_quant(type) || is_legacy_quant(type)) throw Error("op_moe_decode: unsupported quant type");
         if (n_expert < 1 || n_embd < 256 || n_embd % 256 || n_ff < 256 || n_ff % 256) throw Error("op_moe_decode: bad shape");
         for (int k = 0; k < 2; ++k)
             if (sel[k] < 0 || sel[k] >= n_expert) throw Error("op_moe_decode: expert out of range");

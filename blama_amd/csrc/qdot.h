@@ -52,6 +52,9 @@ __device__ __forceinline__ unsigned bld8x(const uint8_t* base, unsigned off, uns
     hi = v.y;
     return v.x;
 }
+__device__ __forceinline__ unsigned bld4(const uint8_t* base, unsigned off) {
+    return __builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(base), off, 0, 2);
+}
 __device__ __forceinline__ unsigned bld2(const uint8_t* base, unsigned off) {
     return __builtin_amdgcn_raw_buffer_load_b16(buf_rsrc(base), off, 0, 2);
 }
@@ -220,6 +223,8 @@ template <> struct PlaneBytes<T_Q4_K> { static constexpr int b[4] = {128, 16, 0,
 template <> struct PlaneBytes<T_Q5_K> { static constexpr int b[4] = {128, 32, 16, 0}; };
 template <> struct PlaneBytes<T_Q6_K> { static constexpr int b[4] = {128, 64, 16, 2}; };
 template <> struct PlaneBytes<T_Q8_0> { static constexpr int b[4] = {256, 16, 0, 0}; };
+template <> struct PlaneBytes<T_Q4_0> { static constexpr int b[4] = {128, 16, 0, 0}; };
+template <> struct PlaneBytes<T_Q5_0> { static constexpr int b[4] = {128, 32, 16, 0}; };
 
 template <> struct Kq<T_Q4_K> {
     static constexpr int LPS = 8;
@@ -441,6 +446,105 @@ template <> struct Kq<T_Q8_0> {
         s = dot4((int)l.q1.w, a1.w, s);
         const float d = h2f(l.d) * r.d0;   // fp16(x.d) * fp16(y.d), then * sumi
         return d * (float)s;
+    }
+};
+
+// Q4_0 / Q5_0 (vec_dot_q4_0_q8_0 / vec_dot_q5_0_q8_0): lane j owns block j of the superblock, as
+// for Q8_0, and reads its 16 nibble bytes in one aligned load.  Byte i of the block holds weight i
+// (low nibble) and weight i + 16 (high nibble), so the low nibbles of the four dwords meet the
+// first 16 activations of the Q8_0 block and the high nibbles the last 16.  The dots run on the
+// unsigned q (0..15, with the fifth bit 0..31); sum((q - OFF) * a) = sum(q * a) - OFF * sum(a) is
+// the same integer (|sum| <= 32 * 31 * 127), with sum(a) taken once per activation block (AR::asum).
+struct ArQ80S { i32x4 a0, a1; float d0; int asum; };
+__device__ __forceinline__ ArQ80S ar_q80s(const i32x4& a0, const i32x4& a1, float d0) {
+    ArQ80S r;
+    r.a0 = a0;
+    r.a1 = a1;
+    r.d0 = d0;
+    int s = 0;
+    s = dot4(0x01010101, a0.x, s);
+    s = dot4(0x01010101, a0.y, s);
+    s = dot4(0x01010101, a0.z, s);
+    s = dot4(0x01010101, a0.w, s);
+    s = dot4(0x01010101, a1.x, s);
+    s = dot4(0x01010101, a1.y, s);
+    s = dot4(0x01010101, a1.z, s);
+    s = dot4(0x01010101, a1.w, s);
+    r.asum = s;
+    return r;
+}
+
+template <> struct Kq<T_Q4_0> {
+    static constexpr int LPS = 8;
+    struct Ld { u32x4 qs; unsigned d; };
+    __device__ static Ld load(const uint8_t* const* rp, int sb, int j) {
+        Ld l;
+        l.qs = ldg16(rp[0] + sb * 128 + j * 16);
+        l.d = __builtin_nontemporal_load(gptr(reinterpret_cast<const unsigned short*>(rp[1] + sb * 16 + j * 2)));
+        return l;
+    }
+    __device__ static Ld bload(const uint8_t* const* rp, int sb, int j, bool park) {
+        Ld l;
+        l.qs = bld16(rp[0], oob(sb * 128 + j * 16, park));
+        l.d = bld2(rp[1], oob(sb * 16 + j * 2, park));
+        return l;
+    }
+    using AR = ArQ80S;
+    __device__ static AR act(const Act& a, int sb, int j) {
+        const int8_t* ab = a.q80 + sb * 256 + j * 32;
+        return ar_q80s(*reinterpret_cast<const i32x4*>(ab), *reinterpret_cast<const i32x4*>(ab + 16), a.d0[sb * 8 + j]);
+    }
+    __device__ static float dot(const Ld& l, const AR& r, int j) {
+        int s = 0;
+        s = dot4((int)(l.qs.x & 0x0F0F0F0Fu), r.a0.x, s);
+        s = dot4((int)(l.qs.y & 0x0F0F0F0Fu), r.a0.y, s);
+        s = dot4((int)(l.qs.z & 0x0F0F0F0Fu), r.a0.z, s);
+        s = dot4((int)(l.qs.w & 0x0F0F0F0Fu), r.a0.w, s);
+        s = dot4((int)((l.qs.x >> 4) & 0x0F0F0F0Fu), r.a1.x, s);
+        s = dot4((int)((l.qs.y >> 4) & 0x0F0F0F0Fu), r.a1.y, s);
+        s = dot4((int)((l.qs.z >> 4) & 0x0F0F0F0Fu), r.a1.z, s);
+        s = dot4((int)((l.qs.w >> 4) & 0x0F0F0F0Fu), r.a1.w, s);
+        const float d = h2f(l.d) * r.d0;
+        return d * (float)(s - 8 * r.asum);
+    }
+};
+
+template <> struct Kq<T_Q5_0> {
+    static constexpr int LPS = 8;
+    struct Ld { u32x4 qs; unsigned qh, d; };
+    __device__ static Ld load(const uint8_t* const* rp, int sb, int j) {
+        Ld l;
+        l.qs = ldg16(rp[0] + sb * 128 + j * 16);
+        l.qh = __builtin_nontemporal_load(gptr(reinterpret_cast<const unsigned*>(rp[1] + sb * 32 + j * 4)));
+        l.d = __builtin_nontemporal_load(gptr(reinterpret_cast<const unsigned short*>(rp[2] + sb * 16 + j * 2)));
+        return l;
+    }
+    __device__ static Ld bload(const uint8_t* const* rp, int sb, int j, bool park) {
+        Ld l;
+        l.qs = bld16(rp[0], oob(sb * 128 + j * 16, park));
+        l.qh = bld4(rp[1], oob(sb * 32 + j * 4, park));
+        l.d = bld2(rp[2], oob(sb * 16 + j * 2, park));
+        return l;
+    }
+    using AR = ArQ80S;
+    __device__ static AR act(const Act& a, int sb, int j) { return Kq<T_Q4_0>::act(a, sb, j); }
+    // bits 4 k .. 4 k + 3 of qh to bit 4 of bytes 0..3: the multiply puts bit b at 8 b (and at
+    // positions the mask drops; no two terms meet, so no carry)
+    __device__ static unsigned fifth(unsigned qh, int k) {
+        return ((((qh >> (4 * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+    }
+    __device__ static float dot(const Ld& l, const AR& r, int j) {
+        int s = 0;
+        s = dot4((int)((l.qs.x & 0x0F0F0F0Fu) | fifth(l.qh, 0)), r.a0.x, s);
+        s = dot4((int)((l.qs.y & 0x0F0F0F0Fu) | fifth(l.qh, 1)), r.a0.y, s);
+        s = dot4((int)((l.qs.z & 0x0F0F0F0Fu) | fifth(l.qh, 2)), r.a0.z, s);
+        s = dot4((int)((l.qs.w & 0x0F0F0F0Fu) | fifth(l.qh, 3)), r.a0.w, s);
+        s = dot4((int)(((l.qs.x >> 4) & 0x0F0F0F0Fu) | fifth(l.qh, 4)), r.a1.x, s);
+        s = dot4((int)(((l.qs.y >> 4) & 0x0F0F0F0Fu) | fifth(l.qh, 5)), r.a1.y, s);
+        s = dot4((int)(((l.qs.z >> 4) & 0x0F0F0F0Fu) | fifth(l.qh, 6)), r.a1.z, s);
+        s = dot4((int)(((l.qs.w >> 4) & 0x0F0F0F0Fu) | fifth(l.qh, 7)), r.a1.w, s);
+        const float d = h2f(l.d) * r.d0;
+        return d * (float)(s - 16 * r.asum);
     }
 };
 

@@ -32,8 +32,8 @@ _SCALAR_FMT = {T_UINT8: "<B", T_INT8: "<b", T_UINT16: "<H", T_INT16: "<h", T_UIN
                T_FLOAT64: "<d"}
 
 # ggml type -> (block elems, block bytes)
-GGML_BLOCK = {0: (1, 4), 1: (1, 2), 8: (32, 34), 12: (256, 144), 13: (256, 176),
-              14: (256, 210), 30: (1, 2)}
+GGML_BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34),
+              12: (256, 144), 13: (256, 176), 14: (256, 210), 30: (1, 2)}
 
 
 def tensor_nbytes(ggml_type: int, shape) -> int:

@@ -23,6 +23,7 @@ import numpy as np
 from . import gguf
 
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
+Q4_0, Q5_0 = 2, 6
 
 
 @dataclass(frozen=True)
@@ -118,6 +119,19 @@ F16_CONFIGS = {
     "llama2-7b-f16": LlamaConfig("Llama-2-7B", 32000, 4096, 32, 32, 32, 11008, 4096, 10000.0, 1e-5, "F16"),
 }
 
+# llama-quantize's classic Q4_0 / Q5_0 files (general.file_type 2 / 8): every matrix of the type,
+# output.weight Q6_K.  A table of their own, as F16_CONFIGS.  GQA 2 with heads of 64 (the streaming
+# decode step) and, in the shape of tiny-q8_0, heads of 32 (the gemv_kernel step)
+LEGACY_CONFIGS = {
+    "tiny-q4_0": LlamaConfig("tiny-q4_0", 512, 256, 2, 4, 2, 512, 256, 10000.0, 1e-5, "Q4_0"),
+    "tiny-q5_0": LlamaConfig("tiny-q5_0", 512, 256, 2, 4, 2, 512, 256, 10000.0, 1e-5, "Q5_0"),
+    "tiny-hd32-q4_0": LlamaConfig("tiny-hd32-q4_0", 384, 256, 2, 8, 4, 768, 256, 10000.0, 1e-6, "Q4_0"),
+    "tiny-hd32-q5_0": LlamaConfig("tiny-hd32-q5_0", 384, 256, 2, 8, 4, 768, 256, 10000.0, 1e-6, "Q5_0"),
+    # benchmark shapes (scripts/legacy_quant_bench.py)
+    "tinyllama-1.1b-q4_0": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q4_0"),
+    "tinyllama-1.1b-q5_0": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q5_0"),
+}
+
 
 def use_more_bits(i: int, n: int) -> bool:
     # llama-quant.cpp use_more_bits
@@ -164,7 +178,7 @@ def _gpt2_shapes(cfg) -> dict:
 def tensor_types(cfg: LlamaConfig) -> dict:
     """name -> ggml type for every weight (the Q*_K_M mixes of llama_tensor_get_type)."""
     base = {"Q4_K_M": Q4_K, "Q5_K_M": Q5_K, "Q6_K": Q6_K, "Q8_0": Q8_0, "Q4_K": Q4_K,
-            "Q5_K": Q5_K, "F16": F16}[cfg.ftype]
+            "Q5_K": Q5_K, "F16": F16, "Q4_0": Q4_0, "Q5_0": Q5_0}[cfg.ftype]
     if cfg.arch == "gpt2":
         return _gpt2_types(cfg, base)
     if base == F16:   # the unquantised file convert_hf_to_gguf writes: every matrix F16, the rest F32
@@ -292,6 +306,9 @@ def fill_quant(view: np.ndarray, t: int, rng, std: float = 0.03):
         elif t == Q8_0:
             d = (std / (256 / np.sqrt(12.0))) * rng.uniform(0.8, 1.2, n)
             b[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
+        elif t in (Q4_0, Q5_0):   # uniform 4- / 5-bit values around 8 / 16: std = d * levels / sqrt(12)
+            d = (std / ((16 if t == Q4_0 else 32) / np.sqrt(12.0))) * rng.uniform(0.8, 1.2, n)
+            b[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
         else:
             raise NotImplementedError(t)
 
@@ -314,6 +331,30 @@ def quantize_q8_0_rows(X):
     out = np.empty((X.shape[0], 34), np.uint8)
     out[:, 0:2] = d16.view(np.uint8).reshape(-1, 2)
     out[:, 2:] = q.astype(np.int8).view(np.uint8)
+    return out
+
+
+def quantize_q45_0_rows(X, q5: bool):
+    """(n, 32) blocks -> block_q4_0 (18 B) / block_q5_0 (22 B): d = amax / 7 (15), the level
+    nearest to x / d (within half a quantum of x), stored + 8 (+ 16): weight j in the low nibble of qs[j],
+    weight j + 16 in the high one, the fifth bits of weights 0..31 in the little-endian u32 qh."""
+    X = X.reshape(-1, 32)
+    n = X.shape[0]
+    off = 16 if q5 else 8
+    d16 = _f16(np.abs(X).max(1) / (off - 1.0))
+    d = d16.astype(np.float32)
+    q = np.clip(np.rint(np.divide(X, d[:, None], out=np.zeros_like(X), where=d[:, None] > 0)), -off, off - 1)
+    q = q.astype(np.int32) + off
+    lo, hi = q[:, :16], q[:, 16:]
+    out = np.empty((n, 22 if q5 else 18), np.uint8)
+    out[:, 0:2] = d16.view(np.uint8).reshape(n, 2)
+    qs = ((lo & 0xF) | ((hi & 0xF) << 4)).astype(np.uint8)
+    if q5:
+        qh = (((q >> 4) & 1).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(1, dtype=np.uint32)
+        out[:, 2:6] = qh.astype("<u4").view(np.uint8).reshape(n, 4)
+        out[:, 6:22] = qs
+    else:
+        out[:, 2:18] = qs
     return out
 
 
@@ -386,6 +427,8 @@ def quantize_rows(X, t: int) -> np.ndarray:
         return quantize_q6_K_rows(X).reshape(-1)
     if t in (Q4_K, Q5_K):
         return quantize_q45_K_rows(X, t == Q5_K).reshape(-1)
+    if t in (Q4_0, Q5_0):
+        return quantize_q45_0_rows(X, t == Q5_0).reshape(-1)
     if t == F32:
         return X.reshape(-1).view(np.uint8)
     if t == F16:
@@ -533,14 +576,14 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     """The whole synthetic GGUF file as one uint8 array (header_only: just the
     metadata + tensor table, enough for a vocab-only or no_upload replica load).
     vocab: a byte-level BPE vocabulary from bpe_vocab() instead of the SPM one.
-    types_override (header_only): name -> ggml type written in place of tensor_types' (files a
-    loader must refuse)."""
+    types_override: name -> ggml type written in place of tensor_types' (header_only: files a
+    loader must refuse; a full image: a file with a tensor of another served type)."""
     w = gguf.GGUFWriter()
     arch = cfg.arch
     w.add_str("general.architecture", arch)
     w.add_str("general.name", f"synthetic {cfg.name} {cfg.ftype}")
     w.add_u32("general.file_type", {"Q8_0": 7, "Q4_K_M": 15, "Q5_K_M": 17, "Q6_K": 18,
-                                    "Q4_K": 15, "Q5_K": 17, "F16": 1}[cfg.ftype])
+                                    "Q4_K": 15, "Q5_K": 17, "F16": 1, "Q4_0": 2, "Q5_0": 8}[cfg.ftype])
     w.add_u32(f"{arch}.context_length", cfg.n_ctx_train)
     w.add_u32(f"{arch}.embedding_length", cfg.n_embd)
     w.add_u32(f"{arch}.block_count", cfg.n_layer)
@@ -588,7 +631,6 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     types = tensor_types(cfg)
     shapes = tensor_shapes(cfg)
     if types_override:
-        assert header_only
         types.update(types_override)
     for name in types:
         w.add_tensor(name, types[name], shapes[name])

@@ -39,7 +39,12 @@ const char* mi_last_error(void);
 
 /* ---- model: replaces llama_model_load_from_file / llama_model_free
  *      (Model.cpp:52, Model.hpp:55) ---- */
-/* Weight types served: quantised models (layer matrices and output head Q4_K / Q5_K / Q6_K / Q8_0),
+/* Weight types served: quantised models (layer matrices, output head and token_embd each one of
+ * Q4_K / Q5_K / Q6_K / Q8_0 and, in a dense LLaMA-graph model, Q4_0 / Q5_0: llama-quantize's Q4_0 and
+ * Q5_0 files -- head Q6_K -- and the tensors it stores as Q4_0 / Q5_0 inside a k-quant file; Q4_0 and
+ * Q5_0 matrices take Q8_0 activations as Q8_0 ones do.  Refused with the tensor and the type by name,
+ * vocab_only included: Q4_1, Q5_1 (Q8_1 activations), Q2_K, Q3_K, the IQ and TQ types, and a Q4_0 /
+ * Q5_0 matrix in a MoE, GPT-2 or BERT model),
  * BERT encoders (F16), and unquantised dense LLaMA-graph models (general.architecture "llama",
  * no experts) whose matrices -- token_embd, output and the seven per layer -- are all F16 with F32
  * norm weights and rope_freqs; without output.weight the head is token_embd (tied models such as
