@@ -96,6 +96,7 @@ GemmParams Ctx::bwo_params(int l, int nt, bool vdot4, const float* pre) const {
     p.out = xb;
     p.resid = xb;
     p.out_stride = m->hp.n_embd;
+    p.bias = m->layers[l].bo;   // GPT-2 (mmq32): (y + b) + x
     set_pre(p, pre, l, 1, 0);   // before the residual add
     return p;
 }
@@ -125,7 +126,36 @@ GemmParams Ctx::bdown_params(int l, int nt, bool vdot4, const float* pre) const 
     p.resid = xb;
     p.addend = cvec_for(l);
     p.out_stride = m->hp.n_embd;
+    p.bias = m->layers[l].bdown;   // GPT-2 (mmq32): ((y + b) + x), then the control vector's row
     set_pre(p, pre, l, 3, 0);
+    return p;
+}
+
+// GPT-2: the fused attn_qkv (+ bias, KV append; no rotation) into qb and the caches -- the launch
+// takes it as three row segments (launch_mmq32_rows)
+GemmParams Ctx::bqkv_gpt2_params(int l, int nt) const {
+    GemmParams p = gemm_base(l, nt, false);   // (n_rot 0)
+    p.A = m->layers[l].qkv[0];
+    p.pair = PAIR_ADJ;
+    p.epi = EPI_STORE;
+    p.K = m->hp.n_embd;
+    p.out = qb;
+    p.out_stride = m->hp.n_embd;
+    p.bias = m->layers[l].bqkv;
+    return p;
+}
+
+// GPT-2: FFN up + bias + GELU into hb (LLM_FFN_GELU, LLM_FFN_SEQ)
+GemmParams Ctx::bup_gelu_params(int l, int nt) const {
+    GemmParams p = gemm_base(l, nt, false);
+    p.A = m->layers[l].up;
+    p.pair = PAIR_ADJ;
+    p.epi = EPI_GELU;
+    p.K = m->hp.n_embd;
+    p.out = hb;
+    p.out_stride = m->hp.n_ff;
+    p.bias = m->layers[l].bup;
+    p.gelu_tab = m->gelu_tab;
     return p;
 }
 
@@ -293,14 +323,21 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
     for (int c0 = 0; c0 < n; c0 += UB_MAX) {
         const int nt = std::min(UB_MAX, n - c0);
         upload_batch(tokens + c0, nt);
+        if (hp.arch == ARCH_GPT2) {   // llm_build_gpt2: every batch on the tiled form
+            if (c0 == 0) batch_path = 2;
+            enqueue_ubatch_gpt2(nt, all, c0, c0 + nt == n);
+            continue;
+        }
         // (a context with a LoRA adapter runs its short batches on the tiled form below, whose
         // epilogues take the adapter's terms; split-K is off for the W_o / down launches an adapter
         // targets, and pending parts are added by the quant_act that precedes every shrink)
         if (mmqs_max > 0 && nt <= mmqs_max && short_ok() && !lora_on()) {   // a short batch (its launches captured as a
             // hipGraph measured no faster: the GPU, not the enqueue, sets the pace)
+            if (c0 == 0) batch_path = 3;
             enqueue_ubatch_short(nt, all, c0, c0 + nt == n);
             continue;
         }
+        if (c0 == 0) batch_path = 2;
         EmbedParams ep{m->tok_embd, tokpos_b, xb, hp.n_embd};
         launch_embed_multi(ep, nt, stream);
         launch_rope_table(tokpos_b, nt, hp.n_rot, theta_scale(), hp.freq_scale, m->rope_freqs, ub_rope, stream);
@@ -394,6 +431,60 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
         }
     }
     logits_valid = !embeddings;
+}
+
+// One physical batch of a GPT-2 model (tokens uploaded to tokpos_b) on the tiled int8-MFMA GEMM:
+// llm_build_gpt2 (b5187) with every matrix streamed once per batch and the arithmetic per token row
+// of the decode step.  The rows are token row + position_embd row of the token's position.  Per
+// layer, 8 launches:
+//   quant_act  layer_norm(x) * attn_norm + attn_norm_b, quantised once
+//   mmq2       attn_qkv as three row segments: (y + b) -> Q rows f32 in qb, K and V rows rounded to
+//              f16 into the caches (no rotation), cell_pos written
+//   attention  attn_mfma (any number of cells), else the fused form within ATTN_SHORT cells
+//   quant_act  the attention rows
+//   mmq2       attn_output: (y + b) + x, in place
+//   quant_act  layer_norm(x) * ffn_norm + ffn_norm_b
+//   mmq2       ffn_up: gelu(y + b) through ggml's f16 table into hb
+//   quant_act  hb
+//   mmq2       ffn_down: ((y + b) + x), then the control vector's row, in place
+// No split-K: every residual GEMM writes xb itself.  The output as decode_ubatch's: every row's
+// logits through the final LayerNorm and the tied head (`all`), the last row's through the decode
+// head, or the embedding tail.
+void Ctx::enqueue_ubatch_gpt2(int nt, bool all, int c0, bool last) {
+    const HParams& hp = m->hp;
+    const int ne = hp.n_embd;
+    EmbedParams ep{m->tok_embd, tokpos_b, xb, ne, m->pos_embd, 1, nullptr};
+    launch_embed_multi(ep, nt, stream);
+    // a LayerNorm'd (norm_w, norm_b set) or plain row set quantised for the matrix `type` reads
+    auto quant = [&](const float* rows, int K, const float* norm_w, const float* norm_b, int type) {
+        const ActQ8 act = ub_act(K, nt, type);
+        launch_quant_act(rows, K, norm_w, hp.eps, act, stream, nullptr, nullptr, 2, 0, nullptr, norm_b);
+        return act;
+    };
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const Layer& L = m->layers[l];
+        {
+            const ActQ8 act = quant(xb, ne, L.attn_norm, L.attn_norm_b, L.qkv[0].type);
+            const int row0[3] = {0, ne, 2 * ne}, nrows[3] = {ne, ne, ne};
+            const int epi[3] = {EPI_STORE, EPI_ROPE_K, EPI_V};   // (n_rot 0: K rows unrotated)
+            launch_mmq32_rows(bqkv_gpt2_params(l, nt), row0, nrows, epi, 3, act, ub_rope, stream);
+        }
+        if (attn_mfma) launch_attn_mfma(battn_params(l), nt, attnb, stream);
+        else launch_attn_multi(battn_params(l), nt, attnb, stream);
+        launch_mmq32(bwo_params(l, nt, false, nullptr), quant(attnb, ne, nullptr, nullptr, L.wo.type), ub_rope, stream);
+        launch_mmq32(bup_gelu_params(l, nt), quant(xb, ne, L.ffn_norm, L.ffn_norm_b, L.up.type), ub_rope, stream);
+        launch_mmq32(bdown_params(l, nt, false, nullptr), quant(hb, hp.n_ff, nullptr, nullptr, L.down.type), ub_rope, stream);
+    }
+    if (embeddings) {
+        embd_tail(xb, nt, c0);
+    } else if (all) {   // final LayerNorm + the tied head over every token of the batch
+        const ActQ8 a_out = quant(xb, ne, m->output_norm, m->output_norm_b, m->output.type);
+        launch_mmq32(mmq32_params(m->output, nullptr, nt, tokpos_b, logits_all + (size_t)c0 * hp.n_vocab, hp.n_vocab), a_out,
+                     ub_rope, stream);
+        finish_logits_all(c0, nt, last);
+    } else if (last) {
+        enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * ne, nullptr);
+    }
 }
 
 // ================================================== unquantised F16 models ===

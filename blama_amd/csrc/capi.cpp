@@ -663,6 +663,7 @@ int32_t mi_decode_path(const mi_ctx* c) {
     if (c->impl->m->f16) return 3;
     return c->impl->sp_ok ? 1 : 0;
 }
+int32_t mi_batch_path(const mi_ctx* c) { return c ? c->impl->batch_path : -1; }
 int32_t mi_debug_stamps(mi_ctx* c, uint64_t* out, int32_t n_launch) {
     try {
         if (!c || !out) throw Error("null argument");

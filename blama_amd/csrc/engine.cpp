@@ -185,9 +185,17 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
 #ifdef MI_STAMPS
     stamps = mem.dev<unsigned long long>((size_t)kStampLaunches * kStampWgs * 8, true);
 #endif
-    // GPT-2 prompts run token by token (one decode graph each): its batch kernels (LayerNorm,
-    // biases, GELU) are not built
-    batch_ok = hp.arch == ARCH_LLAMA && getenv("MI_NO_BATCH") == nullptr;
+    const bool gpt2 = hp.arch == ARCH_GPT2;
+    batch_ok = getenv("MI_NO_BATCH") == nullptr;
+    // GPT-2: physical batches on the tiled int8-MFMA GEMM only (ubatch_gpt2), for a model whose four
+    // matrices per layer are mmq32-capable and whose fused attn_qkv splits into whole row tiles;
+    // any other GPT-2 model keeps one decode step per token
+    if (gpt2) {
+        batch_ok = batch_ok && getenv("MI_NO_MMQ") == nullptr && hp.n_embd % 32 == 0 && hp.n_ff % 32 == 0 &&
+                   kv_dim == hp.n_embd;
+        for (const Layer& L : m->layers)
+            for (const QMat* q : {&L.qkv[0], &L.wo, &L.up, &L.down}) batch_ok = batch_ok && mmq32_supported(q->type);
+    }
     if (batch_ok) {
         // MFMA batch path (decode_ubatch / mmq32) when every layer matrix is mmq32-capable (each
         // matrix reads the activation format of its type: Q8_0 activations for Q8_0 weights, Q8_K
@@ -245,8 +253,9 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
             }
             ub_rope = mem.dev<float2>((size_t)UB_MAX * std::max(1, hp.n_rot / 2));
             // split-K partials of the residual GEMMs (WO, FFN down) of dense models
-            if (mmq2_active()) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
-            mmqs_max = mmqs_token_limit();
+            // (GPT-2: no split-K, no short-batch form -- every batch on the tiled GEMM)
+            if (mmq2_active() && !gpt2) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
+            mmqs_max = gpt2 ? 0 : mmqs_token_limit();
             // MoE: short batches when every expert matrix has the grouped form (k-quants)
             moe_short = hp.n_expert > 0;
             for (const Layer& L : m->layers)
@@ -268,7 +277,8 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
             }
         }
         // MoE prompts need the MFMA path (the v_dot4 GEMM has no routed-expert form)
-        if (hp.n_expert > 0 && !mmq_ok) batch_ok = false;
+        // (and so do GPT-2 prompts: no copy, no batch -- the per-token loop)
+        if ((hp.n_expert > 0 || gpt2) && !mmq_ok) batch_ok = false;
     }
     if (m->f16) f16_init();
     attn_smax = mem.dev<float>((size_t)ATTN_SMAX * hp.n_head);
@@ -898,7 +908,10 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     unsynced = true;
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 0 || tokens[i] >= m->hp.n_vocab) throw Error("decode: token id out of range");
-    if (enc) return decode_enc(tokens, n, all);
+    if (enc) {
+        batch_path = 5;
+        return decode_enc(tokens, n, all);
+    }
     if (n_cells + n > (int)n_ctx) return 1;   // no KV slot (llama_decode returns 1)
     if (m->hp.arch == ARCH_GPT2 && pos_max + n >= m->hp.n_ctx_train)
         throw Error("decode: gpt2 position past the learned position embeddings (n_ctx_train)");
@@ -926,13 +939,15 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
     // an F16 model: any call of two tokens or more on the F16 MFMA GEMM (the MFMA attention over any
     // number of cells; head sizes it does not serve: the fused form within ATTN_SHORT cells)
     if (m->f16 && n >= 2 && batch_ok && prof_layer < 0 && (attn_mfma || n_cells + n <= ATTN_SHORT)) {
+        batch_path = 4;
         decode_f16_batch(tokens, n, all);
         if (all && !embeddings) out_rows = n;
         return 0;
     }
     // prompt ingestion through the batched GEMM when the context stays within the fused
     // attention's reach (dense models; MI_NO_BATCH=1 forces token-by-token decode)
-    const bool fits = n >= 2 && batch_ok && !m->f16 && hp_dense() && n_cells + n <= ATTN_SHORT && prof_layer < 0;
+    const bool fits = n >= 2 && batch_ok && !m->f16 && hp_dense() && m->hp.arch == ARCH_LLAMA && n_cells + n <= ATTN_SHORT &&
+                      prof_layer < 0;
     // the MFMA batch path attends over any number of cells with the MFMA attention kernel
     const bool ub = n >= 2 && batch_ok && mmq_ok && prof_layer < 0 && (attn_mfma || n_cells + n <= ATTN_SHORT);
     if (ub && (!all || out_mmq || embeddings)) {
@@ -941,9 +956,11 @@ int Ctx::decode(const int32_t* tokens, int n, bool all) {
         return 0;
     }
     if (fits && (!all || embeddings)) {
+        batch_path = 1;
         decode_batch(tokens, n);
         return 0;
     }
+    batch_path = 0;   // one decode step per token
     for (int i = 0; i < n; ++i) {
         // embeddings mode: the steps whose row the call's result needs end in the embedding row
         const bool last = i == n - 1 || (all && !pooled) || (pooled && (pooling == MI_POOLING_MEAN || (pooling == MI_POOLING_CLS && i == 0)));

@@ -271,7 +271,7 @@ struct Ctx {
     unsigned* step_ctr = nullptr;       // decode steps so far (incremented by the embedding launch)
     unsigned* h_attn_xerr = nullptr;    // host-mapped: an exchange timed out
     unsigned* d_attn_xerr = nullptr;
-    // batched prompt ingestion (dense models): GEMM_NT rows of residual / q / attention / FFN
+    // batched prompt ingestion (LLaMA, GPT-2): kBatchRows rows of residual / q / attention / FFN
     bool batch_ok = false;
     float *xb = nullptr, *qb = nullptr, *attnb = nullptr, *hb = nullptr;
     int* tokpos_b = nullptr;            // [GEMM_NT][4]
@@ -520,6 +520,8 @@ struct Ctx {
     GemmParams bgate_up_params(int l, int nt, bool vdot4, const float* pre) const;
     GemmParams bdown_params(int l, int nt, bool vdot4, const float* pre) const;   // addend: the control vector's row
     AttnParams battn_params(int l) const;
+    GemmParams bqkv_gpt2_params(int l, int nt) const;   // GPT-2: the fused attn_qkv + bias
+    GemmParams bup_gelu_params(int l, int nt) const;    // GPT-2: ffn_up + bias + GELU
     // Q / K / V by type: the activation formats they read (bit 0 Q8_K, bit 1 Q8_0) and the launches,
     // each the matrices of one type (idx: 0 Q, 1 K, 2 V, ascending; launches ordered by their first)
     struct QkvGroups {
@@ -554,6 +556,10 @@ struct Ctx {
     // into xb (pend_k parts of ub_spart)
     int ubatch_layers_short(int nt);
     void enqueue_ubatch_short(int nt, bool all, int c0, bool last);
+    // one physical batch of a GPT-2 model on the tiled GEMM (batch.cpp)
+    void enqueue_ubatch_gpt2(int nt, bool all, int c0, bool last);
+    // mi_batch_path: the form the most recent decode call took (its first physical batch's; -1: no call yet)
+    int batch_path = -1;
     ActQ8 ub_act(int K, int ntok, int type) const;   // the activation format `type`'s matrices read
     bool hp_dense() const { return m->hp.n_expert == 0; }
     // a second activation set (Q8_0) for a model mixing Q8_0 and k-quant matrices

@@ -248,6 +248,12 @@ struct GemmParams {
     // quantises it
     int ksplit;
     float* part;
+    // mmq32, GPT-2 prompt batches (llm_build_gpt2), optional: y += bias[row] BEFORE everything else
+    // (the ggml_add of a projection bias: ahead of the KV append, the residual add or GELU), like
+    // GemvSeg::bias; with launch_mmq32_rows, a segment's rows read bias from its first row on.
+    // EPI_GELU reads gelu_tab (ggml_table_gelu_f16).  Not with pre, a pair or split-K.
+    const float* bias;
+    const unsigned short* gelu_tab;
 };
 void launch_gemm(const GemmParams& p, hipStream_t s);
 
@@ -432,9 +438,11 @@ constexpr int UB_MAX = 512;    // n_ubatch (reference Instance.hpp:24)
 // row after that, x = (((p0 + p1) + ...) + x) + addend
 // swiglu: part holds the gate/up parts of a pair launch ([nks][ntok][2 K]: gate rows, then up
 // rows); the row quantised is silu(sum gate) * (sum up) (x unused)
+// norm_b (with norm_w; GPT-2): the row quantised is layer_norm(x) * norm_w + norm_b -- ggml_norm as
+// gemv.hip's PRO_LAYERNORM prologue computes it -- instead of rms_norm(x) * norm_w
 void launch_quant_act(const float* x, int x_stride, const float* norm_w, float eps, const ActQ8& a, hipStream_t s,
                       const int* rows = nullptr, const float* part = nullptr, int nks = 2, int swiglu = 0,
-                      const float* addend = nullptr);
+                      const float* addend = nullptr, const float* norm_b = nullptr);
 // whether prompt-batch GEMMs take the mmq2 path (the only one with ksplit)
 bool mmq2_active();
 // ggml_rope_cache_init per token of the batch: out [ntok][n_rot/2] (cos, sin)
@@ -453,6 +461,12 @@ void launch_mmq32(const GemmParams& p, const ActQ8& act, const float2* rope, hip
 // several matrices of one type over the same activation (Q / K / V) as ONE mmq2 launch when they
 // qualify (no pairs, no grouping, a shared output buffer), else one launch each
 void launch_mmq32_multi(const GemmParams* ps, int n, const ActQ8& act, const float2* rope, hipStream_t s);
+// ONE matrix as n (<= 3) row segments of its single MFMA-order copy, each with its own epilogue
+// (GPT-2's fused attn_qkv: Q rows stored, K and V rows to the caches): segment i is rows
+// [row0[i], row0[i] + nrows[i]) of p.A, row0[i] a multiple of 32 (whole row tiles of the copy);
+// p.bias (optional) is the matrix's, indexed by the matrix row.  The other fields as launch_mmq32's.
+void launch_mmq32_rows(const GemmParams& p, const int* row0, const int* nrows, const int* epi, int n, const ActQ8& act,
+                       const float2* rope, hipStream_t s);
 
 // ---- short batches (<= MMQS_MAX tokens, mmq.hip mmqs): a split-K streaming int8-MFMA GEMM ----
 // The matrices (one type; a gate/up pair: one QMat, its pair copy) over act (npad 32 or 64) write

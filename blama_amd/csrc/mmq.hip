@@ -105,17 +105,21 @@ __device__ __forceinline__ V sum_parts(const V* p, long long stride, int n) {
 // ---------------------------------------------------------------------------
 // QA_W waves per token row (16: one 256-element block each at K = 4096); XR blocks per wave at
 // most (the host picks the smallest that covers K: fewer predicated copies, fewer registers)
-template <int QA_W, int XR>
+// LN: the LayerNorm instantiation (GPT-2; norm_w and norm_b set): layer_norm(x) * norm_w + norm_b as
+// gemv.hip's PRO_LAYERNORM prologue forms it (ggml_compute_forward_norm_f32: the sum and the sum of
+// the f32 squares of (x - mean) in double, mean and variance in float), so a row's quantised
+// activation is the decode step's.  The RMSNorm instantiations carry no trace of it.
+template <int QA_W, int XR, bool LN>
 __global__ __launch_bounds__(64 * QA_W) void quant_act_kernel(const float* x, int x_stride, const float* norm_w,
                                                         float eps, ActQ8 a, const int* rows, const float* part, int nks,
-                                                        int swiglu, const float* addend) {
+                                                        int swiglu, const float* addend, const float* norm_b) {
     const int t = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nb = a.K >> 8;
     // this wave's blocks: w0, w0 + bst, ... (gridDim.y > 1, rows without a norm: the row's blocks
     // spread over gridDim.y workgroups)
     const int w0 = (int)blockIdx.y * QA_W + wave, bst = QA_W * (int)gridDim.y;
-    __shared__ double red[QA_W];
+    __shared__ double red[LN ? 2 * QA_W : QA_W];
     // MFMA-fragment order (one wave load = 1 KiB contiguous): q [tile][sb][j][h*32 + t%32][16 B],
     // element 32j + 16h + e of superblock sb of token t at byte e; bsb [tile][sb][t%32][16 B]
     const int tile = t >> 5, tr = t & 31;
@@ -170,8 +174,46 @@ __global__ __launch_bounds__(64 * QA_W) void quant_act_kernel(const float* x, in
             asm volatile("" ::: "memory");   // one block's part loads in flight at a time (registers)
         }
     }
-    float scale = 1.0f;
-    if (norm_w) {   // ggml_compute_forward_rms_norm_f32: sum of squares in double
+    float scale = 1.0f, mean = 0.0f;
+    if constexpr (LN) {
+        double sacc = 0.0;
+#pragma unroll
+        for (int i = 0; i < XR; ++i) {
+            if (w0 + bst * i < nb) {
+                const f32x4 v = xr[i];
+                sacc += (double)v.x;
+                sacc += (double)v.y;
+                sacc += (double)v.z;
+                sacc += (double)v.w;
+            }
+        }
+        sacc = wave_sum63_d(sacc);
+        if (lane == 63) red[wave] = sacc;
+        __syncthreads();
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < QA_W; ++k) tot += red[k];
+        mean = (float)(tot / (double)a.K);
+        double s2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < XR; ++i) {
+            if (w0 + bst * i < nb) {
+                const f32x4 v = xr[i];
+                const float v0 = v.x - mean, v1 = v.y - mean, v2 = v.z - mean, v3 = v.w - mean;
+                s2 += (double)(v0 * v0);
+                s2 += (double)(v1 * v1);
+                s2 += (double)(v2 * v2);
+                s2 += (double)(v3 * v3);
+            }
+        }
+        s2 = wave_sum63_d(s2);
+        if (lane == 63) red[QA_W + wave] = s2;
+        __syncthreads();
+        double tot2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < QA_W; ++k) tot2 += red[QA_W + k];
+        scale = 1.0f / sqrtf((float)(tot2 / (double)a.K) + eps);
+    } else if (norm_w) {   // ggml_compute_forward_rms_norm_f32: sum of squares in double
         double sacc = 0.0;
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
@@ -198,7 +240,14 @@ __global__ __launch_bounds__(64 * QA_W) void quant_act_kernel(const float* x, in
         if (blk >= nb) break;
         const f32x4 xv = xr[i];
         float v[4] = {xv.x, xv.y, xv.z, xv.w};
-        if (norm_w) {
+        if constexpr (LN) {   // (x - mean) * scale, then ggml_mul, ggml_add
+            const f32x4 w = w4[blk * 64 + lane];
+            const f32x4 b = reinterpret_cast<const f32x4*>(norm_b)[blk * 64 + lane];
+            v[0] = ((v[0] - mean) * scale) * w.x + b.x;
+            v[1] = ((v[1] - mean) * scale) * w.y + b.y;
+            v[2] = ((v[2] - mean) * scale) * w.z + b.z;
+            v[3] = ((v[3] - mean) * scale) * w.w + b.w;
+        } else if (norm_w) {
             const f32x4 w = w4[blk * 64 + lane];
             v[0] = (v[0] * scale) * w.x;   // ggml_vec_scale_f32, then ggml_mul
             v[1] = (v[1] * scale) * w.y;
@@ -392,22 +441,27 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
     }
 }
 
-template <bool AB>
-__device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, const float2* rope, int ttok0,
-                                             int lane, int row, const float v[16], int epi, int nrows,
-                                             float* out, const float* pre);
-
 // The epilogue of one 32-token x 32-row D tile (v: this lane's 16 results).
-template <bool AB>
+// GX: the GPT-2 instantiations (llm_build_gpt2): bias (the segment's rows; null: none) is added to
+// y before everything else, and EPI_GELU is compiled in -- ggml_vec_gelu_f32 through the f16 table,
+// gemv.hip's EPI_GELU expression.  The other instantiations carry no trace of either.
+template <bool AB, bool GX>
 __device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, const float2* rope, int ttok0,
                                              int lane, int row, const float v[16], int epi, int nrows,
-                                             float* out, const float* pre) {
+                                             float* out, const float* pre, const float* bias) {
     const int col = lane & 31, h = lane >> 5;
     const bool roped = epi == EPI_ROPE_Q || epi == EPI_ROPE_K;
+    float bv = 0.0f;
+    if constexpr (GX) {
+        if (bias && row < nrows) bv = bias[row];   // this lane's weight row
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int tok = ttok0 + (r & 3) + 8 * (r >> 2) + 4 * h;
         float vr = v[r];
+        if constexpr (GX) {
+            if (bias) vr += bv;   // ggml_add of the projection bias
+        }
         if (pre && tok < tend && row < nrows)   // a LoRA adapter's term, before the epilogue
             vr += pre[(long long)tok * P.pre_stride + row];
         const float pv = __shfl_xor(vr, AB ? 16 : 1, 64);   // SwiGLU partner / RoPE partner
@@ -444,7 +498,15 @@ __device__ __forceinline__ void mmq_epilogue(const GemmParams& P, int tend, cons
             break;
         }
         case EPI_V: P.vcache[(long long)tp[2] * P.kv_dim + row] = __float2half_rn(o); break;
-        default: break;
+        default:
+            if constexpr (GX) {
+                if (epi == EPI_GELU) {
+                    const unsigned short hb = __half_as_ushort(__float2half_rn(o));
+                    const float t = __half2float(__ushort_as_half(P.gelu_tab[hb]));
+                    out[(long long)tok * P.out_stride + row] = o <= -10.0f ? 0.0f : (o >= 10.0f ? o : t);
+                }
+            }
+            break;
         }
     }
 }
@@ -476,6 +538,7 @@ struct MmqSegs {
     int epi[MMQ_SEGS];
     int n;
     int pre_off[MMQ_SEGS];    // GemmParams::pre_off of each segment
+    int bias_off[MMQ_SEGS];   // the segment's first row in GemmParams::bias (launch_mmq32_rows)
 };
 
 template <int T> struct M2 {
@@ -579,8 +642,8 @@ __device__ __forceinline__ void q45_planes(const u32x4 hd, const u32x4 wq, const
 // NST 2: two stages (copy of sb + 1 during sb), one workgroup per CU.  NST 1: one stage, copy and
 // compute in turn, sized (LDS, <= 128 VGPRs) for two workgroups per CU that overlap each other.
 // PRE: the instantiation that adds GemmParams::pre (launched only when it is set: the other kernels
-// carry no trace of it).
-template <int T, bool AB, int NST, bool PRE>
+// carry no trace of it).  GX: the GPT-2 instantiation (GemmParams::bias, EPI_GELU), likewise its own.
+template <int T, bool AB, int NST, bool PRE, bool GX>
 __global__ __launch_bounds__(64 * M2<T>::NW) __attribute__((amdgpu_waves_per_eu(NST == 1 ? 4 : 2)))
 void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSegs S) {
     using C = M2<T>;
@@ -884,8 +947,8 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
         const int row = AB ? rt * 16 + (col & 15) : rt * 32 + col;
         // split-K: this part's partial sums, stored plainly; else the segment's epilogue
         if (P.ksplit > 1)
-            mmq_epilogue<AB>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], EPI_STORE, rows_s,
-                             P.part + (long long)kh * P.ntok * P.out_stride, nullptr);
+            mmq_epilogue<AB, false>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], EPI_STORE, rows_s,
+                                    P.part + (long long)kh * P.ntok * P.out_stride, nullptr, nullptr);
         else {
             // (GemmParams::pre: this segment's rows; a pair's up lanes read the up rows' terms)
             const float* pre = nullptr;
@@ -893,7 +956,12 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
                 const int po = seg == 0 ? S.pre_off[0] : seg == 1 ? S.pre_off[1] : S.pre_off[2];
                 pre = P.pre + po + (AB && col >= 16 ? P.pre_up : 0);
             }
-            mmq_epilogue<AB>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], epi_s, rows_s, P.out, pre);
+            const float* bias = nullptr;
+            if constexpr (GX) {
+                const int bo = seg == 0 ? S.bias_off[0] : seg == 1 ? S.bias_off[1] : S.bias_off[2];
+                if (P.bias) bias = P.bias + bo;
+            }
+            mmq_epilogue<AB, GX>(P, tend, rope, tok0 + 32 * w, lane, row, y[0], epi_s, rows_s, P.out, pre, bias);
         }
     }
   }
@@ -1442,8 +1510,9 @@ template <int T, int NST> constexpr int m2_lds() { return M2<T>::lds(NST); }
 }  // namespace mmq
 
 void launch_quant_act(const float* x, int x_stride, const float* norm_w, float eps, const ActQ8& a, hipStream_t s,
-                      const int* rows, const float* part, int nks, int swiglu, const float* addend) {
+                      const int* rows, const float* part, int nks, int swiglu, const float* addend, const float* norm_b) {
     if (addend && (!part || swiglu)) throw Error("quant_act: an addend goes with the residual's split-K partials");
+    if (norm_b && !norm_w) throw Error("quant_act: a LayerNorm bias goes with the norm weight");
     if (part && (nks < 1 || nks > 64)) throw Error("quant_act: 1..64 split-K partials");
     // (swiglu with rows: the MoE rows of a grouped pair launch, rows[t] < 0 marking padding rows)
     if (swiglu && (!part || norm_w)) throw Error("quant_act: swiglu takes a pair launch's parts, no norm");
@@ -1458,9 +1527,13 @@ void launch_quant_act(const float* x, int x_stride, const float* norm_w, float e
     const int nb = a.K / 256;
     const int ny = norm_w ? 1 : (nb + 15) / 16;
     const int xr = (nb + 16 * ny - 1) / (16 * ny);
-    auto f = xr <= 1 ? mmq::quant_act_kernel<16, 1> : xr <= 2 ? mmq::quant_act_kernel<16, 2>
-           : xr <= 4 ? mmq::quant_act_kernel<16, 4> : mmq::quant_act_kernel<16, 16>;
-    hipLaunchKernelGGL(f, dim3(a.npad, ny), dim3(1024), 0, s, x, x_stride, norm_w, eps, a, rows, part, nks, swiglu, addend);
+    auto f = xr <= 1 ? mmq::quant_act_kernel<16, 1, false> : xr <= 2 ? mmq::quant_act_kernel<16, 2, false>
+           : xr <= 4 ? mmq::quant_act_kernel<16, 4, false> : mmq::quant_act_kernel<16, 16, false>;
+    if (norm_b)   // LayerNorm (ny == 1: the row's blocks in one workgroup)
+        f = xr <= 1 ? mmq::quant_act_kernel<16, 1, true> : xr <= 2 ? mmq::quant_act_kernel<16, 2, true>
+          : xr <= 4 ? mmq::quant_act_kernel<16, 4, true> : mmq::quant_act_kernel<16, 16, true>;
+    hipLaunchKernelGGL(f, dim3(a.npad, ny), dim3(1024), 0, s, x, x_stride, norm_w, eps, a, rows, part, nks, swiglu, addend,
+                       norm_b);
     MI_HIP(hipGetLastError());
 }
 
@@ -1518,28 +1591,38 @@ void launch_mmq2(const GemmParams& p, const mmq::MmqSegs& S, const ActQ8& act, c
         MI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
     const int nst = g2 >= 2 * n_cu ? 1 : 2;
-    decltype(&mmq::mmq2_t<T_Q4_K, false, 2, false>) f2;
+    decltype(&mmq::mmq2_t<T_Q4_K, false, 2, false, false>) f2;
     const bool pre = p.pre != nullptr && p.ksplit <= 1;
+    // the GPT-2 instantiations: a projection bias and / or GELU (single matrices; no pre, no split-K)
+    bool gx = p.bias != nullptr;
+    for (int i = 0; i < S.n; ++i) gx = gx || S.epi[i] == EPI_GELU;
+    if (gx && (ab || pre || p.ksplit > 1 || p.grp)) throw Error("mmq2: bias / GELU launches take one plain matrix, no pre, no split-K");
+    if (gx)
+        for (int i = 0; i < S.n; ++i)
+            if (S.epi[i] == EPI_GELU && !p.gelu_tab) throw Error("mmq2: the GELU epilogue needs the table");
     int lds;
-#define M2_PICK(NST_)                                                                                           \
-    switch (T) {                                                                                                \
-    case T_Q4_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q4_K, true, NST_, true> : mmq::mmq2_t<T_Q4_K, false, NST_, true>) \
-                           : (ab ? mmq::mmq2_t<T_Q4_K, true, NST_, false> : mmq::mmq2_t<T_Q4_K, false, NST_, false>); lds = mmq::m2_lds<T_Q4_K, NST_>(); break; \
-    case T_Q5_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q5_K, true, NST_, true> : mmq::mmq2_t<T_Q5_K, false, NST_, true>) \
-                           : (ab ? mmq::mmq2_t<T_Q5_K, true, NST_, false> : mmq::mmq2_t<T_Q5_K, false, NST_, false>); lds = mmq::m2_lds<T_Q5_K, NST_>(); break; \
-    case T_Q6_K: f2 = pre ? (ab ? mmq::mmq2_t<T_Q6_K, true, NST_, true> : mmq::mmq2_t<T_Q6_K, false, NST_, true>) \
-                           : (ab ? mmq::mmq2_t<T_Q6_K, true, NST_, false> : mmq::mmq2_t<T_Q6_K, false, NST_, false>); lds = mmq::m2_lds<T_Q6_K, NST_>(); break; \
-    default: f2 = pre ? (ab ? mmq::mmq2_t<T_Q8_0, true, NST_, true> : mmq::mmq2_t<T_Q8_0, false, NST_, true>) \
-                           : (ab ? mmq::mmq2_t<T_Q8_0, true, NST_, false> : mmq::mmq2_t<T_Q8_0, false, NST_, false>); lds = mmq::m2_lds<T_Q8_0, NST_>(); break; \
+#define M2_ONE(TT, NST_)                                                                                        \
+    f2 = gx ? mmq::mmq2_t<TT, false, NST_, false, true>                                                          \
+            : pre ? (ab ? mmq::mmq2_t<TT, true, NST_, true, false> : mmq::mmq2_t<TT, false, NST_, true, false>) \
+                  : (ab ? mmq::mmq2_t<TT, true, NST_, false, false> : mmq::mmq2_t<TT, false, NST_, false, false>); \
+    lds = mmq::m2_lds<TT, NST_>();
+#define M2_PICK(NST_)                    \
+    switch (T) {                         \
+    case T_Q4_K: M2_ONE(T_Q4_K, NST_) break; \
+    case T_Q5_K: M2_ONE(T_Q5_K, NST_) break; \
+    case T_Q6_K: M2_ONE(T_Q6_K, NST_) break; \
+    default: M2_ONE(T_Q8_0, NST_) break;     \
     }
     if (nst == 1) { M2_PICK(1) } else { M2_PICK(2) }
 #undef M2_PICK
-    static bool attr_done[2][4][2][2] = {};
+#undef M2_ONE
+    static bool attr_done[2][4][2][3] = {};
     const int ti = T == T_Q4_K ? 0 : T == T_Q5_K ? 1 : T == T_Q6_K ? 2 : 3;
     const int ni = nst == 1 ? 0 : 1;
-    if (!attr_done[ni][ti][ab][pre]) {
+    const int vi = gx ? 2 : pre ? 1 : 0;
+    if (!attr_done[ni][ti][ab][vi]) {
         MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f2), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_done[ni][ti][ab][pre] = true;
+        attr_done[ni][ti][ab][vi] = true;
     }
     hipLaunchKernelGGL(f2, dim3(g2), dim3(64 * NWv), (size_t)lds, s, p, act, rope, S);
     MI_HIP(hipGetLastError());
@@ -1599,6 +1682,33 @@ void launch_mmq32(const GemmParams& p, const ActQ8& act, const float2* rope, hip
     S.rows[0] = p.A.rows;
     S.epi[0] = p.epi;
     S.pre_off[0] = p.pre_off;
+    launch_mmq2(p, S, act, rope, s);
+}
+
+void launch_mmq32_rows(const GemmParams& p, const int* row0, const int* nrows, const int* epi, int n, const ActQ8& act,
+                       const float2* rope, hipStream_t s) {
+    if (!mmq32_supported(p.A.type)) throw Error("mmq32: Q4_K / Q5_K / Q6_K / Q8_0 only");
+    if (takes_q80(p.A.type) != (act.q80 != 0)) throw Error("mmq32: Q8_0 weights take Q8_0 activations, k-quants Q8_K");
+    if (act.K != p.K || p.A.K != p.K) throw Error("mmq32: activation length differs from K");
+    if (p.pair == PAIR_AB || p.grp || p.ksplit > 1 || p.pre) throw Error("mmq32 rows: one plain matrix");
+    if (act.ntok < 1 || act.npad % 32 || act.npad > UB_MAX) throw Error("mmq32: bad token count");
+    if (!p.A.sw) throw Error("mmq32: the matrix has no MFMA-order copy");
+    if (n < 1 || n > mmq::MMQ_SEGS) throw Error("mmq32 rows: 1..3 segments");
+    mmq::MmqSegs S{};
+    S.n = n;
+    const size_t tile_row = (size_t)p.A.nb * mmq32_tile_bytes(p.A.type);   // one 32-row tile of the copy
+    for (int i = 0; i < n; ++i) {
+        if (row0[i] < 0 || row0[i] % 32 || nrows[i] < 1 || row0[i] + nrows[i] > p.A.rows)
+            throw Error("mmq32 rows: a segment starts at a multiple of 32 rows, inside the matrix");
+        // (a segment that ends inside a row tile reads the next segment's rows of that tile and
+        // drops them: every tile of the copy is whole)
+        if ((epi[i] == EPI_ROPE_Q || epi[i] == EPI_ROPE_K) && (!rope || p.head_dim % 2 || p.n_rot > p.head_dim))
+            throw Error("mmq32: RoPE epilogue needs the rope table");
+        S.sw[i] = p.A.sw + (size_t)(row0[i] / 32) * tile_row;
+        S.rows[i] = nrows[i];
+        S.epi[i] = epi[i];
+        S.bias_off[i] = row0[i];
+    }
     launch_mmq2(p, S, act, rope, s);
 }
 

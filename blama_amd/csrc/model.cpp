@@ -302,6 +302,11 @@ bool Model::ensure_mmq_copies() {
     // expert e at sw + e * sw_expert_stride) and the output head
     std::vector<std::pair<QMat*, QMat*>> todo;
     for (Layer& L : layers) {
+        if (hp.arch == ARCH_GPT2) {   // the fused attn_qkv as one copy (its Q, K and V rows are row segments of it), ffn_up alone
+            for (QMat* q : {&L.qkv[0], &L.wo, &L.up, &L.down})
+                if (mmq32_supported(q->type)) todo.push_back({q, nullptr});
+            continue;
+        }
         for (QMat* q : {&L.wq, &L.wk, &L.wv, &L.wo, &L.down})
             if (mmq32_supported(q->type)) todo.push_back({q, nullptr});
         if (mmq32_supported(L.gate.type) && L.up.type == L.gate.type) todo.push_back({&L.gate, &L.up});

@@ -487,6 +487,64 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
     MI_TRY(-1)
 }
 
+int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t ntok,
+                        const float* x, const float* norm_w, const float* norm_b, float eps, const float* bias,
+                        const float* resid, int32_t epilogue, float* y, int8_t* q_out, float* d_out) {
+    try {
+        if (!mmq32_supported(type)) throw Error("op_gemm_bias: Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
+        if (ntok < 1 || ntok > UB_MAX) throw Error("op_gemm_bias: 1..512 token rows");
+        if (rows < 1 || K < 256 || K % 256) throw Error("op_gemm_bias: bad shape");
+        if (epilogue < 0 || epilogue > 2 || (epilogue == 1 && !resid)) throw Error("op_gemm_bias: epilogue 0 / 1 (with resid) / 2");
+        if ((norm_w == nullptr) != (norm_b == nullptr)) throw Error("op_gemm_bias: LayerNorm takes its weight and its bias");
+        if (!x || !y) throw Error("op_gemm_bias: null argument");
+        MI_HIP(hipSetDevice(device));
+        ensure_kernel_attributes(device);
+        Keep keep;
+        QMat A = upload_qmat(type, raw, rows, K, keep);
+        swizzle(A, nullptr, keep);
+        const bool q80 = takes_q80(type);
+        const size_t npad = (size_t)(ntok + 31) / 32 * 32;
+        const int nb = K / 256, nd = q80 ? K / 32 : nb;   // scales per row
+        Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows), ddT(npad * (K / 32));
+        Dev<float> dnw(K, norm_w), dnb(K, norm_b), dbias(rows, bias), dres((size_t)ntok * rows, epilogue == 1 ? resid : nullptr);
+        Dev<int8_t> dq(npad * K), dbs(npad * nb * 16);
+        Dev<int> dtp((size_t)ntok * 4);
+        dtp.fill(0);
+        const std::vector<unsigned short> tab = gelu_table_host();
+        Dev<unsigned short> dtab(tab.size(), tab.data());
+        ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, q80 ? 1 : 0};
+        launch_quant_act(dx.p, K, norm_w ? dnw.p : nullptr, eps, act, nullptr, nullptr, nullptr, 2, 0, nullptr,
+                         norm_b ? dnb.p : nullptr);
+        GemmParams p = mmq32_params(A, nullptr, ntok, dtp.p, dy.p, rows);
+        const int epis[3] = {EPI_STORE, EPI_ADD, EPI_GELU};
+        p.epi = epis[epilogue];
+        p.resid = epilogue == 1 ? dres.p : nullptr;
+        p.bias = bias ? dbias.p : nullptr;
+        p.gelu_tab = dtab.p;
+        launch_mmq32(p, act, nullptr, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dy.download(y);
+        if (q_out) {   // the MFMA-fragment order back to token order: element 32 j + 16 h + e of superblock sb
+            std::vector<int8_t> hq(dq.n);
+            dq.download(hq.data());
+            for (int t = 0; t < ntok; ++t)
+                for (int sb = 0; sb < nb; ++sb)
+                    for (int j = 0; j < 8; ++j)
+                        for (int h = 0; h < 2; ++h)
+                            std::memcpy(q_out + (size_t)t * K + sb * 256 + 32 * j + 16 * h,
+                                        hq.data() + (((size_t)(t / 32) * nb + sb) * 8 + j) * 1024 + (h * 32 + t % 32) * 16, 16);
+        }
+        if (d_out) {   // dT [scale][npad] -> [ntok][scale]
+            std::vector<float> hd(ddT.n);
+            ddT.download(hd.data());
+            for (int t = 0; t < ntok; ++t)
+                for (int b = 0; b < nd; ++b) d_out[(size_t)t * nd + b] = hd[(size_t)b * npad + t];
+        }
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
 int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_cells,
                               int32_t ntok, const float* q, const uint16_t* k_f16, const uint16_t* v_f16,
                               const int32_t* cell_pos, const int32_t* tok_cell, const int32_t* tok_pos, float* out) {

@@ -104,6 +104,7 @@ _SIGS = {
     "mi_prof_read": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_int32]),
     "mi_prof_ffn_bytes": (C.c_int64, [_P]),
     "mi_decode_path": (C.c_int32, [_P]),
+    "mi_batch_path": (C.c_int32, [_P]),
     "mi_op_dgemv": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_op_fgemv": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
@@ -124,6 +125,8 @@ _SIGS = {
     "mi_op_gemm": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_attention_batch": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           _P, _P, _P, _P, _P, _P, _P]),
+    "mi_op_gemm_bias": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float,
+                                    _P, _P, C.c_int32, _P, _P, _P]),
     "mi_op_router": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P,
                                  _P, _P, _P]),
     "mi_op_moe_group": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
@@ -448,6 +451,12 @@ class Context:
         2: an encoder context (bert)."""
         return int(lib().mi_decode_path(self.h))
 
+    def batch_path(self) -> int:
+        """The form the most recent decode call took (its first physical batch's): 0 one decode step
+        per token, 1 the v_dot4 GEMM, 2 the tiled int8-MFMA GEMM, 3 the short split-K GEMM, 4 the F16
+        MFMA GEMM, 5 an encoder pass; -1 before the first call."""
+        return int(lib().mi_batch_path(self.h))
+
     @property
     def prof_bytes(self) -> int:
         """Algorithmic bytes of the launch prof_read last timed (the FFN gate/up GEMV)."""
@@ -592,6 +601,29 @@ def op_gemm(type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, raw_u
     _check(lib().mi_op_gemm(device, type_, _ptr(raw), None if up is None else _ptr(up), rows, K, ntok, _ptr(x),
                             _ptr(y)), "op_gemm")
     return y
+
+
+GEMM_BIAS_PLAIN, GEMM_BIAS_ADD, GEMM_BIAS_GELU = 0, 1, 2
+
+
+def op_gemm_bias(type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, bias=None, resid=None,
+                 epilogue: int = GEMM_BIAS_PLAIN, norm_w=None, norm_b=None, eps: float = 1e-5, device: int = 0):
+    """mi_op_gemm_bias: a GPT-2 prompt-batch projection on the tiled int8-MFMA GEMM.  x (ntok, K) f32
+    [layer-normed with norm_w / norm_b] quantised by the batch path, times the rows x K matrix, + bias,
+    then the epilogue (0 store, 1 + resid, 2 GELU).  Returns (y (ntok, rows) f32, q (ntok, K) int8,
+    d (ntok, K / 256 or K / 32) f32): the output and the quantised activation in token order."""
+    raw = np.ascontiguousarray(raw, np.uint8)
+    x = np.ascontiguousarray(x, np.float32)
+    ntok = x.shape[0]
+    opt = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    bias, resid, norm_w, norm_b = opt(bias), opt(resid), opt(norm_w), opt(norm_b)
+    ptr = lambda a: None if a is None else _ptr(a)
+    y = np.empty((ntok, rows), np.float32)
+    q = np.empty((ntok, K), np.int8)
+    d = np.empty((ntok, K // (32 if type_ in (8, 2, 6) else 256)), np.float32)   # Q8_0 / Q4_0 / Q5_0: per 32
+    _check(lib().mi_op_gemm_bias(device, type_, _ptr(raw), rows, K, ntok, _ptr(x), ptr(norm_w), ptr(norm_b), eps,
+                                 ptr(bias), ptr(resid), epilogue, _ptr(y), _ptr(q), _ptr(d)), "op_gemm_bias")
+    return y, q, d
 
 
 def op_attention_batch(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, n_head_kv: int, tok_cell, tok_pos=None,

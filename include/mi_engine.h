@@ -276,6 +276,11 @@ int64_t mi_prof_bytes(const mi_ctx* ctx);
  * of enc.hip), 3 an unquantised F16 LLaMA model (the F16 streaming GEMV launches of fgemv.hip; prompt
  * batches on the F16 MFMA GEMM of enc.hip); -1 for a null context. */
 int32_t mi_decode_path(const mi_ctx* ctx);
+/* Diagnostics: the form the most recent mi_decode call took (of a call of several physical batches:
+ * its first): 0 one decode step per token, 1 the v_dot4 GEMM, 2 the tiled int8-MFMA GEMM, 3 the
+ * short split-K GEMM, 4 the F16 MFMA GEMM, 5 an encoder pass; -1 for a null context or before the
+ * first call.  Pure reporting. */
+int32_t mi_batch_path(const mi_ctx* ctx);
 /* Diagnostics: copies the per-workgroup s_memrealtime stamps (100 MHz) of the
  * first n_launch launches of the last decode step, [launch][512][8] uint64, to
  * out.  Returns the number of launches copied; 0 unless the library is the
@@ -312,6 +317,17 @@ int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t
  * (raw_blocks = gate): y[t][r] = silu(gate_r . q(x_t)) * (up_r . q(x_t)).  y: [ntok][rows]. */
 int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw_blocks, const void* raw_up, int32_t rows,
                    int32_t K, int32_t ntok, const float* x, float* y);
+/* A GPT-2 prompt-batch projection (llm_build_gpt2) on the tiled int8-MFMA GEMM, whatever ntok:
+ * ntok <= 512 rows x[ntok][K] quantised by the batch path's quantiser -- norm_w and norm_b given:
+ * layer_norm(x, eps) * norm_w + norm_b first (ggml_norm: sums in double, mean and variance in
+ * float); both NULL: x itself -- then y[t][r] = vec_dot(W_r, q(x_t)) + bias[r] (bias NULL: none)
+ * through the epilogue: 0 store, 1 + resid[t][r] (after the bias), 2 gelu(.) by ggml's f16 table.
+ * y, resid: [ntok][rows].  q_out / d_out (nullable): the quantised activation in token order,
+ * q_out[ntok][K] and d_out[ntok][K / 256] (Q8_K, k-quant matrices) or [ntok][K / 32] (Q8_0). */
+int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
+                        int32_t ntok, const float* x, const float* norm_w, const float* norm_b, float eps,
+                        const float* bias, const float* resid, int32_t epilogue, float* y, int8_t* q_out,
+                        float* d_out);
 /* The prompt-batch attention (attn_mfma: f16 MFMA) of ntok query tokens q[ntok][n_head*head_dim]
  * over an f16 cache of n_cells cells: token t sits in cell tok_cell[t] at position tok_pos[t] and
  * sees the cells c <= tok_cell[t] whose cell_pos[c] <= tok_pos[t] (llm_build_llama's kq_mask).
