@@ -3,6 +3,7 @@
 // itself (expert layout, MFMA-order copies, launch parameter blocks) is built by the engine's own
 // functions.
 #include "engine.h"
+#include "qdot.h"   // act_layout: where a published activation keeps its parts
 
 #include <algorithm>
 #include <cmath>
@@ -442,6 +443,160 @@ int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t
         const int v[10] = {k.kernel, k.R, k.LPC, k.HG, k.NWV, k.grid_x, k.grid_y, k.block, (int)k.lds, k.qsplit};
         std::copy(v, v + 10, out);
         return 0;
+    }
+    MI_TRY(-1)
+}
+
+// One decode step's attention through launch_attn in a given mode, with the output the engine's next
+// launch reads: the activation published in act_layout (ATTN_DECODE_QUANT: by the attention kernel;
+// ATTN_DECODE_SPLIT: by attn_combine_quant over the two launches' partials), unpacked.  Returns the
+// plan's kernel (AK_*).
+int32_t mi_op_attention_decode(int32_t device, int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                               int32_t n_ctx, int32_t cell, int32_t pos, const float* q, const uint16_t* k_f16,
+                               const uint16_t* v_f16, const int32_t* cell_pos, int32_t fmt, int32_t want_f32, float* out,
+                               int8_t* q8k, int32_t* bsums, float* dk, int8_t* q80, float* d0) {
+    try {
+        if (mode != ATTN_DECODE_QUANT && mode != ATTN_DECODE_FUSED && mode != ATTN_DECODE_SPLIT)
+            throw Error("attention_decode: mode 0 (quantising), 1 (fused) or 2 (two launches)");
+        if (!q || !k_f16 || !v_f16 || !cell_pos) throw Error("attention_decode: null argument");
+        if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || head_dim <= 0 || n_ctx <= 0)
+            throw Error("attention_decode: bad shape");
+        if (cell < 0 || cell >= n_ctx) throw Error("attention_decode: cell outside the cache");
+        const bool split = mode == ATTN_DECODE_SPLIT;
+        if (split ? cell < ATTN_SHORT : cell >= ATTN_SHORT)
+            throw Error("attention_decode: the single launch serves up to 512 cells, the two launches more");
+        if (fmt < 0 || fmt > 3 || (mode == ATTN_DECODE_QUANT && !fmt) || (mode == ATTN_DECODE_FUSED && fmt))
+            throw Error("attention_decode: fmt bit 0 Q8_K, bit 1 Q8_0 (the fused mode: 0)");
+        const int wk = fmt & 1, w0 = fmt >> 1;
+        if ((want_f32 || !fmt) && !out) throw Error("attention_decode: no f32 output buffer");
+        if ((wk && (!q8k || !bsums || !dk)) || (w0 && (!q80 || !d0))) throw Error("attention_decode: no buffer for a format asked for");
+        const AttnPlan plan = attn_plan((AttnMode)mode, n_head, n_head_kv, head_dim, n_ctx, 1, false);
+        if (plan.kernel == AK_NONE) throw Error("attention_decode: no kernel serves this head geometry in this mode");
+        const int kv_dim = n_head_kv * head_dim, K = n_head * head_dim;
+        if (fmt && K % 256) throw Error("attention_decode: a quantised output needs n_head * head_dim in whole 256-blocks");
+        MI_HIP(hipSetDevice(device));
+        const size_t kvn = (size_t)n_ctx * kv_dim;
+        const int tp[4] = {0, pos, cell, 0};   // {token, query position, last cell}
+        Dev<float> dq(K, q), dsc(split ? (size_t)n_head * n_ctx : 1), dsm((size_t)ATTN_SMAX * n_head);
+        Dev<float> dpo((size_t)(split ? ATTN_SMAX : 1) * K), dout(K);
+        Dev<__half> dkc(kvn, f16(k_f16)), dvc(kvn, f16(v_f16));
+        Dev<int> dcp(n_ctx, cell_pos), dtp(4, tp);
+        Dev<char> act(fmt ? dv_act_bytes(K, wk, w0) : 16);
+        // what the launches do not write stays recognisable: NaN floats, quants of -128
+        dpo.fill(0xFF);
+        dout.fill(0xFF);
+        act.fill(0x80);
+        AttnParams a{dq.p, dkc.p, dvc.p, dtp.p, dcp.p, dsc.p, dsm.p, dpo.p, n_head, n_head_kv, head_dim, kv_dim,
+                     n_ctx, 1.0f / std::sqrt((float)head_dim)};
+        a.fused = split ? 0 : 1;
+        a.long_off = 1;   // past 512 cells: the two launches (the exchange kernel is mi_op_attention's)
+        const ActOut ao{K, wk, w0, act.p, nullptr, 0.0f};
+        const AttnPartials parts{dpo.p, n_head, head_dim};
+        const float* f32 = dout.p;
+        if (split) {
+            launch_attn(a, nullptr);
+            launch_attn_combine(parts, dtp.p, dout.p, nullptr);
+            if (fmt) launch_attn_combine_quant(parts, dtp.p, ao, nullptr);
+        } else {
+            if (fmt) a.act_out = ao;
+            // the decode kernel stores the f32 row on request only; the fused kernel always, as split 0
+            if (plan.kernel == AK_DEC) a.out_f32 = want_f32 ? dout.p : nullptr;
+            else f32 = dpo.p;
+            launch_attn(a, nullptr);
+        }
+        MI_HIP(hipDeviceSynchronize());
+        if (want_f32 || !fmt) MI_HIP(hipMemcpy(out, f32, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+        if (fmt) {
+            std::vector<char> h(act.n);
+            act.download(h.data());
+            const ActLayout L = act_layout(K, wk, w0);
+            if (wk) {
+                std::memcpy(q8k, h.data() + L.q8k, (size_t)K);
+                std::memcpy(bsums, h.data() + L.bsum, (size_t)L.nb * 16 * sizeof(int32_t));
+                std::memcpy(dk, h.data() + L.dk, (size_t)L.nb * sizeof(float));
+            }
+            if (w0) {
+                std::memcpy(q80, h.data() + L.q80, (size_t)K);
+                std::memcpy(d0, h.data() + L.d0, (size_t)L.nb * 8 * sizeof(float));
+            }
+        }
+        return plan.kernel;
+    }
+    MI_TRY(-1)
+}
+
+// A short batch's attention through launch_attn_multi: ntok tokens over up to ATTN_SHORT cells, one
+// grid row per token; with `quant` each token's output also quantised into the batch GEMMs' format
+// (ActQ8, sized as mi_op_gemm sizes it), brought back to token order.  Returns the plan's kernel.
+int32_t mi_op_attention_short(int32_t device, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_cells,
+                              int32_t ntok, const float* q, const uint16_t* k_f16, const uint16_t* v_f16,
+                              const int32_t* cell_pos, const int32_t* tok_cell, const int32_t* tok_pos, int32_t quant,
+                              float* out, int8_t* q_out, float* d_out, int32_t* bsums_out) {
+    try {
+        if (!q || !k_f16 || !v_f16 || !cell_pos || !tok_cell || !tok_pos || !out) throw Error("attention_short: null argument");
+        if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || head_dim <= 0 || n_cells <= 0)
+            throw Error("attention_short: bad shape");
+        if (ntok < 1 || ntok > MMQS_MAX) throw Error("attention_short: 1..64 tokens");
+        if (quant < 0 || quant > 2) throw Error("attention_short: quant 0 (none), 1 (Q8_K) or 2 (Q8_0)");
+        if (quant && (!q_out || !d_out || (quant == 1 && !bsums_out))) throw Error("attention_short: no buffer for the quantised rows");
+        for (int t = 0; t < ntok; ++t) {
+            if (tok_cell[t] < 0 || tok_cell[t] >= n_cells || tok_cell[t] >= ATTN_SHORT)
+                throw Error("attention_short: token cell out of range (the cache, and 512 cells)");
+            if (t && tok_cell[t] <= tok_cell[t - 1]) throw Error("attention_short: token cells must ascend");
+        }
+        const AttnPlan plan = attn_plan(quant ? ATTN_BATCH_QUANT : ATTN_BATCH_FUSED, n_head, n_head_kv, head_dim, n_cells, ntok, false);
+        if (plan.kernel == AK_NONE) throw Error("attention_short: no kernel serves this head geometry in this mode");
+        const int kv_dim = n_head_kv * head_dim, K = n_head * head_dim;
+        if (quant && K % 256) throw Error("attention_short: a quantised output needs n_head * head_dim in whole 256-blocks");
+        MI_HIP(hipSetDevice(device));
+        const size_t kvn = (size_t)n_cells * kv_dim;
+        std::vector<int> tp((size_t)ntok * 4, 0);
+        for (int t = 0; t < ntok; ++t) {
+            tp[t * 4 + 1] = tok_pos[t];
+            tp[t * 4 + 2] = tok_cell[t];
+        }
+        const bool q80 = quant == 2;
+        const size_t npad = (size_t)(ntok + 31) / 32 * 32;
+        const int nb = K / 256, nd = q80 ? K / 32 : nb;   // scales per row
+        Dev<float> dq((size_t)ntok * K, q), dout((size_t)ntok * K), ddT(quant ? npad * (K / 32) : 1);
+        Dev<int8_t> dqa(quant ? npad * K : 1), dbs(quant ? npad * nb * 16 : 1);
+        Dev<__half> dkc(kvn, f16(k_f16)), dvc(kvn, f16(v_f16));
+        Dev<int> dcp(n_cells, cell_pos), dtp(tp.size(), tp.data());
+        // what the launch does not write stays recognisable: NaN floats, quants and sum bytes of -128
+        dout.fill(0xFF);
+        ddT.fill(0xFF);
+        dqa.fill(0x80);
+        dbs.fill(0x80);
+        AttnParams a{dq.p, dkc.p, dvc.p, dtp.p, dcp.p, nullptr, nullptr, nullptr, n_head, n_head_kv, head_dim, kv_dim,
+                     n_cells, 1.0f / std::sqrt((float)head_dim)};
+        if (quant) {
+            a.act_q8 = ActQ8{dqa.p, ddT.p, dbs.p, K, ntok, (int)npad, q80 ? 1 : 0};
+            if (plan.kernel == AK_DEC) a.out_f32 = dout.p;   // the fused kernel stores the rows at `out` anyway
+        }
+        launch_attn_multi(a, ntok, dout.p, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dout.download(out);
+        if (!quant) return plan.kernel;
+        // the MFMA-fragment order back to token order: element 32 j + 16 h + e of superblock sb
+        std::vector<int8_t> hq(dqa.n), hb(dbs.n);
+        std::vector<float> hd(ddT.n);
+        dqa.download(hq.data());
+        dbs.download(hb.data());
+        ddT.download(hd.data());
+        for (int t = 0; t < ntok; ++t)
+            for (int sb = 0; sb < nb; ++sb) {
+                for (int j = 0; j < 8; ++j)
+                    for (int h = 0; h < 2; ++h)
+                        std::memcpy(q_out + (size_t)t * K + sb * 256 + 32 * j + 16 * h,
+                                    hq.data() + (((size_t)(t / 32) * nb + sb) * 8 + j) * 1024 + (h * 32 + t % 32) * 16, 16);
+                if (q80) continue;
+                // the 32-element sums, byte-split: 64 * hi (bytes 0-7) + lo (bytes 8-15)
+                const int8_t* b = hb.data() + (((size_t)(t / 32) * nb + sb) * 32 + t % 32) * 16;
+                for (int j = 0; j < 8; ++j) bsums_out[((size_t)t * nb + sb) * 8 + j] = 64 * (int)b[j] + (int)b[8 + j];
+            }
+        for (int t = 0; t < ntok; ++t)   // dT [scale][npad] -> [ntok][scale]
+            for (int b = 0; b < nd; ++b) d_out[(size_t)t * nd + b] = hd[(size_t)b * npad + t];
+        return plan.kernel;
     }
     MI_TRY(-1)
 }

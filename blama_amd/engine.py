@@ -120,6 +120,8 @@ _SIGS = {
     "mi_op_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                     C.c_int32, _P]),
     "mi_op_attn_plan": (C.c_int32, [C.c_int32] * 7 + [_P]),
+    "mi_op_attention_decode": (C.c_int32, [C.c_int32] * 8 + [_P, _P, _P, _P, C.c_int32, C.c_int32] + [_P] * 6),
+    "mi_op_attention_short": (C.c_int32, [C.c_int32] * 6 + [_P] * 6 + [C.c_int32] + [_P] * 4),
     "mi_op_gemv_bench": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_float)]),
     "mi_op_gemm": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
@@ -586,6 +588,69 @@ def op_attn_plan(mode: int, n_head: int, n_head_kv: int, hd: int, n_ctx: int = 5
     out = np.zeros(len(ATTN_PLAN_FIELDS), np.int32)
     _check(lib().mi_op_attn_plan(mode, n_head, n_head_kv, hd, n_ctx, ntok, int(long_ok), _ptr(out)), "op_attn_plan")
     return dict(zip(ATTN_PLAN_FIELDS, (int(v) for v in out)))
+
+
+ATTN_DECODE_QUANT, ATTN_DECODE_FUSED, ATTN_DECODE_SPLIT, ATTN_BATCH_QUANT, ATTN_BATCH_FUSED = range(5)   # AttnMode
+AK_NONE, AK_DEC, AK_FUSED, AK_LONG, AK_SCORES_PV = range(5)                                              # AttnKernel
+ATTN_FMT_Q8K, ATTN_FMT_Q80 = 1, 2
+
+
+def op_attention_decode(mode: int, q: np.ndarray, k16: np.ndarray, v16: np.ndarray, n_head_kv: int, cell: int,
+                        cell_pos=None, pos=None, fmt: int = 0, want_f32: bool = True, device: int = 0) -> dict:
+    """mi_op_attention_decode: one decode step's attention in `mode` (ATTN_DECODE_*).  q (n_head, hd)
+    f32; k16 / v16 (n_ctx, n_head_kv * hd) f16, cells 0 .. cell the context; fmt: ATTN_FMT_Q8K |
+    ATTN_FMT_Q80.  Returns a dict: kernel (AK_*), out (n_head * hd,) f32 or None (want_f32 false on a
+    quantising mode), and per format asked for q8k (K // 256, 256) int8, bsums (K // 256, 16) int32,
+    dk (K // 256,) f32; q80 (K // 32, 32) int8, d0 (K // 32,) f32."""
+    q = np.ascontiguousarray(q, np.float32)
+    n_head, hd = q.shape
+    k16 = np.ascontiguousarray(k16, np.float16)
+    v16 = np.ascontiguousarray(v16, np.float16)
+    n_ctx, K = k16.shape[0], n_head * hd
+    cp = np.ascontiguousarray(np.arange(n_ctx) if cell_pos is None else cell_pos, np.int32)
+    if k16.shape != (n_ctx, n_head_kv * hd) or v16.shape != k16.shape or cp.shape != (n_ctx,):
+        raise ValueError("op_attention_decode: cache shapes")
+    pos = cell if pos is None else pos
+    r = {"out": np.empty(K, np.float32) if want_f32 or not fmt else None}
+    if fmt & ATTN_FMT_Q8K:
+        r.update(q8k=np.empty((K // 256, 256), np.int8), bsums=np.empty((K // 256, 16), np.int32),
+                 dk=np.empty(K // 256, np.float32))
+    if fmt & ATTN_FMT_Q80:
+        r.update(q80=np.empty((K // 32, 32), np.int8), d0=np.empty(K // 32, np.float32))
+    ptr = lambda name: None if r.get(name) is None else _ptr(r[name])
+    r["kernel"] = _check(lib().mi_op_attention_decode(
+        device, mode, n_head, n_head_kv, hd, n_ctx, cell, pos, _ptr(q), _ptr(k16), _ptr(v16), _ptr(cp), fmt,
+        int(bool(want_f32)), ptr("out"), ptr("q8k"), ptr("bsums"), ptr("dk"), ptr("q80"), ptr("d0")), "op_attention_decode")
+    return r
+
+
+def op_attention_short(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, n_head_kv: int, tok_cell, tok_pos=None,
+                       cell_pos=None, quant: int = 0, device: int = 0) -> dict:
+    """mi_op_attention_short: a short batch's attention, op_attention_batch's arguments on the decode
+    step's kernels; quant 0 none, 1 Q8_K, 2 Q8_0.  Returns a dict: kernel (AK_*), out (ntok, n_head * hd)
+    f32, and with quant q (ntok, K) int8, d (ntok, K // 256 or K // 32) f32 and, for Q8_K, bsums
+    (ntok, K // 256, 8) int32 (32-element sums), all in token order."""
+    q = np.ascontiguousarray(q, np.float32)
+    ntok, n_head, hd = q.shape
+    k16 = np.ascontiguousarray(k16, np.float16)
+    v16 = np.ascontiguousarray(v16, np.float16)
+    n, K = k16.shape[0], n_head * hd
+    cp = np.ascontiguousarray(np.arange(n) if cell_pos is None else cell_pos, np.int32)
+    tc = np.ascontiguousarray(tok_cell, np.int32)
+    tpos = np.ascontiguousarray(tc if tok_pos is None else tok_pos, np.int32)
+    if k16.shape != (n, n_head_kv * hd) or v16.shape != k16.shape or cp.shape != (n,) or tc.shape != (ntok,) \
+            or tpos.shape != (ntok,):
+        raise ValueError("op_attention_short: shapes")
+    r = {"out": np.empty((ntok, K), np.float32)}
+    if quant:
+        r.update(q=np.empty((ntok, K), np.int8), d=np.empty((ntok, K // (256 if quant == 1 else 32)), np.float32))
+    if quant == 1:
+        r["bsums"] = np.empty((ntok, K // 256, 8), np.int32)
+    ptr = lambda name: None if r.get(name) is None else _ptr(r[name])
+    r["kernel"] = _check(lib().mi_op_attention_short(
+        device, n_head, n_head_kv, hd, n, ntok, _ptr(q), _ptr(k16), _ptr(v16), _ptr(cp), _ptr(tc), _ptr(tpos), quant,
+        ptr("out"), ptr("q"), ptr("d"), ptr("bsums")), "op_attention_short")
+    return r
 
 
 def op_gemm(type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, raw_up=None,

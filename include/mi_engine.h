@@ -309,6 +309,33 @@ int32_t mi_op_attention(int32_t device, int32_t n_head, int32_t n_head_kv, int32
  * 3 long, 4 scores + pv), R, LPC, HG, NWV, grid_x, grid_y, block, dynamic LDS bytes, qsplit. */
 int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_ctx,
                         int32_t ntok, int32_t long_ok, int32_t* out);
+/* One decode step's attention as the engine launches it in `mode` (mi_op_attn_plan's 0, 1 or 2),
+ * with the activation it publishes for the W_o launch.  The cache holds n_ctx rows
+ * [n_ctx][n_head_kv*head_dim], of which cells 0 .. cell are the context (rows past `cell` are never
+ * read into the result); a cell c is visible iff c <= cell and cell_pos[c] <= pos.
+ * mode 0 (cell < 512): the launch also quantises its output, fmt bit 0 Q8_K, bit 1 Q8_0 (one or
+ * both); the f32 row is returned only with want_f32 (the decode kernel stores it on request).
+ * mode 1 (cell < 512): no quantised output (fmt 0).  mode 2 (cell >= 512): the scores and pv
+ * launches, never the single exchange launch; their partials combined to f32 and, with fmt, also
+ * quantised by the combine-and-quantise launch.
+ * out: [n_head*head_dim] (K).  The activation unpacked from its published layout: q8k[K],
+ * bsums[K/256][16] (16-element sums), dk[K/256]; q80[K], d0[K/32].  Buffers of a format not asked for
+ * may be NULL.  Returns the plan's kernel (mi_op_attn_plan's out[0]), or -1: a geometry without a
+ * plan in this mode is an error, nothing is launched. */
+int32_t mi_op_attention_decode(int32_t device, int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                               int32_t n_ctx, int32_t cell, int32_t pos, const float* q, const uint16_t* k_f16,
+                               const uint16_t* v_f16, const int32_t* cell_pos, int32_t fmt, int32_t want_f32,
+                               float* out, int8_t* q8k, int32_t* bsums, float* dk, int8_t* q80, float* d0);
+/* A short batch's attention (1 <= ntok <= 64 tokens, every token cell < 512), one grid row per token:
+ * mi_op_attention_batch's inputs on the decode step's kernels.  quant 0: f32 rows only; 1 / 2: every
+ * token's row also quantised to Q8_K / Q8_0 in the batch GEMMs' activation format, returned in token
+ * order: q_out[ntok][K], d_out[ntok][K/256] (Q8_K) or [ntok][K/32] (Q8_0), and for Q8_K
+ * bsums_out[ntok][K/256][8], the 32-element sums.  out: [ntok][K], K = n_head*head_dim.  Returns the
+ * plan's kernel, or -1 (no plan for the geometry: nothing is launched). */
+int32_t mi_op_attention_short(int32_t device, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_cells,
+                              int32_t ntok, const float* q, const uint16_t* k_f16, const uint16_t* v_f16,
+                              const int32_t* cell_pos, const int32_t* tok_cell, const int32_t* tok_pos,
+                              int32_t quant, float* out, int8_t* q_out, float* d_out, int32_t* bsums_out);
 /* The prompt-batch GEMM (Session.cpp:381-392's n_ubatch physical batches; ntok <= MI_MMQS_MAX,
  * default 64: the short-batch GEMM mmqs, otherwise the tiled int8-MFMA GEMM mmq32) of
  * ntok <= 512 token rows x[ntok][K] against a rows x K Q4_K / Q5_K / Q6_K / Q8_0 matrix: each row's
