@@ -346,18 +346,18 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams P, 
 
 bool attn_mfma_supported(int head_dim) { return head_dim == 64 || head_dim == 128; }
 
+// Once per device (init_gemm_attributes): the V chunks' LDS limit
+void init_attn_mfma_attributes() {
+    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(amf::attn_mfma_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(amf::attn_mfma_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+}
+
 void launch_attn_mfma(const AttnParams& p, int ntok, float* out, hipStream_t s) {
     if (ntok < 1) return;
     if (p.n_head % p.n_head_kv) throw Error("attn_mfma: n_head must be a multiple of n_head_kv");
     if (p.n_ctx < 4) throw Error("attn_mfma: n_ctx must be at least 4");
     const dim3 grid(p.n_head, (ntok + 31) / 32);
     const size_t lds = (size_t)amf::NW * amf::CH * p.head_dim * 2;
-    static bool attr = false;
-    if (!attr) {
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(amf::attn_mfma_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(amf::attn_mfma_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        attr = true;
-    }
     if (p.head_dim == 128) hipLaunchKernelGGL(amf::attn_mfma_kernel<128>, grid, dim3(64 * amf::NW), lds, s, p, ntok, out);
     else if (p.head_dim == 64) hipLaunchKernelGGL(amf::attn_mfma_kernel<64>, grid, dim3(64 * amf::NW), lds, s, p, ntok, out);
     else throw Error("attn_mfma: head_dim 64 or 128");

@@ -260,6 +260,52 @@ ActQ8 Ctx::moe_act(int K, int cap, bool q80) const {
     return a;
 }
 
+// ---- what launch_quant_act quantises (engine.h) ----
+QuantAct Ctx::qa_rows(const float* x, int K) const {
+    QuantAct q{};
+    q.x = x;
+    q.x_stride = K;
+    q.eps = m->hp.eps;
+    return q;
+}
+QuantAct Ctx::qa_norm(const float* x, int K, const float* norm_w, PendParts pend) const {
+    QuantAct q = qa_rows(x, K);
+    q.norm_w = norm_w;
+    if (pend.part) {
+        q.part = pend.part;
+        q.nks = pend.nks;
+        q.addend = pend.addend;
+    }
+    return q;
+}
+QuantAct Ctx::qa_layernorm(const float* x, int K, const float* norm_w, const float* norm_b) const {
+    QuantAct q = qa_norm(x, K, norm_w);
+    q.norm_b = norm_b;
+    return q;
+}
+QuantAct Ctx::qa_swiglu(const float* part, int nks, int K) const {
+    QuantAct q{};
+    q.x_stride = K;
+    q.eps = m->hp.eps;
+    q.part = part;
+    q.nks = nks;
+    q.swiglu = 1;
+    return q;
+}
+// the plain sum of kp parts [kp][ntok][pstride] over `rows` rows into out (the caller adds a
+// residual, an addend or SwiGLU by name)
+static PartSum part_sum(const float* part, int kp, int ntok, int rows, int pstride, float* out, int ostride) {
+    PartSum p{};
+    p.part = part;
+    p.kp = kp;
+    p.ntok = ntok;
+    p.rows = rows;
+    p.pstride = pstride;
+    p.out = out;
+    p.ostride = ostride;
+    return p;
+}
+
 // build_moe_ffn over a physical batch: routing, one quantisation of every row, ONE grouped mmq32
 // launch for the experts' gate/up + SwiGLU and one for their down projections (a workgroup per
 // (expert, row tile) over that expert's token tiles), then every token's x += w0*y0 + w1*y1 in
@@ -270,11 +316,15 @@ void Ctx::moe_ffn_batch(int l, int nt, const float* pend) {
     const int cap = moe_route(l, nt, pend);
     // gate/up + SwiGLU: rms_norm(x) * ffn_norm of each row's token
     const ActQ8 act = moe_act(hp.n_embd, cap, takes_q80(L.gate.type));
-    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
+    QuantAct q = qa_norm(xb, hp.n_embd, L.ffn_norm);
+    q.rows = moe_rows;
+    launch_quant_act(q, act, stream);
     launch_mmq32(mmq32_params(L.gate, &L.up, cap, tokpos_b, hb, hp.n_ff, moe_grp, nt), act, ub_rope, stream);
     // down: every row of the FFN output, stored (weighted and summed by the combine)
     const ActQ8 a2 = moe_act(hp.n_ff, cap, takes_q80(L.down.type));
-    launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel);
+    q = qa_rows(hb, hp.n_ff);
+    q.rows = moe_rowsel;
+    launch_quant_act(q, a2, stream);
     launch_mmq32(mmq32_params(L.down, nullptr, cap, tokpos_b, yb, hp.n_embd, moe_grp, nt), a2, ub_rope, stream);
     launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
 }
@@ -290,13 +340,17 @@ void Ctx::moe_ffn_short(int l, int nt) {
     const int E = hp.n_expert;
     const int cap = moe_route(l, nt, nullptr);
     const ActQ8 act = moe_act(hp.n_embd, cap, false);
-    launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, moe_rows);
+    QuantAct q = qa_norm(xb, hp.n_embd, L.ffn_norm);
+    q.rows = moe_rows;
+    launch_quant_act(q, act, stream);
     // an expert receives each token at most once: at most nt rows
     const int kg = launch_mmqs_grouped(L.gate, true, hp.n_ff, act, ub_spart, 2 * hp.n_ff, moe_grp, E, nt, stream);
     const ActQ8 a2 = moe_act(hp.n_ff, cap, false);
-    launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, moe_rowsel, ub_spart, kg, 1);
+    q = qa_swiglu(ub_spart, kg, hp.n_ff);
+    q.rows = moe_rowsel;   // (rows[t] < 0: a padding row)
+    launch_quant_act(q, a2, stream);
     const int kd = launch_mmqs_grouped(L.down, false, 0, a2, ub_spart, hp.n_embd, moe_grp, E, nt, stream);
-    launch_part_sum(ub_spart, kd, cap, hp.n_embd, hp.n_embd, nullptr, 0, yb, hp.n_embd, stream);
+    launch_part_sum(part_sum(ub_spart, kd, cap, hp.n_embd, hp.n_embd, yb, hp.n_embd), stream);
     launch_moe_combine(yb, moe_pos, selw_b, xb, nt, hp.n_embd, stream, cvec_for(l));
 }
 
@@ -355,8 +409,8 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             const QkvGroups G = qkv_type_groups(L);
             for (int f = 0; f < 2; ++f)
                 if (G.fmt >> f & 1) {
-                    launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                     nullptr, pend, ks, 0, pend ? pend_add : nullptr);
+                    launch_quant_act(qa_norm(xb, hp.n_embd, L.attn_norm, {pend, ks, pend_add}),
+                                     ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream);
                     pend = nullptr;
                 }
             // LoRA: a group's terms of the batch after the quant_act of its input, before the GEMM
@@ -370,7 +424,7 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             else launch_attn_multi(battn_params(l), nt, attnb, stream);
             {   // output projection + residual
                 const ActQ8 act = ub_act(hp.n_embd, nt, L.wo.type);
-                launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act, stream);
+                launch_quant_act(qa_rows(attnb, hp.n_embd), act, stream);
                 pre = lora_pre_terms(l, 1, attnb, hp.n_embd, nt, nullptr);
                 GemmParams p = bwo_params(l, nt, false, pre);
                 // parts of K; the FFN's quant_act adds them (not with an adapter on this W_o: its terms
@@ -389,14 +443,14 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             }
             {   // FFN gate/up + SwiGLU
                 const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
-                launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, pend, ks);
+                launch_quant_act(qa_norm(xb, hp.n_embd, L.ffn_norm, {pend, ks}), act, stream);   // (W_o's parts)
                 pend = nullptr;
                 pre = lora_pre_terms(l, 2, xb, hp.n_embd, nt, L.ffn_norm);
                 launch_mmq32(bgate_up_params(l, nt, false, pre), act, ub_rope, stream);
             }
             {   // FFN down + residual
                 const ActQ8 act = ub_act(hp.n_ff, nt, L.down.type);
-                launch_quant_act(hb, hp.n_ff, nullptr, hp.eps, act, stream);
+                launch_quant_act(qa_rows(hb, hp.n_ff), act, stream);
                 pre = lora_pre_terms(l, 3, hb, hp.n_ff, nt, nullptr);
                 GemmParams p = bdown_params(l, nt, false, pre);
                 if (ub_part && L.down.nb >= ks && l + 1 < hp.n_layer && !pre) {   // the next layer's quant_act adds them,
@@ -413,7 +467,7 @@ void Ctx::decode_ubatch(const int32_t* tokens, int n, bool all) {
             embd_tail(xb, nt, c0);
         } else if (all) {   // final norm + output head over every token of the batch
             const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);   // the head's own activation format
-            launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream);
+            launch_quant_act(qa_norm(xb, hp.n_embd, m->output_norm), a_out, stream);
             GemmParams p;
             std::memset(&p, 0, sizeof(p));
             p.A = m->output;
@@ -455,30 +509,30 @@ void Ctx::enqueue_ubatch_gpt2(int nt, bool all, int c0, bool last) {
     const int ne = hp.n_embd;
     EmbedParams ep{m->tok_embd, tokpos_b, xb, ne, m->pos_embd, 1, nullptr};
     launch_embed_multi(ep, nt, stream);
-    // a LayerNorm'd (norm_w, norm_b set) or plain row set quantised for the matrix `type` reads
-    auto quant = [&](const float* rows, int K, const float* norm_w, const float* norm_b, int type) {
-        const ActQ8 act = ub_act(K, nt, type);
-        launch_quant_act(rows, K, norm_w, hp.eps, act, stream, nullptr, nullptr, 2, 0, nullptr, norm_b);
+    // a row set quantised for the matrix `type` reads
+    auto quant = [&](const QuantAct& q, int type) {
+        const ActQ8 act = ub_act(q.x_stride, nt, type);
+        launch_quant_act(q, act, stream);
         return act;
     };
     for (int l = 0; l < hp.n_layer; ++l) {
         const Layer& L = m->layers[l];
         {
-            const ActQ8 act = quant(xb, ne, L.attn_norm, L.attn_norm_b, L.qkv[0].type);
+            const ActQ8 act = quant(qa_layernorm(xb, ne, L.attn_norm, L.attn_norm_b), L.qkv[0].type);
             const int row0[3] = {0, ne, 2 * ne}, nrows[3] = {ne, ne, ne};
             const int epi[3] = {EPI_STORE, EPI_ROPE_K, EPI_V};   // (n_rot 0: K rows unrotated)
             launch_mmq32_rows(bqkv_gpt2_params(l, nt), row0, nrows, epi, 3, act, ub_rope, stream);
         }
         if (attn_mfma) launch_attn_mfma(battn_params(l), nt, attnb, stream);
         else launch_attn_multi(battn_params(l), nt, attnb, stream);
-        launch_mmq32(bwo_params(l, nt, false, nullptr), quant(attnb, ne, nullptr, nullptr, L.wo.type), ub_rope, stream);
-        launch_mmq32(bup_gelu_params(l, nt), quant(xb, ne, L.ffn_norm, L.ffn_norm_b, L.up.type), ub_rope, stream);
-        launch_mmq32(bdown_params(l, nt, false, nullptr), quant(hb, hp.n_ff, nullptr, nullptr, L.down.type), ub_rope, stream);
+        launch_mmq32(bwo_params(l, nt, false, nullptr), quant(qa_rows(attnb, ne), L.wo.type), ub_rope, stream);
+        launch_mmq32(bup_gelu_params(l, nt), quant(qa_layernorm(xb, ne, L.ffn_norm, L.ffn_norm_b), L.up.type), ub_rope, stream);
+        launch_mmq32(bdown_params(l, nt, false, nullptr), quant(qa_rows(hb, hp.n_ff), L.down.type), ub_rope, stream);
     }
     if (embeddings) {
         embd_tail(xb, nt, c0);
     } else if (all) {   // final LayerNorm + the tied head over every token of the batch
-        const ActQ8 a_out = quant(xb, ne, m->output_norm, m->output_norm_b, m->output.type);
+        const ActQ8 a_out = quant(qa_layernorm(xb, ne, m->output_norm, m->output_norm_b), m->output.type);
         launch_mmq32(mmq32_params(m->output, nullptr, nt, tokpos_b, logits_all + (size_t)c0 * hp.n_vocab, hp.n_vocab), a_out,
                      ub_rope, stream);
         finish_logits_all(c0, nt, last);
@@ -547,14 +601,22 @@ void Ctx::decode_f16_batch(const int32_t* tokens, int n, bool all) {
                 float* os[2] = {fb_t, fb_t + nff};
                 f16_gemm(ms, os, 2, fb_xn, nt, fb_t_stride, nullptr);
             }
-            launch_part_sum(fb_t, 1, nt, nff, fb_t_stride, nullptr, 0, hb, nff, stream, nff);   // silu(gate) * up
+            {   // silu(gate) * up
+                PartSum ps = part_sum(fb_t, 1, nt, nff, fb_t_stride, hb, nff);
+                ps.swiglu = nff;
+                launch_part_sum(ps, stream);
+            }
             {
                 const QMat* ms[1] = {&L.down};
                 float* os[1] = {xb};
                 f16_gemm(ms, os, 1, hb, nt, ne, xb);
             }
-            if (const float* cv = cvec_for(l))   // build_cvec: after the FFN residual add
-                launch_part_sum(xb, 1, nt, ne, ne, cv, 0, xb, ne, stream);
+            if (const float* cv = cvec_for(l)) {   // build_cvec: after the FFN residual add (the row as the "residual")
+                PartSum ps = part_sum(xb, 1, nt, ne, ne, xb, ne);
+                ps.resid = cv;
+                ps.rstride = 0;
+                launch_part_sum(ps, stream);
+            }
         }
         const bool last = c0 + nt == n;
         if (embeddings) {
@@ -586,26 +648,31 @@ void Ctx::enqueue_ubatch_short(int nt, bool all, int c0, bool last) {
     const int pend_k = ubatch_layers_short(nt);
     // (the parts pending are the last layer's FFN down's -- dense models; its control-vector row
     // goes in with them)
-    const float* pend_add = pend_k ? cvec_for(hp.n_layer - 1) : nullptr;
+    PendParts pend{};
+    if (pend_k) pend = {ub_spart, pend_k, cvec_for(hp.n_layer - 1)};
     if (all && !embeddings) {   // final norm + output head on mmqs, its parts summed into the logits rows
         const ActQ8 a_out = ub_act(hp.n_embd, nt, m->output.type);
-        launch_quant_act(xb, hp.n_embd, m->output_norm, hp.eps, a_out, stream, nullptr, pend_k ? ub_spart : nullptr,
-                         pend_k ? pend_k : 2, 0, pend_add);
+        launch_quant_act(qa_norm(xb, hp.n_embd, m->output_norm, pend), a_out, stream);
         const int kp = mmqs_one(m->output, false, 0, a_out, hp.n_vocab);
-        launch_part_sum(ub_spart, kp, nt, hp.n_vocab, hp.n_vocab, nullptr, 0, logits_all + (size_t)c0 * hp.n_vocab,
-                        hp.n_vocab, stream);
+        launch_part_sum(part_sum(ub_spart, kp, nt, hp.n_vocab, hp.n_vocab, logits_all + (size_t)c0 * hp.n_vocab, hp.n_vocab),
+                        stream);
         finish_logits_all(c0, nt, last);
     } else {
         // the last residual parts into xb (the next chunk, or the output, reads it)
-        if (pend_k)
-            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream, 0, pend_add);
+        if (pend_k) {
+            PartSum ps = part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd);
+            ps.resid = xb;
+            ps.rstride = hp.n_embd;
+            ps.addend = pend.addend;
+            launch_part_sum(ps, stream);
+        }
         if (embeddings) embd_tail(xb, nt, c0);   // embeddings mode: the rows of the now whole xb, no head
         else if (last) enqueue_output(ACT_PRO, xb + (size_t)(nt - 1) * hp.n_embd, nullptr);
     }
 }
 
 // One short physical batch (<= mmqs_max tokens) through the layers on the split-K streaming GEMM
-// (mmq.hip mmqs): every launch writes K-part sums to ub_spart, and the next kernel adds them --
+// (mmqs.hip): every launch writes K-part sums to ub_spart, and the next kernel adds them --
 // quant_act (the residual, or SwiGLU of the gate/up parts), qkv_finish (RoPE, KV append).
 // Returns the count of the last FFN down's parts, still to be added into xb.
 int Ctx::ubatch_layers_short(int nt) {
@@ -621,9 +688,9 @@ int Ctx::ubatch_layers_short(int nt) {
         for (int f = 0; f < 2; ++f)
             if (G.fmt >> f & 1) {
                 // (parts pending here are the previous layer's FFN down's: its control-vector row with them)
-                launch_quant_act(xb, hp.n_embd, L.attn_norm, hp.eps, ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream,
-                                 nullptr, pend_k ? ub_spart : nullptr, pend_k ? pend_k : 2, 0,
-                                 pend_k && l > 0 ? cvec_for(l - 1) : nullptr);
+                PendParts pend{};
+                if (pend_k) pend = {ub_spart, pend_k, l > 0 ? cvec_for(l - 1) : nullptr};
+                launch_quant_act(qa_norm(xb, hp.n_embd, L.attn_norm, pend), ub_act(hp.n_embd, nt, f ? T_Q8_0 : T_Q4_K), stream);
                 pend_k = 0;
             }
         int kp = 0;
@@ -648,28 +715,31 @@ int Ctx::ubatch_layers_short(int nt) {
         const bool qattn = attn_quant_supported(hp.n_head, hp.n_head_kv, hp.head_dim);
         if (attn_mfma && n_cells > ATTN_SHORT) {
             launch_attn_mfma(a, nt, attnb, stream);
-            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
+            launch_quant_act(qa_rows(attnb, hp.n_embd), act_wo, stream);
         } else if (qattn) {   // the launch also quantises each token's output for W_o
             a.act_q8 = act_wo;
             launch_attn_multi(a, nt, attnb, stream);
         } else {
             launch_attn_multi(a, nt, attnb, stream);
-            launch_quant_act(attnb, hp.n_embd, nullptr, hp.eps, act_wo, stream);
+            launch_quant_act(qa_rows(attnb, hp.n_embd), act_wo, stream);
         }
         // output projection: parts of W_o attn, added to x by the FFN's quant_act
         pend_k = mmqs_one(L.wo, false, 0, act_wo, hp.n_embd);
         if (hp.n_expert > 0) {   // routed experts: x += W_o parts first (the router reads x)
-            launch_part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd, xb, hp.n_embd, stream);
+            PartSum ps = part_sum(ub_spart, pend_k, nt, hp.n_embd, hp.n_embd, xb, hp.n_embd);
+            ps.resid = xb;
+            ps.rstride = hp.n_embd;
+            launch_part_sum(ps, stream);
             pend_k = 0;
             moe_ffn_short(l, nt);
             continue;
         }
         // FFN gate/up: parts of both, SwiGLU'd by the down input's quant_act
         const ActQ8 act = ub_act(hp.n_embd, nt, L.gate.type);
-        launch_quant_act(xb, hp.n_embd, L.ffn_norm, hp.eps, act, stream, nullptr, ub_spart, pend_k);
+        launch_quant_act(qa_norm(xb, hp.n_embd, L.ffn_norm, {ub_spart, pend_k}), act, stream);   // (W_o's parts)
         const int kg = mmqs_one(L.gate, true, hp.n_ff, act, 2 * hp.n_ff);
         const ActQ8 a2 = ub_act(hp.n_ff, nt, L.down.type);
-        launch_quant_act(nullptr, hp.n_ff, nullptr, hp.eps, a2, stream, nullptr, ub_spart, kg, 1);
+        launch_quant_act(qa_swiglu(ub_spart, kg, hp.n_ff), a2, stream);
         pend_k = mmqs_one(L.down, false, 0, a2, hp.n_embd);
     }
     return pend_k;

@@ -254,7 +254,7 @@ Ctx::Ctx(Model* model, uint32_t nctx, uint32_t nbatch, uint32_t nubatch) : m(mod
             ub_rope = mem.dev<float2>((size_t)UB_MAX * std::max(1, hp.n_rot / 2));
             // split-K partials of the residual GEMMs (WO, FFN down) of dense models
             // (GPT-2: no split-K, no short-batch form -- every batch on the tiled GEMM)
-            if (mmq2_active() && !gpt2) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
+            if (!gpt2) ub_part = mem.dev<float>((size_t)2 * UB_MAX * hp.n_embd);
             mmqs_max = gpt2 ? 0 : mmqs_token_limit();
             // MoE: short batches when every expert matrix has the grouped form (k-quants)
             moe_short = hp.n_expert > 0;

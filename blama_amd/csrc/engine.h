@@ -528,6 +528,19 @@ struct Ctx {
         int fmt, n, cnt[3], idx[3][3];
     };
     static QkvGroups qkv_type_groups(const Layer& L);
+    // What launch_quant_act quantises for the next GEMM (rows of K elements; the caller adds `rows`
+    // for the MoE rows of a batch, each reading the row rows[t] names):
+    struct PendParts {         // split-K parts not yet added into x: nks of them, then the addend row (may be null)
+        const float* part;
+        int nks;
+        const float* addend;
+    };
+    QuantAct qa_rows(const float* x, int K) const;                                  // the rows as they are
+    // rms_norm(x) * norm_w -- norm_b set (GPT-2): layer_norm(x) * norm_w + norm_b -- of x, or of x plus
+    // the pending parts (pend.part set), x written back
+    QuantAct qa_norm(const float* x, int K, const float* norm_w, PendParts pend = {}) const;
+    QuantAct qa_layernorm(const float* x, int K, const float* norm_w, const float* norm_b) const;
+    QuantAct qa_swiglu(const float* part, int nks, int K) const;                    // silu(gate) * up of a pair launch's parts
     // one matrix (or gate/up pair) on mmqs, its rows from 0 of the parts; returns the part count
     int mmqs_one(const QMat& A, bool pair, int nff, const ActQ8& act, int pstride);
     // MoE: router and grouping of nt tokens (pend: W_o's split-K parts, added first); returns the

@@ -96,7 +96,7 @@ struct AttnPartials {
 
 // Q8_K / Q8_0 activations of a physical batch (launch_quant_act; layout below)
 struct ActQ8 {
-    int8_t* q;                 // [npad/32][K/256][8][64][16]: MFMA A fragments (mmq.hip quant_act_kernel)
+    int8_t* q;                 // [npad/32][K/256][8][64][16]: MFMA A fragments (quant_act.hip quant_act_kernel)
     float* dT;                 // [K/256][npad]  (Q8_K d, token-minor)
     int8_t* bsb;               // [npad/32][K/256][32][16]: sub-block bsums as 64*hi + lo (bytes 0-7 hi, 8-15 lo)
     int K;
@@ -161,7 +161,11 @@ void launch_gemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start = nullp
 bool gemv_pair_supported(int t1, int t2);
 // workgroups of a launch
 int gemv_grid(const GemvParams& p);
-void init_gemm_attributes();     // the batch GEMMs' LDS limits (kernels.hip)
+void init_gemm_attributes();     // the batch GEMMs' and batch attention's LDS limits, and the device's CU count
+                                 // for mmq_plan: kernels.hip, walking these per-file tables
+void init_mmq2_attributes();     // mmq.hip
+void init_mmqs_attributes();     // mmqs.hip
+void init_attn_mfma_attributes();   // attn_mfma.hip
 
 // ---- decode GEMV over unquantised F16 matrices [rows][K] (fgemv.hip) ----
 // y[r] = sum_k f16(x[k]) * W[r][k]: the f32 activation rounded to f16 once (RNE), exact f32
@@ -428,23 +432,65 @@ void launch_attn_multi(const AttnParams& p, int ntok, float* out, hipStream_t s)
 bool attn_mfma_supported(int head_dim);
 void launch_attn_mfma(const AttnParams& p, int ntok, float* out, hipStream_t s);
 
-// ---- int8-MFMA GEMM over a physical batch of up to UB_MAX tokens (mmq.hip) ----
+// ---- int8-MFMA GEMM over a physical batch of up to UB_MAX tokens (mmq.hip, mmqs.hip) ----
 // Prompt ingestion and batched verification: activations quantised to Q8_K once per matrix
-// input (launch_quant_act), then v_mfma_i32_32x32x32_i8 per sub-block (launch_mmq32).
+// input (launch_quant_act, quant_act.hip), then v_mfma_i32_32x32x32_i8 per sub-block.  The
+// launch_mmq32* / mmq32_* names are for that 32x32x32 MFMA; the kernel behind them is the tiled
+// mmq2_t (mmq.hip), the short batches' are mmqs_t / mmqs1_t / mmqs1_lean_t (mmqs.hip).
 constexpr int UB_MAX = 512;    // n_ubatch (reference Instance.hpp:24)
-// rows (optional): token t of the batch reads row rows[t] of x (the tokens routed to one expert)
-// part (optional): the split-K partial sums of the GEMM that produced x (see GemmParams::ksplit):
-// x = ((p0 + p1) + ...) + x first, written back; addend (optional, with part): [K] added to every
-// row after that, x = (((p0 + p1) + ...) + x) + addend
-// swiglu: part holds the gate/up parts of a pair launch ([nks][ntok][2 K]: gate rows, then up
-// rows); the row quantised is silu(sum gate) * (sum up) (x unused)
-// norm_b (with norm_w; GPT-2): the row quantised is layer_norm(x) * norm_w + norm_b -- ggml_norm as
-// gemv.hip's PRO_LAYERNORM prologue computes it -- instead of rms_norm(x) * norm_w
-void launch_quant_act(const float* x, int x_stride, const float* norm_w, float eps, const ActQ8& a, hipStream_t s,
-                      const int* rows = nullptr, const float* part = nullptr, int nks = 2, int swiglu = 0,
-                      const float* addend = nullptr, const float* norm_b = nullptr);
-// whether prompt-batch GEMMs take the mmq2 path (the only one with ksplit)
-bool mmq2_active();
+// The rows of a physical batch to quantise into an ActQ8 (its K, ntok and npad are the ActQ8's).
+struct QuantAct {
+    const float* x;        // [..][x_stride] f32 rows (unused with swiglu)
+    int x_stride;
+    const float* norm_w;   // optional: the row quantised is rms_norm(x) * norm_w
+    const float* norm_b;   // optional, with norm_w (GPT-2): layer_norm(x) * norm_w + norm_b instead -- ggml_norm
+                           // as gemv.hip's PRO_LAYERNORM prologue computes it
+    float eps;
+    const int* rows;       // optional: token t reads row rows[t] of x (the MoE rows of a batch; < 0: a padding row)
+    const float* part;     // optional: the split-K partial sums of the GEMM that produced x (GemmParams::ksplit,
+                           // launch_mmqs): x = ((p0 + p1) + ...) + x first, written back
+    int nks;               // the parts in `part` (read only when part is set)
+    int swiglu;            // 1: part holds the gate/up parts of a pair launch ([nks][ntok][2 K]: gate rows, then
+                           // up rows); the row quantised is silu(sum gate) * (sum up)
+    const float* addend;   // optional, with part: [K] added to every row after the parts,
+                           // x = (((p0 + p1) + ...) + x) + addend
+};
+void launch_quant_act(const QuantAct& q, const ActQ8& a, hipStream_t s);
+
+// Where a batch GEMM launch is chosen: mmq_plan is a pure function of the launch's shape (no
+// device, no pointers; the CU count is an argument; mi_op_mmq_plan shows it to the tests).
+// mmq2_fn / mmqs_fn (mmq.hip / mmqs.hip) are the tables from a plan to the instantiated kernel,
+// and init_gemm_attributes walks them once per device.
+enum MmqForm { MMQ_TILED = 0, MMQ_SHORT = 1 };
+enum MmqKernel { MK_NONE, MK_TILED, MK_SHORT, MK_SHORT1, MK_SHORT1_LEAN };
+struct MmqShape {
+    int type;                  // the matrices' quant type
+    bool pair;                 // a gate/up pair copy
+    int rows[3], nseg;         // rows of each matrix (segment)
+    int npad;                  // the activation's padded tokens
+    int K;
+    int grp_n, grp_max;        // grouped (MoE; grp_n > 0): experts, the most rows one expert can have
+    int ksplit;                // tiled: GemmParams::ksplit
+    bool pre, gx;              // tiled: GemmParams::pre is set; a bias or a GELU epilogue is present
+};
+struct MmqPlan {
+    MmqKernel kernel;          // MK_NONE: no kernel serves the shape (why: the launcher's message)
+    const char* why;
+    int T;                     // the operand type: the kernels' template type (Q4_0 / Q5_0 run as Q8_0)
+    bool pair, pre, gx, grouped;
+    int nst;                   // tiled: LDS stages (1: two workgroups per CU, 2: one)
+    int nt;                    // short: 32-token tiles
+    int nrb, ntb;              // tiled: row blocks, token blocks
+    int kp;                    // short: K-parts
+    int grid_x, grid_y, grid_z, block;
+    size_t lds;                // dynamic LDS bytes
+};
+MmqPlan mmq_plan(MmqForm form, const MmqShape& s, int n_cu);   // n_cu: the tiled form's stage choice
+inline MmqPlan mmq_no_plan(const char* why) {
+    MmqPlan k{};
+    k.why = why;
+    return k;
+}
 // ggml_rope_cache_init per token of the batch: out [ntok][n_rot/2] (cos, sin)
 void launch_rope_table(const int* tokpos, int ntok, int n_rot, float theta_scale, float freq_scale,
                        const float* freq_factors, float2* out, hipStream_t s);
@@ -468,7 +514,7 @@ void launch_mmq32_multi(const GemmParams* ps, int n, const ActQ8& act, const flo
 void launch_mmq32_rows(const GemmParams& p, const int* row0, const int* nrows, const int* epi, int n, const ActQ8& act,
                        const float2* rope, hipStream_t s);
 
-// ---- short batches (<= MMQS_MAX tokens, mmq.hip mmqs): a split-K streaming int8-MFMA GEMM ----
+// ---- short batches (<= MMQS_MAX tokens, mmqs.hip): a split-K streaming int8-MFMA GEMM ----
 // The matrices (one type; a gate/up pair: one QMat, its pair copy) over act (npad 32 or 64) write
 // the plain partial sums of their K-parts to part[kp][ntok][pstride], matrix i's rows from prow[i]
 // (a pair: gate rows from prow[0], up rows from prow[0] + nff).  Returns kp (mmqs_parts(K)).  The
@@ -502,11 +548,18 @@ struct QkvFinish {
     int n_rot, head_dim;
 };
 void launch_qkv_finish(const QkvFinish& F, hipStream_t s);
-// out[t][r] = ((p0 + p1) + ...) [+ resid[t][r]] over rows [0, rows) of the parts; swiglu > 0 (a
-// pair launch's parts, up rows from swiglu): silu(sum gate) * (sum up); addend (optional, with
-// resid): [rows] added to every token's row after the residual
-void launch_part_sum(const float* part, int kp, int ntok, int rows, int pstride, const float* resid, int rstride,
-                     float* out, int ostride, hipStream_t s, int swiglu = 0, const float* addend = nullptr);
+// out[t][r] = ((p0 + p1) + ...) [+ resid[t][r]] over rows [0, rows) of the parts
+struct PartSum {
+    const float* part;     // [kp][ntok][pstride]
+    int kp, ntok, rows, pstride;
+    const float* resid;    // optional: [ntok][rstride], added after the parts (may alias out)
+    int rstride;
+    float* out;            // [ntok][ostride]
+    int ostride;
+    int swiglu;            // > 0 (a pair launch's parts, up rows from swiglu): silu(sum gate) * (sum up)
+    const float* addend;   // optional, with resid: [rows] added to every token's row after the residual
+};
+void launch_part_sum(const PartSum& p, hipStream_t s);
 
 // ---- LoRA adapters (lora.hip): llama-graph.cpp build_lora_mm, b5187 ----
 // The adapters set on a context are stacked into one matrix pair of concatenated rank per base

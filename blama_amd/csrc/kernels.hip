@@ -252,6 +252,10 @@ void init_gemm_attributes() {
         for (bool pre : {false, true})
             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t, pre)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    // the int8-MFMA batch GEMMs and the batch attention, each from its own table
+    init_mmq2_attributes();
+    init_mmqs_attributes();
+    init_attn_mfma_attributes();
 }
 static GemmFn gemm_fn(int type, bool pre) {
     switch (type) {

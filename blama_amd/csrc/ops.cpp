@@ -447,6 +447,35 @@ int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t
     MI_TRY(-1)
 }
 
+// mmq_plan for one shape: out[16] = {kernel, T, pair, pre, gx, grouped, nst, nt, nrb, ntb, kp, grid_x, grid_y,
+// grid_z, block, lds}.  form: 0 tiled, 1 short.  Opens no device.
+int32_t mi_op_mmq_plan(int32_t form, int32_t type, int32_t pair, const int32_t* rows, int32_t nseg, int32_t npad, int32_t K,
+                       int32_t grp_n, int32_t grp_max, int32_t ksplit, int32_t pre, int32_t gx, int32_t n_cu, int32_t* out) {
+    try {
+        if (form != MMQ_TILED && form != MMQ_SHORT) throw Error("mmq_plan: form 0 (tiled) or 1 (short)");
+        if (nseg < 0 || nseg > 3) throw Error("mmq_plan: at most 3 segments");
+        MmqShape sh{};
+        sh.type = type;
+        sh.pair = pair != 0;
+        sh.nseg = nseg;
+        for (int i = 0; i < nseg; ++i) sh.rows[i] = rows[i];
+        sh.npad = npad;
+        sh.K = K;
+        sh.grp_n = grp_n;
+        sh.grp_max = grp_max;
+        sh.ksplit = ksplit;
+        sh.pre = pre != 0;
+        sh.gx = gx != 0;
+        const MmqPlan k = mmq_plan((MmqForm)form, sh, n_cu);
+        const int v[16] = {k.kernel, k.T, k.pair, k.pre, k.gx, k.grouped, k.nst, k.nt, k.nrb, k.ntb, k.kp,
+                           k.grid_x, k.grid_y, k.grid_z, k.block, (int)k.lds};
+        std::copy(v, v + 16, out);
+        if (k.kernel == MK_NONE) set_last_error(k.why);   // (mi_last_error: the message the launcher throws)
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
 // One decode step's attention through launch_attn in a given mode, with the output the engine's next
 // launch reads: the activation published in act_layout (ATTN_DECODE_QUANT: by the attention kernel;
 // ATTN_DECODE_SPLIT: by attn_combine_quant over the two launches' partials), unpacked.  Returns the
@@ -621,7 +650,10 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
         Dev<int> dtp((size_t)ntok * 4);
         dtp.fill(0);
         ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, takes_q80(type) ? 1 : 0};
-        launch_quant_act(dx.p, K, nullptr, 0.0f, act, nullptr);
+        QuantAct qa{};
+        qa.x = dx.p;
+        qa.x_stride = K;
+        launch_quant_act(qa, act, nullptr);
         // up to the short-batch limit: the short-batch GEMM (K-part sums, added by part_sum) as the
         // engine's verification batches take it; MI_MMQS_MAX=0: the tiled GEMM for every count
         if (ntok <= mmqs_token_limit()) {
@@ -630,7 +662,16 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
             const QMat* mats[1] = {&A};
             const int prow[1] = {0};
             const int kp = launch_mmqs(mats, prow, 1, pair, rows, act, part.p, pst, nullptr);
-            launch_part_sum(part.p, kp, ntok, rows, pst, nullptr, 0, dy.p, rows, nullptr, pair ? rows : 0);
+            PartSum ps{};
+            ps.part = part.p;
+            ps.kp = kp;
+            ps.ntok = ntok;
+            ps.rows = rows;
+            ps.pstride = pst;
+            ps.out = dy.p;
+            ps.ostride = rows;
+            ps.swiglu = pair ? rows : 0;
+            launch_part_sum(ps, nullptr);
             MI_HIP(hipDeviceSynchronize());
         } else {
             launch_mmq32(mmq32_params(A, pair ? &B : nullptr, ntok, dtp.p, dy.p, rows), act, nullptr, nullptr);
@@ -668,8 +709,13 @@ int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t r
         const std::vector<unsigned short> tab = gelu_table_host();
         Dev<unsigned short> dtab(tab.size(), tab.data());
         ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, q80 ? 1 : 0};
-        launch_quant_act(dx.p, K, norm_w ? dnw.p : nullptr, eps, act, nullptr, nullptr, nullptr, 2, 0, nullptr,
-                         norm_b ? dnb.p : nullptr);
+        QuantAct qa{};
+        qa.x = dx.p;
+        qa.x_stride = K;
+        qa.norm_w = norm_w ? dnw.p : nullptr;
+        qa.norm_b = norm_b ? dnb.p : nullptr;
+        qa.eps = eps;
+        launch_quant_act(qa, act, nullptr);
         GemmParams p = mmq32_params(A, nullptr, ntok, dtp.p, dy.p, rows);
         const int epis[3] = {EPI_STORE, EPI_ADD, EPI_GELU};
         p.epi = epis[epilogue];
@@ -712,6 +758,7 @@ int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv,
             if (t && tok_cell[t] <= tok_cell[t - 1]) throw Error("attention_batch: token cells must ascend");
         }
         MI_HIP(hipSetDevice(device));
+        ensure_kernel_attributes(device);
         const int kv_dim = n_head_kv * head_dim, d = n_head * head_dim;
         const size_t kvn = (size_t)n_cells * kv_dim;
         std::vector<int> tp((size_t)ntok * 4, 0);
@@ -819,7 +866,11 @@ int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* r
         Dev<float> ddT((size_t)cap * (K / 32)), dy((size_t)cap * rows);
         Dev<int8_t> dq((size_t)cap * K), dbs((size_t)cap * (K / 256) * 16);
         ActQ8 act{dq.p, ddT.p, dbs.p, K, cap, cap, type == T_Q8_0 ? 1 : 0};
-        launch_quant_act(dx.p, K, nullptr, 0.0f, act, nullptr, per_pick ? drs.p : drows.p);
+        QuantAct qa{};
+        qa.x = dx.p;
+        qa.x_stride = K;
+        qa.rows = per_pick ? drs.p : drows.p;
+        launch_quant_act(qa, act, nullptr);
         dy.fill(0);
         if (mode == 0) {   // the tiled grouped launch of a physical batch
             Dev<int> dtp((size_t)cap * 4);
@@ -831,7 +882,16 @@ int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* r
             Dev<float> part((size_t)mmqs_parts(K) * cap * pst);
             part.fill(0);
             const int kp = launch_mmqs_grouped(A, pair, pair ? rows : 0, act, part.p, pst, dgrp.p, n_expert, ntok, nullptr);
-            launch_part_sum(part.p, kp, cap, rows, pst, nullptr, 0, dy.p, rows, nullptr, pair ? rows : 0);
+            PartSum ps{};
+            ps.part = part.p;
+            ps.kp = kp;
+            ps.ntok = cap;
+            ps.rows = rows;
+            ps.pstride = pst;
+            ps.out = dy.p;
+            ps.ostride = rows;
+            ps.swiglu = pair ? rows : 0;
+            launch_part_sum(ps, nullptr);
             MI_HIP(hipDeviceSynchronize());
         }
         std::vector<float> hy((size_t)cap * rows);

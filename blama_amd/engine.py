@@ -120,6 +120,7 @@ _SIGS = {
     "mi_op_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                     C.c_int32, _P]),
     "mi_op_attn_plan": (C.c_int32, [C.c_int32] * 7 + [_P]),
+    "mi_op_mmq_plan": (C.c_int32, [C.c_int32] * 3 + [_P] + [C.c_int32] * 9 + [_P]),
     "mi_op_attention_decode": (C.c_int32, [C.c_int32] * 8 + [_P, _P, _P, _P, C.c_int32, C.c_int32] + [_P] * 6),
     "mi_op_attention_short": (C.c_int32, [C.c_int32] * 6 + [_P] * 6 + [C.c_int32] + [_P] * 4),
     "mi_op_gemv_bench": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
@@ -588,6 +589,27 @@ def op_attn_plan(mode: int, n_head: int, n_head_kv: int, hd: int, n_ctx: int = 5
     out = np.zeros(len(ATTN_PLAN_FIELDS), np.int32)
     _check(lib().mi_op_attn_plan(mode, n_head, n_head_kv, hd, n_ctx, ntok, int(long_ok), _ptr(out)), "op_attn_plan")
     return dict(zip(ATTN_PLAN_FIELDS, (int(v) for v in out)))
+
+
+MMQ_PLAN_FIELDS = ("kernel", "T", "pair", "pre", "gx", "grouped", "nst", "nt", "nrb", "ntb", "kp", "grid_x", "grid_y",
+                   "grid_z", "block", "lds")
+MMQ_TILED, MMQ_SHORT = 0, 1                                                    # MmqForm
+MK_NONE, MK_TILED, MK_SHORT, MK_SHORT1, MK_SHORT1_LEAN = range(5)              # MmqKernel
+
+
+def op_mmq_plan(form: int, type_: int, rows, npad: int, K: int, pair: bool = False, grp_n: int = 0, grp_max: int = 0,
+                ksplit: int = 0, pre: bool = False, gx: bool = False, n_cu: int = 256) -> dict:
+    """mi_op_mmq_plan: the kernel, template arguments and launch shape a batch GEMM launch of this
+    shape would use, by MMQ_PLAN_FIELDS (needs no GPU).  rows: the rows of each matrix of the launch.
+    A shape no kernel serves has kernel MK_NONE and, under "why", the launcher's message."""
+    r = np.asarray(list(rows), np.int32)
+    out = np.zeros(len(MMQ_PLAN_FIELDS), np.int32)
+    _check(lib().mi_op_mmq_plan(form, type_, int(pair), _ptr(r), len(r), npad, K, grp_n, grp_max, ksplit, int(pre), int(gx),
+                                n_cu, _ptr(out)), "op_mmq_plan")
+    plan = dict(zip(MMQ_PLAN_FIELDS, (int(v) for v in out)))
+    if plan["kernel"] == MK_NONE:
+        plan["why"] = last_error()
+    return plan
 
 
 ATTN_DECODE_QUANT, ATTN_DECODE_FUSED, ATTN_DECODE_SPLIT, ATTN_BATCH_QUANT, ATTN_BATCH_FUSED = range(5)   # AttnMode

@@ -309,6 +309,18 @@ int32_t mi_op_attention(int32_t device, int32_t n_head, int32_t n_head_kv, int32
  * 3 long, 4 scores + pv), R, LPC, HG, NWV, grid_x, grid_y, block, dynamic LDS bytes, qsplit. */
 int32_t mi_op_attn_plan(int32_t mode, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_ctx,
                         int32_t ntok, int32_t long_ok, int32_t* out);
+/* Which int8-MFMA batch GEMM kernel a launch of this shape would run (no device is touched).
+ * form: 0 the tiled GEMM of a physical batch, 1 the short streaming GEMM (npad 32 or 64; grouped: the
+ * padded MoE rows).  type: the matrices' quant type; pair: a gate/up pair; rows[nseg]: the rows of
+ * each matrix of the launch; grp_n > 0: a grouped (MoE) launch over grp_n experts of at most grp_max
+ * rows each; ksplit, pre, gx (tiled): split-K parts, a pre-epilogue term, a bias or GELU epilogue;
+ * n_cu (tiled): the device's compute units.  out[16]: kernel (0 none, 1 tiled, 2 short, 3 short
+ * one-wave, 4 short one-wave lean), operand type, pair, pre, gx, grouped, stages (tiled), token
+ * tiles (short), row blocks (short: row tiles), token blocks, K-parts (short), grid_x, grid_y,
+ * grid_z, block, dynamic LDS bytes.  With kernel 0, mi_last_error() holds the launcher's message. */
+int32_t mi_op_mmq_plan(int32_t form, int32_t type, int32_t pair, const int32_t* rows, int32_t nseg, int32_t npad,
+                       int32_t K, int32_t grp_n, int32_t grp_max, int32_t ksplit, int32_t pre, int32_t gx, int32_t n_cu,
+                       int32_t* out);
 /* One decode step's attention as the engine launches it in `mode` (mi_op_attn_plan's 0, 1 or 2),
  * with the activation it publishes for the W_o launch.  The cache holds n_ctx rows
  * [n_ctx][n_head_kv*head_dim], of which cells 0 .. cell are the context (rows past `cell` are never
