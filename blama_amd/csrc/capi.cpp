@@ -676,5 +676,13 @@ int32_t mi_debug_stamps(mi_ctx* c, uint64_t* out, int32_t n_launch) {
     }
     MI_TRY(-1)
 }
+int32_t mi_debug_down_quant(mi_ctx* c, int32_t form) {
+    try {
+        if (!c) throw Error("null argument");
+        c->impl->set_down_quant(form);
+        return 0;
+    }
+    MI_TRY(-1)
+}
 
 }  // extern "C"

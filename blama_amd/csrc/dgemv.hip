@@ -16,9 +16,14 @@
 //    the activation inside the producing launch by arrival tickets cost 6-10 us per launch; an
 //    rms-norm prologue in every QKV / gate/up workgroup (DV_QKVN / DV_SWIGLUN) 8-9 % slower for 7B
 //    and Llama-3-8B but 17 % faster for TinyLlama; the FFN down launch quantising h itself in
-//    every workgroup (DV_ADDQ) 1-1.5 % slower per 7B token but 4-5 % faster for TinyLlama -- so
-//    the step quantises in-launch for small models only (n_ff * n_embd <= 2^24; bit-identical to
-//    the dv_quant launches; profiles/r06_hq_ab.txt, r06_nq_ab.txt); an Infinity-Cache prefetch of the next layer's weights from a side stream slowed the
+//    every workgroup of 8 waves (DV_ADDQ) 2.5 % slower per 7B token and 7 % per Llama-3-8B token
+//    but 6 % faster for TinyLlama; in 16-wave workgroups of 16 rows (DV_ADDQW: half the workgroups
+//    quantise, each wave half the blocks) level with the dv_quant launch for 7B and Llama-3-8B
+//    (+0.4 % / +0.3 % at the median of 6 runs, inside the run-to-run spread) and 4 % slower than
+//    the 8-wave form for TinyLlama -- so small models (n_ff * n_embd <= 2^24) norm and quantise
+//    in-launch in 8-wave workgroups and the others quantise h in the 16-wave down launch (all
+//    bit-identical to the dv_quant launches; profiles/r06_hq_ab.txt, r06_nq_ab.txt,
+//    r07_hq16_ab.txt); an Infinity-Cache prefetch of the next layer's weights from a side stream slowed the
 //    chain 1.7-2.6x.
 //    Every sum is taken in a fixed order: results are bit-reproducible.
 #include "lora.h"
@@ -33,12 +38,19 @@ namespace mi {
 namespace {
 
 constexpr int DV_NW = 8;       // waves per workgroup
+constexpr int DV_NWW = 16;     // DV_ADDQW: waves per workgroup of the wide in-launch-quantising down launch
 constexpr int DV_ACT_LD = 5;   // 16-B activation loads per lane: act bytes <= 5 x 8 KiB
+constexpr size_t DV_ACT_MAX = (size_t)DV_ACT_LD * DV_NW * 64 * 16;   // the activation in LDS, whatever the wave count
 
 // DV_ADDQ: DV_ADD whose workgroups quantise the fp32 activation (hraw, no norm) into LDS themselves;
-// DV_QKVN / DV_SWIGLUN: DV_QKV / DV_SWIGLU whose workgroups build rms_norm(hraw) * norm_w so
-enum DvRole { DV_QKV = 0, DV_ADD = 1, DV_SWIGLU = 2, DV_STORE = 3, DV_ADDQ = 4, DV_QKVN = 5, DV_SWIGLUN = 6 };
-constexpr int dv_base(int r) { return r == DV_ADDQ ? DV_ADD : r == DV_QKVN ? DV_QKV : r == DV_SWIGLUN ? DV_SWIGLU : r; }
+// DV_ADDQW: DV_ADDQ in 16-wave workgroups (half as many workgroups quantise, each wave half as
+// many blocks; the same Q8 bytes in LDS); DV_QKVN / DV_SWIGLUN: DV_QKV / DV_SWIGLU whose
+// workgroups build rms_norm(hraw) * norm_w so
+enum DvRole { DV_QKV = 0, DV_ADD = 1, DV_SWIGLU = 2, DV_STORE = 3, DV_ADDQ = 4, DV_QKVN = 5, DV_SWIGLUN = 6, DV_ADDQW = 7 };
+constexpr int dv_base(int r) {
+    return r == DV_ADDQ || r == DV_ADDQW ? DV_ADD : r == DV_QKVN ? DV_QKV : r == DV_SWIGLUN ? DV_SWIGLU : r;
+}
+constexpr int dv_nw(int r) { return r == DV_ADDQW ? DV_NWW : DV_NW; }   // waves per workgroup of a role
 
 
 struct DvSeg {
@@ -81,6 +93,7 @@ __device__ __forceinline__ void dv_lds_barrier() {
 template <int T, int SI, int RW, int C, int ROLE0, bool LORA>
 __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     constexpr int ROLE = dv_base(ROLE0);
+    constexpr int NW = dv_nw(ROLE0);
     using K = Kq<T>;
     const DvSeg& S = a.seg[SI];
     const int tid = threadIdx.x;
@@ -89,20 +102,21 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     const int sbl = lane >> 3, j = lane & 7;
     const int nb = a.K >> 8;
     const int wg = (int)blockIdx.x - S.blk0;
-    const int u = wg * DV_NW + wave;
+    const int u = wg * NW + wave;
     const bool uv = u < S.units;
     const int uc = uv ? u : S.units - 1;
     constexpr bool ADD = ROLE == DV_ADD;
-    constexpr bool RAWQ = ROLE0 == DV_ADDQ;
+    constexpr bool RAWQ = ROLE0 == DV_ADDQ || ROLE0 == DV_ADDQW;
+    constexpr int NH = (8 * C + NW - 1) / NW;   // RAWQ: blocks a wave quantises (8 waves: C; 16: ceil(C / 2))
     constexpr bool NORMQ = ROLE0 == DV_QKVN || ROLE0 == DV_SWIGLUN;
     constexpr int NP = NORMQ ? 2 * C : 1;   // NORMQ: pieces tid + 256 k of waves 0-3 (dv_quant_kernel's)
     const int n4 = a.K >> 2;
-    constexpr int NLD = DV_ACT_LD;
+    constexpr int NLD = (DV_ACT_LD * DV_NW + NW - 1) / NW;   // (8 waves: DV_ACT_LD)
     const ActLayout L = act_layout(a.K, a.q8k, a.q80);
     // ---- 1. the activation and the epilogue's inputs, requested before any weight (loads retire
     // in order: the compiler's wait for them is then a count that leaves the weights in flight)
     u32x4 av[RAWQ || NORMQ ? 1 : NLD];
-    f32x4 hv[RAWQ ? C : 1];   // DV_ADDQ: blocks wave, wave + 8, .. (nb <= 8 C), 4 floats per lane
+    f32x4 hv[RAWQ ? NH : 1];   // DV_ADDQ / _ADDQW: blocks wave, wave + NW, .. (nb <= 8 C), 4 floats per lane
     f32x4 xv[NP], nv[NP];
     if constexpr (NORMQ) {
         if (wave < 4) {
@@ -118,14 +132,14 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     } else if constexpr (RAWQ) {
         const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.hraw), 0, a.K * 4, 0x00020000);
 #pragma unroll
-        for (int k = 0; k < C; ++k) {
-            const int b = wave + DV_NW * k;
+        for (int k = 0; k < NH; ++k) {
+            const int b = wave + NW * k;
             hv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hr, oob((b * 64 + lane) * 16, b >= nb), 0, 0));
         }
     } else {
         const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.act), 0, a.act_bytes, 0x00020000);
 #pragma unroll
-        for (int k = 0; k < NLD; ++k) av[k] = __builtin_amdgcn_raw_buffer_load_b128(ar, (k * DV_NW * 64 + tid) * 16, 0, 0);
+        for (int k = 0; k < NLD; ++k) av[k] = __builtin_amdgcn_raw_buffer_load_b128(ar, (k * NW * 64 + tid) * 16, 0, 0);
     }
     i32x4 tp = {0, 0, 0, 0};
     if (ROLE == DV_QKV) tp = *gptr(reinterpret_cast<const i32x4*>(a.tokpos));
@@ -200,8 +214,8 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     } else if constexpr (RAWQ) {   // dv_quant_kernel's arithmetic without the norm, block by block into LDS
         const ActOut t{a.K, a.q8k, a.q80, lds, nullptr, 0.0f};
 #pragma unroll
-        for (int k = 0; k < C; ++k) {
-            const int b = wave + DV_NW * k;
+        for (int k = 0; k < NH; ++k) {
+            const int b = wave + NW * k;
             if (b < nb) {
                 const float q[4] = {hv[k].x, hv[k].y, hv[k].z, hv[k].w};
                 dv_quant_block(t, b, q, lane);
@@ -210,7 +224,7 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
     } else {
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
-            const int o = (k * DV_NW * 64 + tid) * 16;
+            const int o = (k * NW * 64 + tid) * 16;
             if (o < a.act_bytes) *reinterpret_cast<u32x4*>(lds + o) = av[k];
         }
     }
@@ -291,7 +305,7 @@ __device__ __forceinline__ void dv_body(const DvArgs& a, char* lds) {
 
 // T1: -1 one segment, else the type of segment 1 (a mixed-type Q/K/V launch)
 template <int T0, int T1, int RW, int C, int ROLE, bool LORA>
-__global__ __launch_bounds__(DV_NW * 64) void dgemv_kernel(const DvArgs a) {
+__global__ __launch_bounds__(dv_nw(ROLE) * 64) void dgemv_kernel(const DvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     if (T1 < 0 || (int)blockIdx.x < a.seg[1].blk0) dv_body<T0, 0, RW, C, ROLE, LORA>(a, lds);
     else dv_body<(T1 < 0 ? T0 : T1), 1, RW, C, ROLE, LORA>(a, lds);
@@ -352,6 +366,7 @@ DvFn dv_fn_l(int role, int t0, int t1, int c) {
     case DV_QKV: return dv_fn_role<DV_QKV, LORA>(t0, t1, c);
     case DV_ADD: return dv_fn_role<DV_ADD, LORA>(t0, t1, c);
     case DV_ADDQ: return dv_fn_role<DV_ADDQ, LORA>(t0, t1, c);
+    case DV_ADDQW: return dv_fn_role<DV_ADDQW, LORA>(t0, t1, c);
     case DV_QKVN: return c <= 4 ? dv_fn_role<DV_QKVN, LORA>(t0, t1, c) : nullptr;
     case DV_SWIGLUN: return c <= 4 ? dv_fn_role<DV_SWIGLUN, LORA>(t0, t1, c) : nullptr;
     case DV_SWIGLU: return dv_fn_role<DV_SWIGLU, LORA>(t0, t1, c);
@@ -443,14 +458,15 @@ int dv_role(const GemvParams& p) {
     // Q/K/V and SwiGLU with rms_norm * norm_w, quantised in every workgroup)
     const bool raw = !p.act_in && p.x[0];
     if (raw && (g.epi == EPI_ADD) == (p.norm_w != nullptr)) return -1;
-    return g.epi == EPI_QKV ? (raw ? DV_QKVN : DV_QKV) : g.epi == EPI_ADD ? (raw ? DV_ADDQ : DV_ADD)
+    if (p.act_wide && !(raw && g.epi == EPI_ADD)) return -1;   // (only the in-launch-quantising add has a wide form)
+    return g.epi == EPI_QKV ? (raw ? DV_QKVN : DV_QKV) : g.epi == EPI_ADD ? (raw ? (p.act_wide ? DV_ADDQW : DV_ADDQ) : DV_ADD)
          : g.epi == EPI_SWIGLU ? (raw ? DV_SWIGLUN : DV_SWIGLU) : g.epi == EPI_STORE && !raw ? DV_STORE : -1;
 }
 }  // namespace
 
 bool dgemv_supported(const GemvParams& p) {
     if (p.nseg < 1 || p.nseg > 2 || p.K % 256 || (!p.act_q8k && !p.act_q80) ||
-        dv_act_bytes(p.K, p.act_q8k, p.act_q80) > (size_t)DV_ACT_LD * DV_NW * 64 * 16)
+        dv_act_bytes(p.K, p.act_q8k, p.act_q80) > DV_ACT_MAX)
         return false;
     const GemvSeg& g = p.seg[0];
     const int role = dv_role(p);
@@ -469,6 +485,7 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
     const int role0 = dv_role(p);
     const int role = dv_base(role0);
     const int rw = (role == DV_QKV || role == DV_SWIGLU) ? 2 : 1;
+    const int nw = dv_nw(role0);
     DvArgs a;
     std::memset(&a, 0, sizeof(a));
     int blk = 0;
@@ -489,7 +506,7 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
         o.nq = g.nq;
         o.nk = g.nk;
         o.blk0 = blk;
-        o.nblk = (o.units + DV_NW - 1) / DV_NW;
+        o.nblk = (o.units + nw - 1) / nw;
         blk += o.nblk;
         a.lora[i] = g.lora;
     }
@@ -516,15 +533,16 @@ void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEv
     a.eps = p.eps;
     const size_t actb = (dv_act_bytes(p.K, p.act_q8k, p.act_q80) + 15) / 16 * 16;
     a.red_off = (int)actb;
-    if (role0 == DV_ADDQ && p.K > DV_NW * 256 * dv_chunks(p.K)) throw Error("dgemv: activation too long to quantise in-launch");
+    // (a wave quantises blocks wave + nw k, k < ceil(8 C / nw): every block of a row of <= 8 C)
+    if (role == DV_ADD && role0 != DV_ADD && p.K > 8 * 256 * dv_chunks(p.K)) throw Error("dgemv: activation too long to quantise in-launch");
     if (role == DV_ADD && !g0.resid) throw Error("dgemv: residual epilogue without resid");
     if (role == DV_QKV && !p.tokpos) throw Error("dgemv: QKV epilogue needs tokpos");
     const DvFn fn = dv_fn(role0, g0.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K), a.lora[0] || a.lora[1]);
     const size_t smem = actb + (role0 == DV_QKVN || role0 == DV_SWIGLUN ? 4 * sizeof(double) : 0);
     if (ev_start || ev_stop)
-        hipExtLaunchKernelGGL(fn, dim3(blk), dim3(DV_NW * 64), smem, s, ev_start, ev_stop, 0, a);
+        hipExtLaunchKernelGGL(fn, dim3(blk), dim3(nw * 64), smem, s, ev_start, ev_stop, 0, a);
     else
-        hipLaunchKernelGGL(fn, dim3(blk), dim3(DV_NW * 64), smem, s, a);
+        hipLaunchKernelGGL(fn, dim3(blk), dim3(nw * 64), smem, s, a);
     MI_HIP(hipGetLastError());
 }
 

@@ -328,6 +328,21 @@ void Ctx::invalidate_graphs() {
     }
 }
 
+void Ctx::set_down_quant(int form) {
+    if (!sp_ok || m->hp.n_expert > 0) throw Error("down_quant: no streaming dense decode step in this context");
+    if (form < HQ_LAUNCH || form > HQ_WG16) throw Error("down_quant: form");
+    MI_HIP(hipSetDevice(device));
+    sync();
+    std::vector<SpLayer> old = sp;
+    for (SpLayer& b : sp) b.hq = form;
+    for (int l = 0; l < m->hp.n_layer; ++l)
+        if (!dgemv_supported(down_params_sp(l))) {
+            sp = std::move(old);
+            throw Error("down_quant: no compiled variant for this form");
+        }
+    invalidate_graphs();    // the next step re-captures with the other launches
+}
+
 void Ctx::apply_cvec(const float* data, size_t len, int n_embd, int il_start, int il_end) {
     const HParams& hp = m->hp;
     if (enc) throw Error("apply_cvec: encoder models take no control vector");
@@ -541,6 +556,14 @@ GemvParams Ctx::down_params(int l, ActSrc src) const {
     return p;
 }
 
+// the streaming step's FFN down launch: h quantised by a dv_quant launch, or by the launch's own
+// workgroups of 8 or 16 waves (sp[l].hq)
+GemvParams Ctx::down_params_sp(int l) const {
+    GemvParams p = down_params(l, sp[l].hq == HQ_LAUNCH ? ACT_QUANT : ACT_RAW);
+    p.act_wide = sp[l].hq == HQ_WG16;
+    return p;
+}
+
 // final norm + output head of one residual row
 GemvParams Ctx::head_params(ActSrc src, const float* xrow) const {
     GemvParams p = gemv_base();
@@ -609,16 +632,23 @@ bool Ctx::sp_setup() {
         for (int f : {b.fA, b.fB, b.fC}) act_n = std::max(act_n, dv_act_bytes(hp.n_embd, f & 1, f >> 1));
         act_f = std::max(act_f, dv_act_bytes(hp.n_ff, b.fD & 1, b.fD >> 1));
     }
-    // The FFN down launch quantises h in every workgroup itself (no dv_quant launch before it) when
-    // that redundant work -- n_ff elements in each of n_embd / 8 workgroups -- is small: one launch
-    // fewer per layer wins for TinyLlama (1398-1409 vs 1341-1342 tok/s), loses 1 % for 7B
-    // (profiles/r06_hq_ab.txt).
-    sp_hq_down = (long long)hp.n_ff * hp.n_embd <= (1LL << 24);
+    // The FFN down launch quantises h in every workgroup itself (no dv_quant launch before it): one
+    // launch fewer per layer.  Which workgroup shape does it is by measurement, decode tok/s on one
+    // box, dv_quant launch / 8-wave / 16-wave workgroups (profiles/r07_hq16_ab.txt):
+    //   tiny-q4_k_m       7397-7420 / 7651-7715 / 7263-7677
+    //   TinyLlama Q8_0    1540-1552 / 1644-1649 / 1572-1575
+    //   7B Q4_K_M          651-653  /  635-636  /  649-653;  6 runs each: 625.3-626.7 / - / 626.8-629.8
+    //   Llama-3-8B Q6_K    512-513  /  477-478  /  515-516;  6 runs each: 490.6-499.9 / - / 490.1-503.2
+    // Small models (the redundant work, n_ff elements in each of n_embd / 8 workgroups, is small) keep
+    // the 8-wave form; the others take the 16-wave one, which halves that work: no slower than the
+    // launch, +0.4 % at the median for 7B -- inside the run-to-run spread.
+    const bool small = (long long)hp.n_ff * hp.n_embd <= (1LL << 24);
+    for (int l = 0; l < nl; ++l) sp[l].hq = small ? HQ_WG8 : HQ_WG16;
     // The same rule for the normed inputs of Q/K/V and gate/up (dense models): their workgroups
     // build rms_norm(x) * norm_w and quantise it themselves, bit-identical to dv_quant_kernel. That
     // removes two more launches per layer: TinyLlama 1407-1412 -> 1639-1653 tok/s, but 7B 637-643 ->
     // 579-589 and Llama-3-8B 511 -> 470-480 (profiles/r06_nq_ab.txt).
-    sp_nq_in = sp_hq_down && !moe && hp.n_embd <= 8192;
+    sp_nq_in = small && !moe && hp.n_embd <= 8192;
     act_n = (act_n + 255) / 256 * 256;
     act_f = (act_f + 255) / 256 * 256;
     sp_mem = mem.dev<char>(4 * act_n + act_f, true);
@@ -627,6 +657,9 @@ bool Ctx::sp_setup() {
     sp_act[2] = sp_mem + 2 * act_n;
     sp_act[4] = sp_mem + 3 * act_n;
     sp_act[3] = sp_mem + 4 * act_n;
+    if (!moe)   // (a down matrix without a 16-wave variant keeps the dv_quant launch)
+        for (int l = 0; l < nl; ++l)
+            if (sp[l].hq == HQ_WG16 && !dgemv_supported(down_params_sp(l))) sp[l].hq = HQ_LAUNCH;
     // every launch must have a variant: the parameter blocks enqueue_step_sp will launch, dry
     const ActSrc in = sp_nq_in ? ACT_RAW : ACT_QUANT;
     bool ok = dgemv_supported(head_params(ACT_QUANT, nullptr));
@@ -638,7 +671,7 @@ bool Ctx::sp_setup() {
         ok = ok && dgemv_supported(wo_params(l, ACT_QUANT));
         if (moe) continue;
         ok = ok && L.gate.type == L.up.type && dgemv_supported(gate_up_params(l, in)) &&
-             dgemv_supported(down_params(l, sp_hq_down ? ACT_RAW : ACT_QUANT));
+             dgemv_supported(down_params_sp(l));
     }
     if (!ok) {   // the r04 step serves this model
         mem.release(sp_mem);
@@ -652,7 +685,7 @@ bool Ctx::sp_setup() {
 // dv_quant(rms_norm(x) * attn_norm) -> QKV -> attention (its output also quantised; past ATTN_SHORT
 // cells the split attention + attn_combine_quant) -> WO + residual -> dv_quant(rms_norm
 // * ffn_norm) -> gate/up -> dv_quant(h) -> down + residual; small models quantise inside the
-// consuming launch instead (sp_nq_in, sp_hq_down).
+// consuming launch instead (sp_nq_in); who quantises h is chosen per layer (SpLayer::hq).
 void Ctx::enqueue_step_sp(bool with_logits) {
     const HParams& hp = m->hp;
     const bool moe = hp.n_expert > 0;
@@ -695,8 +728,8 @@ void Ctx::enqueue_step_sp(bool with_logits) {
             if (!sp_nq_in) quant(x, act_out(2, sp[l].fC, hp.n_embd, m->layers[l].ffn_norm));
             run_gemv(gate_up_params(l, in), l, true);
             if (ld) lora_shrink(*ld, h, hp.n_ff, hp.n_ff, 1, nullptr);
-            if (!sp_hq_down) quant(h, act_out(3, sp[l].fD, hp.n_ff, nullptr));
-            run_gemv(down_params(l, sp_hq_down ? ACT_RAW : ACT_QUANT));
+            if (sp[l].hq == HQ_LAUNCH) quant(h, act_out(3, sp[l].fD, hp.n_ff, nullptr));
+            run_gemv(down_params_sp(l));
         }
         quant_x_for(l + 1);
     }

@@ -446,18 +446,20 @@ struct Ctx {
     // compiled variant (MoE: the attention half; the experts keep gemv_kernel): a GEMV reads its
     // activation quantised from sp_act[role] -- WO's written by the attention kernel (past
     // ATTN_SHORT cells by attn_combine_quant), the others' by a dv_quant launch (rms_norm'd x, or
-    // h) -- or, in small models, quantises the fp32 row itself (sp_hq_down, sp_nq_in)
+    // h) -- or quantises the fp32 row itself (SpLayer::hq, sp_nq_in)
+    enum { HQ_LAUNCH = 0, HQ_WG8 = 1, HQ_WG16 = 2 };   // who quantises h for the FFN down launch
     struct SpLayer {
         int fA, fB, fC, fD;             // activation formats of QKV, WO, gate/up, down: bit 0 Q8_K, bit 1 Q8_0
+        int hq;                         // HQ_LAUNCH: a dv_quant launch; HQ_WG8 / HQ_WG16: every down workgroup of 8 / 16 waves
     };
     bool sp_ok = false;                 // false: the r04 step on gemv_kernel (GPT-2, geometries sp_setup rejects)
     std::vector<SpLayer> sp;
     int sp_fH = 0;                      // the output head's activation formats
-    bool sp_hq_down = false;            // FFN down quantises h in-launch (no dv_quant launch before it)
     bool sp_nq_in = false;              // Q/K/V and gate/up norm and quantise x in-launch
     char* sp_mem = nullptr;
     char* sp_act[5] = {};               // QKV, WO, gate/up, down, head inputs
     bool sp_setup();
+    void set_down_quant(int form);      // diagnostics: every layer's SpLayer::hq (the parity tests' A/B of the forms)
     void enqueue_step_sp(bool with_logits);
 
     // ---- unquantised F16 models (Model::f16): the decode step on fgemv.hip (engine.cpp), prompt
@@ -496,6 +498,7 @@ struct Ctx {
     GemvParams wo_params(int l, ActSrc src) const;
     GemvParams gate_up_params(int l, ActSrc src) const;
     GemvParams down_params(int l, ActSrc src) const;
+    GemvParams down_params_sp(int l) const;   // the streaming step's, by sp[l].hq
     GemvParams head_params(ActSrc src, const float* xrow) const;
     AttnParams attn_params(int l, bool quant_out) const;
     ActOut act_out(int role, int fmt, int K, const float* norm_w) const;

@@ -147,6 +147,9 @@ struct GemvParams {
     // arrives quantised, act_layout(K, act_q8k, act_q80) at act_in (pro / x / norm_w unused)
     const char* act_in;
     int act_q8k, act_q80;
+    // EPI_ADD given the fp32 row x[0] instead of act_in (the launch quantises it in every workgroup):
+    // 1 = 16-wave workgroups of 16 rows (half as many workgroups quantise), 0 = the 8-wave ones
+    int act_wide;
 };
 
 void init_kernel_attributes();   // once per device, before any graph capture

@@ -131,12 +131,14 @@ int32_t mi_op_gemv(int32_t device, int32_t type, const void* raw, int32_t rows, 
 // device by dv_quant_kernel (no norm), then dgemv_kernel.  role 0 (Q/K/V, no RoPE: every row a Q
 // row; a second matrix = a second segment of another type), 1 (residual add), 2 (SwiGLU of the pair
 // A = gate, B = up), 3 (store), 4 (residual add with x quantised inside the launch, by every
-// workgroup: the small models' FFN down).
+// workgroup: the small models' FFN down), 5 (role 4 in 16-wave workgroups of 16 rows: the large
+// models' FFN down).
 int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t type2,
                     const void* raw2, int32_t rows2, const float* x, const float* resid, float* y) {
     try {
-        if (role < 0 || role > 4) throw Error("op_dgemv: role");
-        const bool addq = role == 4;
+        if (role < 0 || role > 5) throw Error("op_dgemv: role");
+        const bool wide = role == 5;
+        const bool addq = role == 4 || wide;
         if (addq) role = 1;
         const bool two = raw2 && rows2 > 0;
         check_quant(type, K);
@@ -164,6 +166,7 @@ int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw,
         p.x[0] = addq ? dx.p : nullptr;
         p.act_q8k = fmt & 1;
         p.act_q80 = fmt >> 1;
+        p.act_wide = wide;
         p.tokpos = dtp.p;
         p.head_dim = 128;
         p.nseg = role == 0 && two ? 2 : 1;

@@ -113,6 +113,7 @@ _SIGS = {
                                       C.POINTER(C.c_int64)]),
     "mi_prof_bytes": (C.c_int64, [_P]),
     "mi_debug_stamps": (C.c_int32, [_P, _P, C.c_int32]),
+    "mi_debug_down_quant": (C.c_int32, [_P, C.c_int32]),
     "mi_op_gemv": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_dequant": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mi_op_quantize_q8_K": (C.c_int32, [C.c_int32, _P, C.c_int32, _P, _P, _P]),
@@ -449,6 +450,11 @@ class Context:
     def ffn_bytes(self) -> int:
         return lib().mi_prof_ffn_bytes(self.h)
 
+    def debug_down_quant(self, form: int):
+        """Who quantises h for the FFN down launch of the streaming decode step, every layer: 0 a
+        dv_quant launch, 1 the down workgroups of 8 waves, 2 those of 16 waves (same bits)."""
+        _check(lib().mi_debug_down_quant(self.h, form), "debug_down_quant")
+
     def decode_path(self) -> int:
         """1: decode steps within 512 cells run on the streaming GEMV (dgemv.hip); 0: gemv_kernel;
         2: an encoder context (bert)."""
@@ -494,7 +500,8 @@ def op_gemv(type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, devic
 def op_dgemv(role: int, type_: int, raw: np.ndarray, rows: int, K: int, x: np.ndarray, type2: int = -1,
              raw2=None, rows2: int = 0, resid=None, device: int = 0) -> np.ndarray:
     """mi_op_dgemv: the decode step's streaming GEMV launch of `role` (0 Q/K/V without RoPE, 1 residual
-    add, 2 SwiGLU pair, 3 store, 4 residual add with x quantised inside the launch)."""
+    add, 2 SwiGLU pair, 3 store, 4 residual add with x quantised inside the launch, 5 the same in
+    16-wave workgroups)."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out_rows = rows + (rows2 if role == 0 and raw2 is not None else 0)
     y = np.empty(out_rows, np.float32)

@@ -286,6 +286,11 @@ int32_t mi_batch_path(const mi_ctx* ctx);
  * out.  Returns the number of launches copied; 0 unless the library is the
  * diagnostic build (libmi_engine_stamps.so, compiled with -DMI_STAMPS). */
 int32_t mi_debug_stamps(mi_ctx* ctx, uint64_t* out, int32_t n_launch);
+/* Diagnostics: who quantises h for the FFN down launch of the streaming dense decode step, in every
+ * layer from the next step on: 0 a dv_quant launch before it, 1 every down workgroup of 8 waves,
+ * 2 every down workgroup of 16 waves and 16 rows.  The three compute the same bits; the context's
+ * own choice is by measured speed.  0 ok, < 0 error (no such step, or no kernel for the form). */
+int32_t mi_debug_down_quant(mi_ctx* ctx, int32_t form);
 
 /* ---- op-level entry points (host buffers in/out) used by the parity tests ----
  * raw_blocks: GGUF-layout blocks of a rows x K matrix of ggml type `type`. */
@@ -379,7 +384,7 @@ int32_t mi_op_attention_batch(int32_t device, int32_t n_head, int32_t n_head_kv,
  * Q8_0 as the matrices need), then role 0 Q/K/V rows without RoPE (a second matrix of another type
  * = a second segment; y = [A x | B x]), 1 y = A x + resid, 2 y = silu(A x) * (B x) (gate/up pair),
  * 3 y = A x, 4 as 1 with x quantised inside the launch by every workgroup (the FFN down launch
- * of small models).  type2/raw2/rows2: the second matrix (raw2 NULL: none). */
+ * of small models), 5 as 4 in 16-wave workgroups of 16 rows.  type2/raw2/rows2: the second matrix (raw2 NULL: none). */
 int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                     int32_t type2, const void* raw_blocks2, int32_t rows2, const float* x, const float* resid, float* y);
 /* The F16 decode step's streaming GEMV (fgemv.hip), one launch over F16 matrices [rows][K] (K a
