@@ -641,6 +641,22 @@ const float* mi_embeddings(mi_ctx* c, int32_t row) {
     MI_TRY(nullptr)
 }
 
+int32_t mi_encode_seqs(mi_ctx* c, const int32_t* tokens, const int32_t* seq_len, int32_t n_seq) {
+    try {
+        if (!c || !tokens || !seq_len) throw Error("null argument");
+        return c->impl->encode_seqs(tokens, seq_len, n_seq);
+    }
+    MI_TRY(-1)
+}
+
+const float* mi_embeddings_seq(mi_ctx* c, int32_t seq) {
+    try {
+        if (!c) throw Error("null ctx");
+        return c->impl->embeddings_seq_host(seq);
+    }
+    MI_TRY(nullptr)
+}
+
 int32_t mi_prof_enable(mi_ctx* c, int32_t layer) {
     if (!c) return -1;
     if (layer >= c->impl->m->hp.n_layer) layer = c->impl->m->hp.n_layer - 1;

@@ -9,6 +9,10 @@
 //   up GEMM (+ bias, GELU), down GEMM (+ bias + residual), embd_norm (layer_output_norm)
 // -- 7 n_layer + 2 launches, and the pooling launch of a pooled context.  They are not captured
 // in a hipGraph: a graph per distinct n would be replayed once by most callers.
+//
+// encode_seqs (mi_encode_seqs) runs the same chain once over several sequences laid end to end:
+// the embedding takes each row's position inside its sequence, the norm and GEMM launches take all
+// rows, the attention is enc_seq.hip's segmented kernel, and one launch pools every sequence.
 #include "engine.h"
 
 #include <algorithm>
@@ -22,9 +26,12 @@ void Ctx::enc_init() {
     enc_max = (int)std::min<uint32_t>({n_batch, (uint32_t)ENC_MAX_TOK, (uint32_t)hp.n_ctx_train});
     if (enc_max < 1) throw Error("encoder context: no room for a token");
     init_enc_attributes();
-    const size_t rows = (size_t)enc_max, ne = (size_t)hp.n_embd;
-    enc_tok = mem.dev<int>(rows);
-    h_enc_tok = mem.host<int>((size_t)kEncRing * rows);
+    // the row buffers hold a multi-sequence call: up to n_batch rows, ENC_MAX_ROWS at the most
+    enc_rows = (int)std::min<uint32_t>(n_batch, (uint32_t)ENC_MAX_ROWS);
+    const size_t rows = (size_t)enc_rows, ne = (size_t)hp.n_embd;
+    // one upload per call: token ids, positions, the sequence list, the tile list (int4 entries)
+    enc_tok = mem.dev<int>(kEncInts * (rows + 1));
+    h_enc_tok = mem.host<int>((size_t)kEncRing * kEncInts * (rows + 1));
     enc_x = mem.dev<float>(rows * ne);
     enc_a = mem.dev<float>(rows * ne);
     enc_x1 = mem.dev<float>(rows * ne);
@@ -33,31 +40,25 @@ void Ctx::enc_init() {
     enc_h = mem.dev<float>(rows * (size_t)hp.n_ff);
     enc_k = mem.dev<__half>(rows * ne);
     enc_v = mem.dev<__half>(rows * ne);
+    enc_pool = mem.dev<float>(rows * ne);
     // always in embeddings mode: [n_batch] token rows, the pooled row, the last token's row
     embeddings = true;
     embd = mem.dev<float>(((size_t)n_batch + 2) * ne);
     h_embd = mem.host<float>(ne);
 }
 
-int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
-    const HParams& hp = m->hp;
-    if (n > enc_max)
-        throw Error("decode: an encoder call takes at most " + std::to_string(enc_max) +
-                    " tokens (min of n_batch, 512 and n_ctx_train), got " + std::to_string(n));
-    const int ne = hp.n_embd, nff = hp.n_ff;
-    const bool pooled = pooling != MI_POOLING_NONE;
-    embd_n = n;
-    embd_all = all && !pooled;
-    embd_rows = 0;
-    embd_valid = false;
-    out_rows = 0;
-
+int* Ctx::enc_upload_slot() {
     const long long slot = enc_slot++ % kEncRing;
     if (slot == 0 && enc_slot > 1) MI_HIP(hipStreamSynchronize(stream));   // the ring's copies are done
-    int* ht = h_enc_tok + slot * enc_max;
-    std::copy(tokens, tokens + n, ht);
-    MI_HIP(hipMemcpyAsync(enc_tok, ht, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+    return h_enc_tok + slot * kEncInts * (enc_rows + 1);
+}
 
+// The launch chain over n token rows whose ids are in enc_tok.  seq_len == nullptr: one sequence,
+// position = row, enc_attn_kernel.  Otherwise the rows are n_seq sequences end to end, with their
+// positions at d_pos and the tile list at d_tiles (device).
+void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_len, int n_seq) {
+    const HParams& hp = m->hp;
+    const int ne = hp.n_embd, nff = hp.n_ff;
     auto norm = [&](const float* in, const float* w, const float* b, float* out) {
         launch_embd_norm(EmbdNorm{in, ne, n, ne, w, b, hp.eps, out, ne}, stream);
     };
@@ -79,6 +80,7 @@ int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
 
     EncEmbed e{};
     e.tokens = enc_tok;
+    e.positions = d_pos;
     e.ntok = n;
     e.n_embd = ne;
     e.tok = m->tok_embd.p[0];
@@ -105,7 +107,12 @@ int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
         g.x_stride = ne;
         g.out_stride = ne;
         launch_enc_gemm(g, stream);
-        launch_enc_attn(EncAttn{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o}, stream);
+        if (seq_len)
+            launch_enc_attn_seq(EncAttnSeq{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o,
+                                           d_tiles, seq_len, n_seq},
+                                stream);
+        else
+            launch_enc_attn(EncAttn{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o}, stream);
         gemm(ENC_RESID, enc_o, ne, ne, L.wo, L.bo, enc_x, enc_a);
         norm(enc_a, L.attn_out_norm, L.attn_out_norm_b, enc_x1);
         gemm(ENC_GELU, enc_x1, ne, nff, L.up, L.bup, nullptr, enc_h);
@@ -113,6 +120,25 @@ int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
         // the last layer's rows are the embeddings (no final norm): token t -> row t of embd
         norm(enc_a, L.layer_out_norm, L.layer_out_norm_b, l == hp.n_layer - 1 ? embd : enc_x);
     }
+}
+
+int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
+    if (n > enc_max)
+        throw Error("decode: an encoder call takes at most " + std::to_string(enc_max) +
+                    " tokens (min of n_batch, 512 and n_ctx_train), got " + std::to_string(n));
+    const int ne = m->hp.n_embd;
+    const bool pooled = pooling != MI_POOLING_NONE;
+    embd_n = n;
+    embd_all = all && !pooled;
+    embd_rows = 0;
+    embd_valid = false;
+    enc_nseq = 0;
+    out_rows = 0;
+
+    int* ht = enc_upload_slot();
+    std::copy(tokens, tokens + n, ht);
+    MI_HIP(hipMemcpyAsync(enc_tok, ht, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+    enc_pass(n, nullptr, nullptr, nullptr, 0);
     if (pooled) {
         embd_pool_rows(0, n);
     } else if (embd_all) {
@@ -123,6 +149,70 @@ int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
     }
     embd_valid = true;
     return 0;
+}
+
+int Ctx::encode_seqs(const int32_t* tokens, const int32_t* seq_len, int n_seq) {
+    MI_HIP(hipSetDevice(device));
+    if (!enc) throw Error("encode_seqs: the model is not an encoder (general.architecture bert)");
+    if (n_seq < 1) throw Error("encode_seqs: n_seq must be at least 1, got " + std::to_string(n_seq));
+    const HParams& hp = m->hp;
+    long long total = 0;
+    for (int s = 0; s < n_seq; ++s) {
+        if (seq_len[s] < 1 || seq_len[s] > enc_max)
+            throw Error("encode_seqs: sequence " + std::to_string(s) + " has " + std::to_string(seq_len[s]) +
+                        " tokens; a sequence takes 1 to " + std::to_string(enc_max) + " (min of n_batch, 512 and n_ctx_train)");
+        total += seq_len[s];
+        if (total > enc_rows)
+            throw Error("encode_seqs: the call holds more than " + std::to_string(enc_rows) +
+                        " tokens (min of n_batch and 8192) with sequence " + std::to_string(s));
+    }
+    const int n = (int)total;
+    for (int s = 0, i = 0; s < n_seq; ++s)
+        for (int t = 0; t < seq_len[s]; ++t, ++i)
+            if (tokens[i] < 0 || tokens[i] >= hp.n_vocab)
+                throw Error("encode_seqs: token id out of range in sequence " + std::to_string(s) + " (token " + std::to_string(t) + ")");
+    const bool pooled = pooling != MI_POOLING_NONE;
+    unsynced = true;
+    batch_path = 6;
+    embd_n = n;
+    embd_all = !pooled;
+    embd_rows = 0;
+    embd_valid = false;
+    enc_nseq = 0;
+    out_rows = 0;
+
+    // ids | positions | sequence list | tile list, the lists 16-byte aligned, in one copy
+    int* ht = enc_upload_slot();
+    const size_t o_pos = ((size_t)n + 3) & ~(size_t)3, o_seq = 2 * o_pos, o_tile = o_seq + 4 * (size_t)n_seq;
+    std::copy(tokens, tokens + n, ht);
+    for (int s = 0, i = 0; s < n_seq; ++s)
+        for (int t = 0; t < seq_len[s]; ++t) ht[o_pos + i++] = t;
+    const int n_tiles = enc_seq_lists(seq_len, n_seq, ht + o_seq, ht + o_tile);
+    MI_HIP(hipMemcpyAsync(enc_tok, ht, (o_tile + 4 * (size_t)n_tiles) * sizeof(int), hipMemcpyHostToDevice, stream));
+    enc_pass(n, enc_tok + o_pos, enc_tok + o_tile, seq_len, n_seq);
+    if (pooled) launch_enc_pool_seq(EncPoolSeq{embd, hp.n_embd, hp.n_embd, n_seq, pooling, enc_tok + o_seq, enc_pool}, stream);
+    else embd_rows = n;
+    enc_nseq = n_seq;
+    embd_valid = true;
+    return 0;
+}
+
+const float* Ctx::embeddings_seq_host(int seq) {
+    if (!embeddings) throw Error("embeddings: the context is not in embeddings mode (mi_ctx_set_embeddings)");
+    if (!embd_valid) throw Error("no embeddings: decode since the mode was set first");
+    if (pooling == MI_POOLING_NONE)
+        throw Error("embeddings_seq: the context pools nothing (pooling NONE): read token rows with mi_embeddings");
+    if (enc_nseq == 0) {   // after mi_decode: the call is sequence 0
+        if (seq != 0) throw Error("embeddings_seq: sequence out of range (the last call held one sequence)");
+        return embeddings_host(0);
+    }
+    if (seq < 0 || seq >= enc_nseq)
+        throw Error("embeddings_seq: sequence " + std::to_string(seq) + " out of range (the last call held " + std::to_string(enc_nseq) + ")");
+    const int ne = m->hp.n_embd;
+    MI_HIP(hipSetDevice(device));
+    MI_HIP(hipMemcpyAsync(h_embd, enc_pool + (size_t)seq * ne, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, stream));
+    sync();
+    return h_embd;
 }
 
 }  // namespace mi

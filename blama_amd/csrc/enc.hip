@@ -2,8 +2,9 @@
 // flash_attn off) for the n <= ENC_MAX_TOK tokens of one call -- the first workload of this engine
 // with no quantised matrix in it.
 //
-//  * enc_embed_kernel: x[t] = pos_embd[t] + (tok_embd[token t] + token_types[0]): two f32 adds in
-//    that order, F16 table rows widened first (ggml_get_rows, ggml_add, ggml_add).
+//  * enc_embed_kernel: x[t] = pos_embd[p] + (tok_embd[token t] + token_types[0]), p = t or the
+//    caller's position of row t: two f32 adds in that order, F16 table rows widened first
+//    (ggml_get_rows, ggml_add, ggml_add).
 //  * enc_gemm_f16_kernel<EPI>: y[t][r] = sum_k f16(x[t][k]) * W[r][k] on v_mfma_f32_32x32x16_f16
 //    for one to three F16 matrices over one activation.  ggml_mul_mat of an F16 matrix rounds its
 //    f32 operand to f16 (the f16 vec_dot_type) and accumulates the exact products in f32; only the
@@ -25,22 +26,12 @@
 //    softmax (max, expf, the sum in double, p = e * (float)(1 / sum)); p rounded to f16; PV in f32.
 //    K and V of the head stream through LDS in 64-key chunks; the tile's scores stay in LDS
 //    ([32][n] f32) between the passes.
+#include "enc_common.h"
 #include "kernels.h"
-#include <hip/hip_runtime.h>
 
 namespace mi {
 namespace enc {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const unsigned lo = __half_as_ushort(__float2half_rn(a)), hi = __half_as_ushort(__float2half_rn(b));
-    return lo | (hi << 16);
-}
-__device__ __forceinline__ half8 as_h8(u32x4 v) { return __builtin_bit_cast(half8, v); }
 // elements i .. i + 7 of an F16 or F32 table row as f32 (i % 8 == 0: one or two 16-byte loads)
 __device__ __forceinline__ void widen8(const void* tab, int f16, long long i, float (&v)[8]) {
     if (f16) {
@@ -58,13 +49,13 @@ __device__ __forceinline__ void widen8(const void* tab, int f16, long long i, fl
 // ------------------------------------------------------------------ embedding ---
 __global__ __launch_bounds__(256) void enc_embed_kernel(const EncEmbed P) {
     const int t = blockIdx.x;
-    const long long tok = P.tokens[t];
+    const long long tok = P.tokens[t], pos = P.positions ? P.positions[t] : t;
     float* out = P.out + (long long)t * P.n_embd;
     for (int d = 8 * threadIdx.x; d < P.n_embd; d += 8 * 256) {   // 8 columns per thread: 16-byte accesses
         float a[8], b[8], c[8];
         widen8(P.tok, P.tok_f16, tok * P.n_embd + d, a);
         widen8(P.typ, P.typ_f16, d, b);
-        widen8(P.pos, P.pos_f16, (long long)t * P.n_embd + d, c);
+        widen8(P.pos, P.pos_f16, pos * P.n_embd + d, c);
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = c[e] + (a[e] + b[e]);
         *reinterpret_cast<float4*>(out + d) = float4{a[0], a[1], a[2], a[3]};
@@ -176,12 +167,6 @@ __global__ __launch_bounds__(64 * GW) void enc_gemm_f16_kernel(const EncGemm P) 
 // ------------------------------------------------------------------ attention ---
 constexpr int AW = 4;          // waves per workgroup: 8 of the tile's 32 queries each
 constexpr int CK = 64;         // keys per LDS chunk
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <int HD>
 __global__ __launch_bounds__(64 * AW) void enc_attn_kernel(const EncAttn P) {
@@ -301,7 +286,7 @@ void launch_enc_embed(const EncEmbed& p, hipStream_t s) {
 }
 
 void launch_enc_gemm(const EncGemm& p, hipStream_t s) {
-    if (p.ntok < 1 || p.ntok > ENC_MAX_TOK) throw Error("enc gemm: 1 to 512 tokens");
+    if (p.ntok < 1 || p.ntok > ENC_MAX_ROWS) throw Error("enc gemm: 1 to 8192 token rows");
     if (p.K < 32 || p.K % 32 || p.x_stride % 4 || p.out_stride % 4 || !p.x) throw Error("enc gemm: K must be a multiple of 32");
     if (p.nmat < 1 || p.nmat > 3) throw Error("enc gemm: one to three matrices");
     int tiles = 0;
@@ -333,6 +318,7 @@ void init_enc_attributes() {
     const int lds = (int)enc::attn_lds(ENC_MAX_TOK, 64);
     MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc::enc_attn_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc::enc_attn_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    enc::init_attn_seq_attributes();
 }
 
 void launch_enc_attn(const EncAttn& p, hipStream_t s) {

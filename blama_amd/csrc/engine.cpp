@@ -1146,6 +1146,7 @@ const float* Ctx::embeddings_host(int row) {
     const int ne = m->hp.n_embd;
     const float* src;
     if (pooling != MI_POOLING_NONE) {
+        if (enc_nseq > 0) throw Error("embeddings: after mi_encode_seqs a pooled context has a row per sequence (mi_embeddings_seq)");
         if (row != 0 && row != -1) throw Error("embeddings: a pooled context has one row (0 or -1)");
         src = embd_pooled();
     } else if (embd_rows > 0) {

@@ -328,14 +328,25 @@ struct Ctx {
     // must either check `embeddings` (the logits reads do) or check `enc` first.
     bool enc = false;
     int enc_max = 0;                    // tokens a call may hold: min(n_batch, ENC_MAX_TOK, n_ctx_train)
-    int* enc_tok = nullptr;             // [enc_max] token ids
-    int* h_enc_tok = nullptr;           // pinned ring [kEncRing][enc_max]
+    int enc_rows = 0;                   // token rows the buffers hold: min(n_batch, ENC_MAX_ROWS)
+    // a call's upload, packed: n token ids; for mi_encode_seqs also n positions and the int4 lists
+    // of enc_seq_lists (sequences, tiles; each of at most n entries) -- at most kEncInts x enc_rows ints
+    static constexpr int kEncInts = 10;
+    int* enc_tok = nullptr;
+    int* h_enc_tok = nullptr;           // pinned ring [kEncRing] of such uploads
     long long enc_slot = 0;
     static constexpr int kEncRing = 16;
+    int* enc_upload_slot();             // the next pinned slot (waits for the ring's copies on wrap)
     float *enc_x = nullptr, *enc_a = nullptr, *enc_x1 = nullptr, *enc_q = nullptr, *enc_o = nullptr, *enc_h = nullptr;
-    __half *enc_k = nullptr, *enc_v = nullptr;   // [enc_max][n_embd] f16 K / V of the layer
+    __half *enc_k = nullptr, *enc_v = nullptr;   // [enc_rows][n_embd] f16 K / V of the layer
+    float* enc_pool = nullptr;          // [enc_rows][n_embd] the pooled row of each sequence of mi_encode_seqs
+    int enc_nseq = 0;                   // sequences of the last call when it was mi_encode_seqs, else 0
     void enc_init();
+    void enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_len, int n_seq);
     int decode_enc(const int32_t* tokens, int n, bool all);
+    // several sequences laid end to end in one pass (enc_seq.hip); pooled: a row per sequence
+    int encode_seqs(const int32_t* tokens, const int32_t* seq_len, int n_seq);
+    const float* embeddings_seq_host(int seq);
     // control vector (llama_adapter_cvec, b5187): row l is layer l's direction, added to the
     // residual stream after the layer's FFN residual add (build_cvec) in every path.  A property
     // of the context, not of its state (mi_state_get / mi_state_set leave it alone).

@@ -619,10 +619,13 @@ struct EmbdPool {
 void launch_embd_pool(const EmbdPool& p, hipStream_t s);
 
 // ---- encoder models (enc.hip): llm_build_bert, b5187 ----
-constexpr int ENC_MAX_TOK = 512;   // tokens of one call (llama.cpp: n_ubatch >= n_tokens for non-causal attention)
-// out[t] = pos[t] + (tok[tokens[t]] + typ[0]): the tables F16 (*_f16) or F32 rows of n_embd
+constexpr int ENC_MAX_TOK = 512;   // tokens of one sequence (llama.cpp: n_ubatch >= n_tokens for non-causal attention)
+constexpr int ENC_MAX_ROWS = 8192; // token rows of one call: the sequences of mi_encode_seqs laid end to end
+// out[t] = pos[p] + (tok[tokens[t]] + typ[0]), p = positions ? positions[t] : t: the tables F16
+// (*_f16) or F32 rows of n_embd
 struct EncEmbed {
     const int* tokens;     // [ntok]
+    const int* positions;  // [ntok], or null: the row is the position
     int ntok, n_embd;
     const void *tok, *typ, *pos;
     int tok_f16, typ_f16, pos_f16;
@@ -632,7 +635,7 @@ void launch_enc_embed(const EncEmbed& p, hipStream_t s);
 // y[t][r] = sum_k f16(x[t][k]) * W[r][k] (f32 accumulation of exact f16 products) for one to three
 // F16 matrices [rows][K] over one activation, then the epilogue: + bias[r]; gelu(. + bias[r]) by
 // ggml's f16 table; (. + bias[r]) + resid[t][r] -- each add a separate f32 operation.  rows % 32
-// == 0, K % 32 == 0, 1 <= ntok <= ENC_MAX_TOK.  A matrix writes f32 rows (out) or f16 rows (out16).
+// == 0, K % 32 == 0, 1 <= ntok <= ENC_MAX_ROWS.  A matrix writes f32 rows (out) or f16 rows (out16).
 // ENC_ADD: y + resid[t][r] with no bias (the bias-free projections of an F16 LLaMA model's prompt batches)
 enum EncEpi { ENC_NONE = 0, ENC_BIAS = 1, ENC_GELU = 2, ENC_RESID = 3, ENC_ADD = 4 };
 struct EncMat {
@@ -664,5 +667,39 @@ struct EncAttn {
 bool enc_attn_supported(int head_dim);
 void init_enc_attributes();      // once per device (the attention kernel's LDS limit)
 void launch_enc_attn(const EncAttn& p, hipStream_t s);
+
+// ---- several sequences per encoder call (enc_seq.hip) ----
+// The call's sequences lie end to end: sequence s owns rows [start_s, start_s + len_s), 1 <= len_s <=
+// ENC_MAX_TOK, and a token attends to the tokens of its own sequence only.  The device lists are
+// built on the host by enc_seq_lists and uploaded with the tokens:
+//   seqs  [n_seq]   int4 {start, len, bits of 1.0f / len, 0}
+//   tiles [n_tiles] int4 {start, len, offset of the 32-query tile inside the sequence, s}
+// Tiles are counted per sequence (ceil(len / 32) each), so n_tiles <= the call's tokens.
+// Returns n_tiles; throws when a length is outside 1 .. ENC_MAX_TOK (naming the sequence).
+int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles);
+// Attention as EncAttn's, per sequence, on v_mfma_f32_32x32x16_f16; a workgroup per (head, tile).
+// A sequence's output rows have the same bits whatever else the call holds.
+struct EncAttnSeq {
+    const float* q;        // [ntok][q_stride]
+    const __half *k, *v;   // [ntok][kv_stride]
+    int q_stride, kv_stride, out_stride;
+    int n_head, head_dim, ntok;
+    float scale;
+    float* out;            // [ntok][out_stride]
+    const int* tiles;      // device, from enc_seq_lists
+    const int* seq_len;    // host [n_seq]: read by the launcher's checks only
+    int n_seq;
+};
+void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s);
+// Pooling of every sequence of a call, a workgroup per (sequence, 64 columns): CLS the first row,
+// LAST the last, MEAN sum_t row_t * (1.0f / len) -- embd_pool_kernel's arithmetic per sequence.
+struct EncPoolSeq {
+    const float* rows;     // [ntok][stride]
+    int stride, K, n_seq;
+    int pooling;           // MI_POOLING_MEAN / CLS / LAST
+    const int* seqs;       // device, from enc_seq_lists
+    float* out;            // [n_seq][K]
+};
+void launch_enc_pool_seq(const EncPoolSeq& p, hipStream_t s);
 
 }  // namespace mi

@@ -951,8 +951,8 @@ int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int3
         if (epilogue < ENC_NONE || epilogue > ENC_RESID) throw Error("op_gemm_f16: epilogue 0 .. 3");
         if (epilogue != ENC_NONE && !bias) throw Error("op_gemm_f16: this epilogue needs a bias");
         if (epilogue == ENC_RESID && !resid) throw Error("op_gemm_f16: residual epilogue without resid");
-        if (rows < 32 || rows % 32 || K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_TOK)
-            throw Error("op_gemm_f16: rows % 32, K % 32, 1 <= ntok <= 512");
+        if (rows < 32 || rows % 32 || K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_ROWS)
+            throw Error("op_gemm_f16: rows % 32, K % 32, 1 <= ntok <= 8192");
         MI_HIP(hipSetDevice(device));
         const size_t ny = (size_t)ntok * rows;
         Dev<__half> dw((size_t)rows * K, f16(w_f16));
@@ -994,6 +994,35 @@ int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, in
         Dev<__half> dk(n, f16(k_f16)), dv(n, f16(v_f16));
         launch_enc_attn(EncAttn{dq.p, dk.p, dv.p, ne, ne, ne, n_head, head_dim, ntok, 1.0f / std::sqrt((float)head_dim), dout.p},
                         nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dout.download(out);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// The segmented attention of mi_encode_seqs (enc_seq.hip enc_attn_seq_kernel): n_seq sequences laid end
+// to end, sequence s of seq_len[s] tokens, every token over the tokens of its own sequence only.
+int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
+                                 const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out) {
+    try {
+        if (!seq_len || !q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc_seqs: null argument");
+        if (n_head < 1 || n_seq < 1 || !enc_attn_supported(head_dim)) throw Error("op_attention_enc_seqs: head_dim 32 or 64, n_seq >= 1");
+        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 512
+        enc_seq_lists(seq_len, n_seq, nullptr, tiles.data());
+        long long ntok = 0;
+        for (int s = 0; s < n_seq; ++s) ntok += seq_len[s];
+        if (ntok > ENC_MAX_ROWS) throw Error("op_attention_enc_seqs: at most 8192 tokens");
+        MI_HIP(hipSetDevice(device));
+        init_enc_attributes();
+        const int ne = n_head * head_dim;
+        const size_t n = (size_t)ntok * ne;
+        Dev<float> dq(n, q), dout(n);
+        Dev<__half> dk(n, f16(k_f16)), dv(n, f16(v_f16));
+        Dev<int> dt(tiles.size(), tiles.data());
+        launch_enc_attn_seq(EncAttnSeq{dq.p, dk.p, dv.p, ne, ne, ne, n_head, head_dim, (int)ntok, 1.0f / std::sqrt((float)head_dim),
+                                       dout.p, dt.p, seq_len, n_seq},
+                            nullptr);
         MI_HIP(hipDeviceSynchronize());
         dout.download(out);
         return 0;

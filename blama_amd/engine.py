@@ -100,6 +100,8 @@ _SIGS = {
     "mi_ctx_set_embeddings": (C.c_int32, [_P, C.c_int32, C.c_int32]),
     "mi_ctx_pooling": (C.c_int32, [_P]),
     "mi_embeddings": (C.POINTER(C.c_float), [_P, C.c_int32]),
+    "mi_encode_seqs": (C.c_int32, [_P, _P, _P, C.c_int32]),
+    "mi_embeddings_seq": (C.POINTER(C.c_float), [_P, C.c_int32]),
     "mi_prof_enable": (C.c_int32, [_P, C.c_int32]),
     "mi_prof_read": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_int32]),
     "mi_prof_ffn_bytes": (C.c_int64, [_P]),
@@ -138,6 +140,7 @@ _SIGS = {
                                    C.c_int32, _P, C.c_int32, _P, _P]),
     "mi_op_gemm_f16": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "mi_op_attention_enc": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mi_op_attention_enc_seqs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "mi_op_moe_decode": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                      C.c_float, _P, _P, _P, _P, _P]),
 }
@@ -438,6 +441,22 @@ class Context:
             raise EngineError(f"embeddings: {last_error()}")
         return np.ctypeslib.as_array(p, shape=(self.model.n_embd,)).copy()
 
+    def encode(self, seqs) -> int:
+        """mi_encode_seqs: one encoder pass over several sequences (a list of int32 token arrays), each
+        at positions 0 .. len - 1 and attending to itself only.  Pooled context: embeddings_seq(i);
+        pooling NONE: embeddings(row) over the concatenation."""
+        seqs = [np.ascontiguousarray(s, dtype=np.int32).ravel() for s in seqs]
+        lens = np.array([s.size for s in seqs], np.int32)
+        t = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.int32), dtype=np.int32)
+        return _check(lib().mi_encode_seqs(self.h, _ptr(t), _ptr(lens), len(seqs)), "encode")
+
+    def embeddings_seq(self, i: int) -> np.ndarray:
+        """mi_embeddings_seq: the pooled row of sequence i of the last call."""
+        p = lib().mi_embeddings_seq(self.h, i)
+        if not p:
+            raise EngineError(f"embeddings_seq: {last_error()}")
+        return np.ctypeslib.as_array(p, shape=(self.model.n_embd,)).copy()
+
     def prof_enable(self, stride: int):
         lib().mi_prof_enable(self.h, stride)
 
@@ -463,7 +482,7 @@ class Context:
     def batch_path(self) -> int:
         """The form the most recent decode call took (its first physical batch's): 0 one decode step
         per token, 1 the v_dot4 GEMM, 2 the tiled int8-MFMA GEMM, 3 the short split-K GEMM, 4 the F16
-        MFMA GEMM, 5 an encoder pass; -1 before the first call."""
+        MFMA GEMM, 5 an encoder pass, 6 a multi-sequence encoder pass (encode); -1 before the first call."""
         return int(lib().mi_batch_path(self.h))
 
     @property
@@ -846,4 +865,20 @@ def op_attention_enc(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, device: in
     out = np.empty((ntok, n_head, hd), np.float32)
     _check(lib().mi_op_attention_enc(device, n_head, hd, ntok, _ptr(q), _ptr(k16), _ptr(v16), _ptr(out)),
            "op_attention_enc")
+    return out
+
+
+def op_attention_enc_seqs(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, seq_len, device: int = 0) -> np.ndarray:
+    """mi_op_attention_enc_seqs: as op_attention_enc over sequences of seq_len tokens laid end to end
+    (sum(seq_len) == ntok): every token over the tokens of its own sequence only."""
+    q = np.ascontiguousarray(q, np.float32)
+    ntok, n_head, hd = q.shape
+    k16 = np.ascontiguousarray(k16, np.float16)
+    v16 = np.ascontiguousarray(v16, np.float16)
+    lens = np.ascontiguousarray(seq_len, np.int32)
+    if int(lens.sum()) != ntok:
+        raise EngineError(f"op_attention_enc_seqs: the lengths sum to {int(lens.sum())}, q has {ntok} rows")
+    out = np.empty((ntok, n_head, hd), np.float32)
+    _check(lib().mi_op_attention_enc_seqs(device, n_head, hd, lens.size, _ptr(lens), _ptr(q), _ptr(k16), _ptr(v16),
+                                          _ptr(out)), "op_attention_enc_seqs")
     return out

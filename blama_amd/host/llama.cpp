@@ -1066,6 +1066,41 @@ std::vector<float> InstanceEmbedding::getEmbeddingVector(std::span<const Token> 
     return out;
 }
 
+std::vector<std::vector<float>> InstanceEmbedding::getEmbeddingVectors(std::span<const std::vector<Token>> prompts,
+                                                                       int32_t normalization) const {
+    std::vector<std::vector<float>> out;
+    out.reserve(prompts.size());
+    if (mi_model_causal_attn(m_model.mmodel()) != 0) {   // no encoder: a call per prompt
+        for (const std::vector<Token>& p : prompts) out.push_back(getEmbeddingVector(p, normalization));
+        return out;
+    }
+    const size_t cap = std::min<size_t>(mi_n_batch(m_ctx), 8192), n = embeddingDim();
+    const bool pooled = mi_ctx_pooling(m_ctx) != MI_POOLING_NONE;
+    std::vector<Token> tokens;
+    std::vector<int32_t> lens;
+    for (size_t i = 0; i < prompts.size();) {
+        tokens.clear();
+        lens.clear();
+        // the prompts from i on that fit one call (an oversized or empty one goes alone, for the engine's message)
+        do {
+            tokens.insert(tokens.end(), prompts[i].begin(), prompts[i].end());
+            lens.push_back((int32_t)prompts[i].size());
+            ++i;
+        } while (i < prompts.size() && tokens.size() + prompts[i].size() <= cap);
+        if (mi_encode_seqs(m_ctx, tokens.data(), lens.data(), (int32_t)lens.size()) != 0)
+            BL_THROW("Failed to decode! " << last_error());
+        int32_t row = -1;
+        for (size_t s = 0; s < lens.size(); ++s) {
+            row += lens[s];   // pooling NONE: the sequence's last token, as getEmbeddingVector
+            const float* embd = pooled ? mi_embeddings_seq(m_ctx, (int32_t)s) : mi_embeddings(m_ctx, row);
+            if (!embd) BL_THROW("Failed to get embeddings: " << last_error());
+            out.emplace_back(n, 0.0f);
+            normalize(std::span<const float>(embd, n), out.back(), normalization);
+        }
+    }
+    return out;
+}
+
 uint32_t InstanceEmbedding::embeddingDim() const noexcept { return (uint32_t)mi_model_n_embd(m_model.mmodel()); }
 
 void Instance::addControlVector(const ControlVector& ctrlVector) {

@@ -402,6 +402,12 @@ public:
     // (-1 none, 0 max-abs / 32760, 1 taxicab, 2 Euclidean [default], other p: p-norm).  Throws on an
     // empty prompt or one longer than the batch or the context, where the reference only logs.
     std::vector<float> getEmbeddingVector(std::span<const Token> prompt, int32_t normalization = 2) const;
+    // One vector per prompt, each normalised as getEmbeddingVector does it.  On an encoder model the
+    // prompts go, in order, into as few mi_encode_seqs calls as the batch size allows (a prompt's
+    // vector has the same bits whatever shares its call); on any other model this is one
+    // getEmbeddingVector per prompt.  Throws as getEmbeddingVector does.
+    std::vector<std::vector<float>> getEmbeddingVectors(std::span<const std::vector<Token>> prompts,
+                                                        int32_t normalization = 2) const;
     uint32_t embeddingDim() const noexcept;
     const Model& model() const noexcept { return m_model; }
     mi_ctx* mctx() const noexcept { return m_ctx; }

@@ -227,7 +227,21 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * mi_ctx_apply_cvec < 0; mi_state_size / mi_state_get / mi_state_set return 0; mi_logits NULL,
  * mi_topk / mi_gather / mi_gather_rows < 0; mi_lora_load on the model is refused.  Not served:
  * quantised or F32 BERT matrices, the nomic / jina variants (RoPE, gated FFN, attention-norm
- * tensors), RANK pooling, token types other than 0, several sequences in one call. */
+ * tensors), RANK pooling, token types other than 0.
+ *
+ * Several sequences in one call (an encoder context only): mi_encode_seqs runs ONE pass over n_seq
+ * sequences laid end to end in tokens -- sequence s has seq_len[s] tokens at positions 0 ..
+ * seq_len[s] - 1, and a token attends to the tokens of its own sequence only (the segmented MFMA
+ * attention of enc_seq.hip).  The launches of the pass are those of one mi_decode call whatever
+ * n_seq is.  A sequence's rows have the same bits alone and in any batch of sequences.  Refused (< 0,
+ * with a message naming the sequence; n_batch is truncated to n_ctx as for every context, so create the
+ * context with n_ctx >= the rows a call should hold): a context that is no encoder, n_seq < 1, a length < 1 or >
+ * min(512, n_ctx_train), a total above min(n_batch, 8192), a token id outside the vocabulary.
+ * Pooled context: mi_embeddings_seq(ctx, s) is sequence s's row (MEAN = sum_t row_t * (1.0f / len_s)
+ * in token order, CLS the first row, LAST the last), and mi_embeddings is refused until the next
+ * mi_decode.  Pooling NONE: mi_embeddings(ctx, row) is the row of token `row` of the concatenation
+ * (0 .. total - 1, -1 the last) and mi_embeddings_seq is refused.  After an mi_decode on a pooled
+ * context (of any architecture) mi_embeddings_seq(ctx, 0) is the call's row. */
 #define MI_POOLING_UNSPECIFIED (-1)
 #define MI_POOLING_NONE 0
 #define MI_POOLING_MEAN 1
@@ -258,6 +272,11 @@ int32_t mi_ctx_pooling(const mi_ctx* ctx);
  * NULL with a message when the mode is off, no decode has happened since it was set, or the row is
  * out of range. */
 const float* mi_embeddings(mi_ctx* ctx, int32_t row);
+/* n_seq sequences laid end to end in tokens; sequence s has seq_len[s] tokens at positions 0..seq_len[s]-1 */
+int32_t mi_encode_seqs(mi_ctx* ctx, const int32_t* tokens, const int32_t* seq_len, int32_t n_seq);
+/* llama_get_embeddings_seq: the pooled row of sequence seq of the last call; n_embd floats, context-owned,
+ * valid until the next decode / encode or embeddings call.  Synchronises.  NULL with a message. */
+const float* mi_embeddings_seq(mi_ctx* ctx, int32_t seq);
 
 /* ---- measurement: HIP events on the context's stream bracketing the FFN
  * gate/up GEMV launch of `layer` in every output-producing decode step (the
@@ -278,8 +297,8 @@ int64_t mi_prof_bytes(const mi_ctx* ctx);
 int32_t mi_decode_path(const mi_ctx* ctx);
 /* Diagnostics: the form the most recent mi_decode call took (of a call of several physical batches:
  * its first): 0 one decode step per token, 1 the v_dot4 GEMM, 2 the tiled int8-MFMA GEMM, 3 the
- * short split-K GEMM, 4 the F16 MFMA GEMM, 5 an encoder pass; -1 for a null context or before the
- * first call.  Pure reporting. */
+ * short split-K GEMM, 4 the F16 MFMA GEMM, 5 an encoder pass, 6 a multi-sequence encoder pass
+ * (mi_encode_seqs); -1 for a null context or before the first call.  Pure reporting. */
 int32_t mi_batch_path(const mi_ctx* ctx);
 /* Diagnostics: copies the per-workgroup s_memrealtime stamps (100 MHz) of the
  * first n_launch launches of the last decode step, [launch][512][8] uint64, to
@@ -440,7 +459,7 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
 /* The encoder pass's dense F16 GEMM (enc.hip, v_mfma_f32_32x32x16_f16): y[t][r] = sum_k f16(x[t][k]) *
  * w[r][k] in f32, then the epilogue -- 0 none, 1 + bias[r], 2 gelu(. + bias[r]) by ggml's f16 table,
  * 3 (. + bias[r]) + resid[t][r].  w: [rows][K] f16 bits, x: [ntok][K], resid / y: [ntok][rows];
- * rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 512. */
+ * rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 8192. */
 int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int32_t K, int32_t ntok,
                        const float* x, const float* bias, const float* resid, int32_t epilogue, float* y);
 /* The encoder pass's bidirectional attention (enc.hip): every token over all ntok <= 512 tokens, no
@@ -448,6 +467,11 @@ int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int3
  * shape; head_dim 32 or 64. */
 int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok,
                             const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
+/* The segmented attention of mi_encode_seqs (enc_seq.hip, v_mfma_f32_32x32x16_f16): n_seq sequences laid
+ * end to end, sequence s of 1 <= seq_len[s] <= 512 tokens, every token over the tokens of its own
+ * sequence only; shapes and scale as mi_op_attention_enc with ntok = the sum of the lengths (<= 8192). */
+int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
+                                 const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);
