@@ -11,7 +11,7 @@ namespace mi {
 
 // ggml_type ids (llama.cpp b5187 ggml.h) -- the GGUF tensor type field.
 enum GgmlType : int {
-    T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q8_0 = 8, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
+    T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q8_0 = 8, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
     T_BF16 = 30,
 };
 // ggml's name of a tensor type id (ggml.c type_traits), for messages; "type N" for ids past the table
@@ -34,15 +34,18 @@ inline int block_bytes(int t) {
     switch (t) {
     case T_F32: return 4; case T_F16: return 2; case T_Q8_0: return 34;
     case T_Q4_0: return 18; case T_Q5_0: return 22;
+    case T_Q3_K: return 110;
     case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
     default: return 0;
     }
 }
 inline bool is_quant(int t) {
-    return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K;
+    return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K;
 }
 // The 32-weight-block types with an f16 scale per block (Q4_0, Q5_0: llama-quantize's classic outputs).
 inline bool is_legacy_quant(int t) { return t == T_Q4_0 || t == T_Q5_0; }
+// The types only the dense LLaMA kernels read: refused in MoE, GPT-2 and BERT models (Model::check_types).
+inline bool dense_only_quant(int t) { return is_legacy_quant(t) || t == T_Q3_K; }
 // Whether a matrix of this type takes Q8_0 activations (vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0);
 // the k-quants take Q8_K ones.
 inline bool takes_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0; }
@@ -58,17 +61,27 @@ inline bool takes_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0;
 //   Q8_0: p0 qs[256]  p1 f16 d[8]
 //   Q4_0: p0 qs[128]  p1 f16 d[8]                 (block j of the superblock: qs bytes 16 j.., d[j])
 //   Q5_0: p0 qs[128]  p1 qh[32]  p2 f16 d[8]      (block j: qs bytes 16 j.., qh bytes 4 j.., d[j])
+//   Q3_K: p0 qs[64]   p1 hmask[32]  p2 hdr[16] = {u8 scales[12], f16 d, 2 zero bytes}
+//         Weight 128 n + 32 s + l of the superblock is bits 2 s.. of qs[32 n + l] with bit 4 n + s of
+//         hmask[l] as its third bit (set: q = low2, clear: q = low2 - 4).  The GEMV kernels give every
+//         superblock 8 lanes: lane j reads the qs bytes 16 (j >> 1).. (half n = j >> 2, l from
+//         16 ((j >> 1) & 1)) and the hmask bytes 16 ((j >> 1) & 1).. -- two lanes share each 16-byte
+//         piece, one request per line -- and owns the shifts 2 (j & 1) and 2 (j & 1) + 1 of it: 32
+//         weights in the 16-weight scale groups 8 n + 4 (j & 1) + ((j >> 1) & 1) and that + 2, against
+//         two 16-byte activation runs 32 bytes apart (qdot.h, Kq<T_Q3_K>).
 constexpr int kPlanePadSb = 16;  // tail padding (superblocks) after every plane (ring GEMV over-reads)
 inline int plane_count(int t) {
     switch (t) { case T_Q4_K: return 2; case T_Q5_K: return 3; case T_Q6_K: return 4;
-                 case T_Q8_0: return 2; case T_Q4_0: return 2; case T_Q5_0: return 3; default: return 0; }
+                 case T_Q8_0: return 2; case T_Q4_0: return 2; case T_Q5_0: return 3; case T_Q3_K: return 3;
+                 default: return 0; }
 }
 inline int plane_sb_bytes(int t, int p) {
     static const int q4k[] = {128, 16}, q5k[] = {128, 32, 16}, q6k[] = {128, 64, 16, 2}, q80[] = {256, 16};
-    static const int q40[] = {128, 16}, q50[] = {128, 32, 16};
+    static const int q40[] = {128, 16}, q50[] = {128, 32, 16}, q3k[] = {64, 32, 16};
     switch (t) {
     case T_Q4_K: return q4k[p]; case T_Q5_K: return q5k[p]; case T_Q6_K: return q6k[p];
-    case T_Q8_0: return q80[p]; case T_Q4_0: return q40[p]; case T_Q5_0: return q50[p]; default: return 0;
+    case T_Q8_0: return q80[p]; case T_Q4_0: return q40[p]; case T_Q5_0: return q50[p];
+    case T_Q3_K: return q3k[p]; default: return 0;
     }
 }
 

@@ -357,6 +357,14 @@ DvFn dv_fn_role(int t0, int t1, int c) {
     // Q4_0 / Q5_0: one type per launch (llama-quantize gives Q, K and V one type)
     case T_Q4_0: return t1 >= 0 ? nullptr : dv_fn_c<T_Q4_0, -1, RW, ROLE, LORA>(c);
     case T_Q5_0: return t1 >= 0 ? nullptr : dv_fn_c<T_Q5_0, -1, RW, ROLE, LORA>(c);
+    // Q3_K: alone, or Q and K of it with V as Q4_K / Q5_K (llama-quantize's Q3_K_M / Q3_K_L)
+    case T_Q3_K:
+        if (t1 < 0) return dv_fn_c<T_Q3_K, -1, RW, ROLE, LORA>(c);
+        if constexpr (dv_base(ROLE) == DV_QKV) {
+            if (t1 == T_Q4_K) return dv_fn_c<T_Q3_K, T_Q4_K, RW, ROLE, LORA>(c);
+            if (t1 == T_Q5_K) return dv_fn_c<T_Q3_K, T_Q5_K, RW, ROLE, LORA>(c);
+        }
+        return nullptr;
     default: return nullptr;
     }
 }

@@ -147,6 +147,20 @@ template <> struct GvAct<T_Q6_K> {
         return r;
     }
 };
+template <> struct GvAct<T_Q3_K> {   // lane j: half n, mask half lh, shift pair sp (Kq<T_Q3_K>)
+    __device__ static Kq<T_Q3_K>::AR get(const char* s, const GvLds& L, int sb, int j) {
+        const int n = j >> 2, lh = (j >> 1) & 1, sp = j & 1;
+        const char* ab = s + L.q8k + sb * GV_ASTR + 128 * n + 64 * sp + 16 * lh;
+        Kq<T_Q3_K>::AR r;
+        r.alo = *reinterpret_cast<const i32x4*>(ab);
+        r.ahi = *reinterpret_cast<const i32x4*>(ab + 32);
+        const int* bs = reinterpret_cast<const int*>(s + L.bsum) + sb * 16 + 8 * n + 4 * sp + lh;
+        r.bs_lo = bs[0];
+        r.bs_hi = bs[2];
+        r.dx = reinterpret_cast<const float*>(s + L.dk)[sb];
+        return r;
+    }
+};
 template <> struct GvAct<T_Q8_0> {
     __device__ static Kq<T_Q8_0>::AR get(const char* s, const GvLds& L, int sb, int j) {
         const char* ab = s + L.q80 + sb * GV_ASTR + 32 * j;
@@ -962,6 +976,7 @@ GvFn gv_fn_rw(int t0, int t1, int kb, int tag) {
     switch (t0) {
     case T_Q4_0: return gv_fn_same<T_Q4_0, RW>(t1, kb, tag);
     case T_Q5_0: return gv_fn_same<T_Q5_0, RW>(t1, kb, tag);
+    case T_Q3_K: return gv_fn_same<T_Q3_K, RW>(t1, kb, tag);   // (a Q3_K_M layer's V of another type: its own launch)
     case T_Q4_K: return gv_fn_pair<T_Q4_K, RW>(t1, kb, tag);
     case T_Q5_K: return gv_fn_pair<T_Q5_K, RW>(t1, kb, tag);
     case T_Q6_K: return t1 == T_Q6_K ? nullptr : gv_fn_pair<T_Q6_K, RW>(t1, kb, tag);
@@ -1020,7 +1035,7 @@ int gemv_grid(const GemvParams& p) {
 
 void init_kernel_attributes() {
     init_gemm_attributes();
-    const int types[6] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0};
+    const int types[7] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K};
     for (int rw = 1; rw <= 2; ++rw)
         for (int kb : {1, 2, 4})
             for (int t0 : types)

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
 typedef void (*GemmFn)(const GemmParams);
 static GemmFn gemm_fn(int type, bool pre);
 void init_gemm_attributes() {
-    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0})
+    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K})
         for (bool pre : {false, true})
             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t, pre)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -265,6 +265,7 @@ static GemmFn gemm_fn(int type, bool pre) {
     case T_Q8_0: return pre ? gemm_t<T_Q8_0, 4, true> : gemm_t<T_Q8_0, 4, false>;
     case T_Q4_0: return pre ? gemm_t<T_Q4_0, 4, true> : gemm_t<T_Q4_0, 4, false>;
     case T_Q5_0: return pre ? gemm_t<T_Q5_0, 4, true> : gemm_t<T_Q5_0, 4, false>;
+    case T_Q3_K: return pre ? gemm_t<T_Q3_K, 4, true> : gemm_t<T_Q3_K, 4, false>;
     default: return nullptr;
     }
 }
@@ -358,6 +359,16 @@ __device__ float dequant_elem(const QMat& M, long long row, int col) {
         }
         const uint8_t* dp = M.p[q5 ? 2 : 1] + sbi * 16 + blk * 2;
         return (float)(q - (q5 ? 16 : 8)) * h2f(dp[0] | (dp[1] << 8));
+    }
+    case T_Q3_K: {   // dequantize_row_q3_K: (d * (sc6 - 32)) * q, q = low2 - (mask bit ? 0 : 4)
+        const int n = i >> 7, s = (i >> 5) & 3, l = i & 31, g = i >> 4;
+        const int low2 = (M.p[0][sbi * 64 + 32 * n + l] >> (2 * s)) & 3;
+        const int q = low2 - (((M.p[1][sbi * 32 + l] >> (4 * n + s)) & 1) ? 0 : 4);
+        const uint8_t* sc = M.p[2] + sbi * 16;
+        const int lo4 = g < 8 ? (sc[g] & 0xF) : (sc[g - 8] >> 4);
+        const int sc6 = lo4 | (((sc[8 + (g & 3)] >> (2 * (g >> 2))) & 3) << 4);
+        const float d = h2f(sc[12] | (sc[13] << 8));
+        return (d * (float)(sc6 - 32)) * (float)q;
     }
     case T_F32:
         return reinterpret_cast<const float*>(M.p[0])[row * M.K + col];
@@ -796,6 +807,12 @@ __global__ void repack_kernel(const uint8_t* raw, int type, long long nsb, uint8
                 for (int k = 0; k < 4; ++k) p1[i * 32 + blk * 4 + k] = b[blk * 22 + 2 + k];
                 for (int k = 0; k < 16; ++k) p0[i * 128 + blk * 16 + k] = b[blk * 22 + 6 + k];
             }
+        } else if (type == T_Q3_K) {
+            const uint8_t* b = raw + i * 110;   // hmask[32], qs[64], scales[12], f16 d
+            for (int k = 0; k < 64; ++k) p0[i * 64 + k] = b[32 + k];
+            for (int k = 0; k < 32; ++k) p1[i * 32 + k] = b[k];
+            for (int k = 0; k < 14; ++k) p2[i * 16 + k] = b[96 + k];
+            p2[i * 16 + 14] = p2[i * 16 + 15] = 0;
         }
     }
 }

@@ -16,6 +16,8 @@
 //     work is done once per row tile instead of once per wave, and there is no integer multiply
 //     per sub-block and result (VALU was the bound: ~310 VALU against 10 MFMAs per wave and
 //     superblock); the min terms sum_j m_j * bsum_j are two more MFMAs (bsum = 64 hi + lo);
+//   * Q3_K: the same once-per-row-tile decode into ONE plane of the negated scaled weights
+//     -q (sc6 - 32) in -128..+124 (q3k_span), one MFMA per span, the sign taken back in the update;
 //   * Q6_K: the scaled hi/lo operands of the MFMA-order copy, accumulated by the MFMA; Q8_0:
 //     one MFMA per 32-block and a float update per block (vec_dot_q8_0_q8_0's order);
 //   * per 32x32 tile the integer sums are the contract's exact int32 values, and the float update
@@ -86,6 +88,16 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
             } else {
                 plane = 2; c = (off - 5120) >> 4; byte = (off - 5120) & 15;
             }
+        } else if (A.type == T_Q3_K) {
+            if (off < 2048) {
+                const int p = off >> 10, ln = (off >> 4) & 63, e = off & 15;
+                plane = 0; c = ln & 31; byte = 32 * p + 16 * (ln >> 5) + e;
+            } else if (off < 3072) {
+                const int ln = (off - 2048) >> 4, e = off & 15;
+                plane = 1; c = ln & 31; byte = 16 * (ln >> 5) + e;
+            } else {
+                plane = 2; c = (off - 3072) >> 4; byte = (off - 3072) & 15;
+            }
         } else {   // Q6_K
             if (off < 16384) {   // w = (q - 32) * scale of element 32s + 16h + e (dequantize_row_q6_K)
                 const int lo = off >= 8192, o2 = off & 8191;
@@ -109,6 +121,7 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
         long long row = pair ? 16LL * rt + (c & 15) : 32LL * rt + c;
         if (row >= M.rows) row = M.rows - 1;
         const int pb = (A.type == T_Q4_0 || A.type == T_Q5_0) ? 16
+                     : A.type == T_Q3_K ? (plane == 0 ? 64 : plane == 1 ? 32 : 16)
                      : A.type == T_Q8_0 ? (plane == 0 ? 256 : 16)
                      : A.type == T_Q4_K ? (plane == 0 ? 128 : 16)
                      : A.type == T_Q5_K ? (plane == 0 ? 128 : plane == 1 ? 32 : 16)
@@ -210,7 +223,7 @@ template <int T> struct M2 {
     static constexpr int NI = STAGE / 1024;                             // 1 KiB LDS-DMA pieces
     static constexpr int NIW = (NI + NW - 1) / NW;                      // per wave (some repeat)
     static constexpr int NPL = 2;                                       // K-quant operand planes
-    static constexpr int PLANES = (T == T_Q4_K || T == T_Q5_K) ? RT * NPL * 8 * 1024 : 0;
+    static constexpr int PLANES = (T == T_Q4_K || T == T_Q5_K) ? RT * NPL * 8 * 1024 : T == T_Q3_K ? RT * 8 * 1024 : 0;   // Q3_K: one plane
     static constexpr int lds(int nst) { return nst * STAGE + PLANES; }
 };
 
@@ -529,6 +542,47 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
                     }
                 }
             }
+        } else if (T == T_Q3_K) {
+            // (1) decode: wave w of row tile wr turns spans 2w, 2w + 1 of its superblock into the int8
+            //     operands -q (sc6 - 32) of every lane's row (q3k_span), once per row tile;
+            // (2) one MFMA per span; S = -acc, y = fmaf(d_x d_y, S, y)
+            const lchar* wt = stg + wr * C::SLOT;
+            lchar* pl = (lchar*)(smem + NST * C::STAGE) + wr * (8 * 1024) + lane * 16;
+            const u32x4 hd = lds_ld<u32x4>(wt + 3072 + col * 16);
+            {
+                const u32x4 wq = lds_ld<u32x4>(wt + (w >> 1) * 1024 + lane * 16);
+                const u32x4 hm = lds_ld<u32x4>(wt + 2048 + lane * 16);
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (2 * w) * 1024) = q3k_span(wq, hm, hd, 2 * w, h);
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (2 * w + 1) * 1024) = q3k_span(wq, hm, hd, 2 * w + 1, h);
+                __builtin_amdgcn_s_waitcnt((0xF) | (0x3 << 14) | (0x7 << 4));   // lgkmcnt(0): operands written
+                __builtin_amdgcn_s_barrier();
+            }
+            if (busy) {
+                constexpr int r = 0;
+                v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                v4i av[8], bv[8];   // operands read first (counted LDS waits)
+#pragma unroll
+                for (int sp = 0; sp < 8; ++sp) {
+                    av[sp] = lds_ld<v4i>(A0 + sp * 1024);
+                    bv[sp] = lds_ld<v4i>((const lchar*)pl + sp * 1024);
+                }
+#pragma unroll
+                for (int sp = 0; sp < 8; ++sp) {
+                    if (NST == 2) {
+                        pin(av[sp]);
+                        pin(bv[sp]);
+                    }
+                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[sp], bv[sp], acc, 0, 0, 0);
+                }
+                const float dr = h2f(hd.w);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 dx4 = lds_ld<f32x4>(dTw + 32 * g);
+                    const float dx[4] = {dx4.x, dx4.y, dx4.z, dx4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[r][4 * g + i] = fmaf(dr * dx[i], (float)(-acc[4 * g + i]), y[r][4 * g + i]);
+                }
+            }
         } else {   // Q6_K: the 8 spans of w = 64*hi + lo, each operand accumulated by the MFMA
             if (busy) {
                 constexpr int r = 0;
@@ -599,7 +653,8 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
 }  // namespace mmq
 
 bool mmq32_supported(int type) {
-    return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0 || is_legacy_quant(type);
+    return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0 || is_legacy_quant(type) ||
+           type == T_Q3_K;
 }
 
 int mmq32_tile_bytes(int type) { return mmq::mmq32_tile_bytes_d(type); }
@@ -632,6 +687,7 @@ size_t mmq2_lds(int T, int nst) {
     case T_Q4_K: return mmq::M2<T_Q4_K>::lds(nst);
     case T_Q5_K: return mmq::M2<T_Q5_K>::lds(nst);
     case T_Q6_K: return mmq::M2<T_Q6_K>::lds(nst);
+    case T_Q3_K: return mmq::M2<T_Q3_K>::lds(nst);
     default: return mmq::M2<T_Q8_0>::lds(nst);
     }
 }
@@ -686,6 +742,7 @@ Mmq2Fn mmq2_fn(const MmqPlan& k) {
     case T_Q4_K: return mmq2_fn_t<T_Q4_K>(k);
     case T_Q5_K: return mmq2_fn_t<T_Q5_K>(k);
     case T_Q6_K: return mmq2_fn_t<T_Q6_K>(k);
+    case T_Q3_K: return mmq2_fn_t<T_Q3_K>(k);
     case T_Q8_0: return mmq2_fn_t<T_Q8_0>(k);
     default: return nullptr;
     }
@@ -705,7 +762,7 @@ int mmq_n_cu() {
 // Once per device (init_gemm_attributes): the LDS limit of every instantiation a plan can name, and
 // the device's CU count for the plans of its launches.
 void init_mmq2_attributes() {
-    for (int T : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
+    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
         for (int nst : {1, 2})
             for (int v = 0; v < 5; ++v) {   // plain, pair, pre, pair + pre, gx
                 MmqPlan k{};

@@ -109,8 +109,15 @@ __device__ __forceinline__ v16i mfma(v4i a, v4i b) {
 //   Q4_0 / Q5_0  the Q8_0 tile of the same blocks: every block is the Q8_0 block with the same d and
 //         qs[i] = the signed weight (q - 8, q - 16), expanded to int8 once when the copy is built, so
 //         the GEMMs run their Q8_0 form on it (mmq_op_type) with the same exact int32 sums          8704 B
+//   Q3_K  [p 2][lane 64][16] qs bytes 32p + 16h.. | [lane 64][16] hmask bytes 16h.. | [c 32][16]
+//         header {scales[12], f16 d, pad}                                                     3584 B
+//         A 32-element span sp (elements 32 sp + 16 h..: half p = sp >> 2, 2-bit field sp & 3) holds
+//         two 16-element scale groups, one per k-half, so the scale is folded into the operand; the
+//         scaled weight q (sc6 - 32) reaches +128, so the kernels decode the NEGATED one,
+//         -q (sc6 - 32) in -128..+124, into an int8 operand (q3k_span): one MFMA per span, the
+//         exact int32 sum is minus the accumulator, taken back in the float update
 __host__ __device__ constexpr int mmq32_tile_bytes_d(int type) {
-    return type == T_Q4_K ? 4608 : type == T_Q5_K ? 5632 : type == T_Q6_K ? 16448
+    return type == T_Q4_K ? 4608 : type == T_Q5_K ? 5632 : type == T_Q6_K ? 16448 : type == T_Q3_K ? 3584
          : (type == T_Q8_0 || type == T_Q4_0 || type == T_Q5_0) ? 8704 : 0;
 }
 // the operand format of a type's MFMA-order copy: the kernels' template type
@@ -140,6 +147,30 @@ __device__ __forceinline__ unsigned bmul(unsigned x, unsigned s) {
     unsigned o;
     __builtin_memcpy(&o, &r, 4);
     return o;
+}
+// Q3_K: sc6 - 32 of scale group g (0..15) from the header {scales[12], d}: the low nibble is in
+// byte g & 7 (nibble g >> 3), the top two bits in byte 8 + (g & 3) at bit 2 (g >> 2)
+__device__ __forceinline__ int q3k_scale(const u32x4 hd, int g) {
+    const unsigned lo = (((g & 4) ? hd.y : hd.x) >> (8 * (g & 3) + ((g & 8) ? 4 : 0))) & 0xFu;
+    return (int)(lo | (((hd.z >> (8 * (g & 3) + 2 * (g >> 2))) & 3u) << 4)) - 32;
+}
+// Q3_K: the int8 MFMA operand of span sp for this lane's row and k-half h: elements 32 sp + 16 h ..
+// + 15 as -(q)(sc6 - 32).  qs: the lane's piece sp >> 2 of the 2-bit plane, hm: its mask bytes.
+// q + 4 = field | mask bit << 2 in 0..7; (q + 4) n - 4 n with n = -(sc6 - 32) is formed modulo 256
+// in 16-bit lanes (7 * 255 + 255 < 2^16: no carry between elements), and the result fits int8.
+__device__ __forceinline__ v4i q3k_span(const u32x4 qs, const u32x4 hm, const u32x4 hd, int sp, int h) {
+    const int n = -q3k_scale(hd, 2 * sp + h);
+    const unsigned m = (unsigned)n & 0xFFu, b = ((unsigned)(-4 * n) & 0xFFu) * 0x00010001u;
+    const unsigned Q[4] = {qs.x, qs.y, qs.z, qs.w}, H[4] = {hm.x, hm.y, hm.z, hm.w};
+    const int fs = 2 * (sp & 3), ms = 4 * (sp >> 2) + (sp & 3);
+    unsigned o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned q7 = ((Q[i] >> fs) & 0x03030303u) | (((H[i] >> ms) << 2) & 0x04040404u);
+        const unsigned m02 = wmul16(q7 & 0x00FF00FFu, m) + b, m13 = wmul16((q7 >> 8) & 0x00FF00FFu, m) + b;
+        o[i] = (m02 & 0x00FF00FFu) | ((m13 & 0x00FF00FFu) << 8);
+    }
+    return v4i{(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
 }
 template <typename V>
 __device__ __forceinline__ V lds_ld(const lchar* p) { return *reinterpret_cast<const __attribute__((address_space(3))) V*>(p); }

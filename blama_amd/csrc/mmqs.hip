@@ -66,6 +66,7 @@ template <int T> struct MsT;
 template <> struct MsT<T_Q4_K> { static constexpr int NV = 5, D = 4; };    // qs [4] | header
 template <> struct MsT<T_Q5_K> { static constexpr int NV = 6, D = 4; };    // qs [4] | qh | header
 template <> struct MsT<T_Q6_K> { static constexpr int NV = 16, D = 2; };   // hi [8] | lo [8] (+ d)
+template <> struct MsT<T_Q3_K> { static constexpr int NV = 4, D = 4; };    // qs [2] | hmask | header
 template <> struct MsT<T_Q8_0> { static constexpr int NV = 9, D = 2; };    // qs [8] | d [8 x f16]
 template <int T> struct MsW {
     u32x4 v[MsT<T>::NV];
@@ -81,6 +82,12 @@ __device__ __forceinline__ MsW<T> ms_load(const uint8_t* tile, int lane) {
         for (int p = 0; p < 4; ++p) w.v[p] = ld(p * 1024 + lane * 16);
         if (T == T_Q5_K) w.v[4] = ld(4096 + lane * 16);
         w.v[MsT<T>::NV - 1] = ld((T == T_Q5_K ? 5120 : 4096) + col * 16);
+        w.d6 = 0;
+    } else if (T == T_Q3_K) {
+        w.v[0] = ld(lane * 16);
+        w.v[1] = ld(1024 + lane * 16);
+        w.v[2] = ld(2048 + lane * 16);
+        w.v[3] = ld(3072 + col * 16);
         w.d6 = 0;
     } else if (T == T_Q6_K) {
 #pragma unroll
@@ -181,6 +188,30 @@ __device__ __forceinline__ void ms_sb(const MsW<T>& w, int s, const char* lds, i
                 }
             }
         }
+    } else if (T == T_Q3_K) {   // one MFMA per span on -q (sc6 - 32) (q3k_span); S = -(the two chains)
+        const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        v16i acc[2][NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[0][t] = acc[1][t] = z;
+#pragma unroll
+        for (int sp = 0; sp < 8; ++sp) {
+            const v4i b = q3k_span(w.v[sp >> 2], w.v[2], w.v[3], sp, h);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[sp & 1][t] = mfma_acc(act(t, sp), b, acc[sp & 1][t]);
+        }
+        const float dr = h2f(w.v[3].w);
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 d4 = dx4(DB + s * 256 + (t * 32 + 8 * g + 4 * h) * 4);
+                const float dx[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = 4 * g + i;
+                    y[t][e] = fmaf(dr * dx[i], (float)(-(acc[0][t][e] + acc[1][t][e])), y[t][e]);
+                }
+            }
     } else if (T == T_Q6_K) {
         const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         v16i ah[2][NT], al[2][NT];   // [sp & 1]: four independent MFMA chains per token tile
@@ -414,6 +445,17 @@ __device__ __forceinline__ void ms1_sb(const MsW<T>& w, const MsAct& A, int lane
                 y[e] = fmaf(-dm, (float)(64 * x1[e] + x2[e]), fmaf(d, (float)S, y[e]));
             }
         }
+    } else if (T == T_Q3_K) {
+        v16i acc = z;
+#pragma unroll
+        for (int sp = 0; sp < 8; ++sp) acc = mfma_acc(A.a[sp], q3k_span(w.v[sp >> 2], w.v[2], w.v[3], sp, h), acc);
+        const float dr = h2f(w.v[3].w);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float dx[4] = {A.dx[g].x, A.dx[g].y, A.dx[g].z, A.dx[g].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) y[4 * g + i] = fmaf(dr * dx[i], (float)(-acc[4 * g + i]), y[4 * g + i]);
+        }
     } else {   // Q6_K
         v16i ah = z, al = z;
 #pragma unroll
@@ -587,6 +629,10 @@ MmqsFn mmqs_fn_t(const MmqPlan& k) {
         if (k.grouped) return k.pair ? mmq::mmqs1_lean_t<T, true, true> : mmq::mmqs1_lean_t<T, false, true>;
         return k.pair ? mmq::mmqs1_lean_t<T, true, false> : mmq::mmqs1_lean_t<T, false, false>;
     }
+    if constexpr (T == T_Q3_K) {   // (dense models only: no grouped form)
+        if (k.kernel != MK_SHORT1_LEAN || k.grouped) return nullptr;
+        return k.pair ? mmq::mmqs1_lean_t<T, true, false> : mmq::mmqs1_lean_t<T, false, false>;
+    }
     if constexpr (T == T_Q6_K) {
         if (k.kernel != MK_SHORT1) return nullptr;
         if (k.grouped) return k.pair ? mmq::mmqs1_t<T, true, true> : mmq::mmqs1_t<T, false, true>;
@@ -600,6 +646,7 @@ MmqsFn mmqs_fn(const MmqPlan& k) {
     case T_Q4_K: return mmqs_fn_t<T_Q4_K>(k);
     case T_Q5_K: return mmqs_fn_t<T_Q5_K>(k);
     case T_Q6_K: return mmqs_fn_t<T_Q6_K>(k);
+    case T_Q3_K: return mmqs_fn_t<T_Q3_K>(k);
     case T_Q8_0: return mmqs_fn_t<T_Q8_0>(k);
     default: return nullptr;
     }
@@ -623,7 +670,7 @@ void mmqs_launch(const MmqShape& sh, mmq::MsArgs& M, const ActQ8& act, float* pa
 // Once per device (init_gemm_attributes): the LDS limit of every mmqs_t instantiation a plan can name
 // (the mmqs1 kernels use no LDS).
 void init_mmqs_attributes() {
-    for (int T : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
+    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
         for (int nt : {1, 2})
             for (bool pair : {false, true}) {
                 MmqPlan k{};

@@ -81,6 +81,50 @@ void swizzle(QMat& A, const QMat* B, Keep& keep) {
     MI_HIP(hipDeviceSynchronize());
 }
 
+// The timed entry points cycle through this many copies of `bytes` of weights, so that consecutive
+// launches stream them from HBM, not from the 256 MiB Infinity Cache.
+int stream_copies(size_t bytes) { return (int)std::min<size_t>(64, std::max<size_t>(1, (768ull << 20) / bytes + 1)); }
+
+size_t planes_bytes(const QMat& m) {
+    size_t n = 0;
+    for (int k = 0; k < plane_count(m.type); ++k) n += plane_bytes(m.type, m.rows, m.K, k);
+    return n;
+}
+
+// n views of m0: m0 itself, then copies of its planes
+std::vector<QMat> plane_copies(const QMat& m0, int n, Keep& keep) {
+    std::vector<QMat> mats(n, m0);
+    for (int c = 1; c < n; ++c)
+        for (int k = 0; k < plane_count(m0.type); ++k) {
+            keep.emplace_back(plane_bytes(m0.type, m0.rows, m0.K, k));
+            keep.back().copy_device(m0.p[k]);
+            mats[c].p[k] = keep.back().p;
+        }
+    return mats;
+}
+
+// Median device time (us) of launch(i), i < iters, each between two events, after `warm` launches.
+template <class F> float median_us(int iters, int warm, F launch) {
+    hipEvent_t a, b;
+    MI_HIP(hipEventCreate(&a));
+    MI_HIP(hipEventCreate(&b));
+    std::vector<float> t;
+    for (int i = 0; i < warm; ++i) launch(i);
+    for (int i = 0; i < iters; ++i) {
+        MI_HIP(hipEventRecord(a, nullptr));
+        launch(i);
+        MI_HIP(hipEventRecord(b, nullptr));
+        MI_HIP(hipEventSynchronize(b));
+        float ms = 0;
+        MI_HIP(hipEventElapsedTime(&ms, a, b));
+        t.push_back(ms * 1000.0f);
+    }
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    std::sort(t.begin(), t.end());
+    return t.empty() ? 0.0f : t[t.size() / 2];
+}
+
 GemvParams gemv_of(int pro, const float* x, int K) {
     GemvParams p;
     std::memset(&p, 0, sizeof(p));
@@ -106,6 +150,75 @@ void check_picks(const int32_t* sel, int ntok, int n_expert) {
         if (a < 0 || a >= n_expert || b < 0 || b >= n_expert) throw Error("op_moe: expert out of range");
         if (a == b) throw Error("op_moe: a token's two picks must differ");
     }
+}
+
+// One launch of mi_op_dgemv: the role's checks, and its parameter block over a (and b).
+struct DgemvOp {
+    int role, fmt, out_rows;
+    bool addq, wide, two;
+    DgemvOp(int role_in, int type, int rows, int K, int type2, const void* raw2, int rows2, bool has_resid) {
+        if (role_in < 0 || role_in > 5) throw Error("op_dgemv: role");
+        wide = role_in == 5;
+        addq = role_in == 4 || wide;
+        role = addq ? 1 : role_in;
+        two = raw2 && rows2 > 0;
+        check_quant(type, K);
+        if (two) check_quant(type2, K);
+        if (role == 2 && (!two || type2 != type || rows2 != rows)) throw Error("op_dgemv: SwiGLU needs a pair");
+        if ((role == 1 || role == 3) && two) throw Error("op_dgemv: one matrix for this role");
+        if (role == 1 && !has_resid) throw Error("op_dgemv: residual role needs resid");
+        out_rows = role == 0 ? rows + (two ? rows2 : 0) : rows;
+        fmt = act_fmt({type, two ? type2 : type});
+    }
+    // act: x quantised by launch_dv_quant (the in-launch-quantising roles read x itself)
+    GemvParams params(const QMat& a, const QMat& b, const char* act, const float* x, const int* tokpos, const float* resid,
+                      float* y) const {
+        GemvParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.K = a.K;
+        p.act_in = addq ? nullptr : act;
+        p.x[0] = addq ? x : nullptr;
+        p.act_q8k = fmt & 1;
+        p.act_q80 = fmt >> 1;
+        p.act_wide = wide;
+        p.tokpos = tokpos;
+        p.head_dim = 128;
+        p.nseg = role == 0 && two ? 2 : 1;
+        const int epi[4] = {EPI_QKV, EPI_ADD, EPI_SWIGLU, EPI_STORE};
+        for (int s = 0; s < p.nseg; ++s) {
+            GemvSeg& g = p.seg[s];
+            g = seg_of(s == 0 ? a : b, role == 2 ? PAIR_AB : PAIR_ADJ, epi[role], y + (s == 0 ? 0 : a.rows));
+            if (role == 2) g.B = b;
+            g.nq = g.A.rows;   // Q/K/V: every row a Q row, n_rot 0 (no rotation)
+            g.resid = role == 1 ? resid : nullptr;
+        }
+        if (!dgemv_supported(p)) throw Error("op_dgemv: no compiled variant for this launch");
+        return p;
+    }
+};
+
+// mi_op_gemm's launches over an already quantised activation: up to the short-batch limit the
+// short-batch GEMM (K-part sums, added by part_sum) as the engine's verification batches take it;
+// MI_MMQS_MAX=0: the tiled GEMM for every count.
+void gemm_launches(const QMat& A, const QMat* B, int ntok, const ActQ8& act, float* part, const int* tokpos, float* y) {
+    const int rows = A.rows;
+    if (ntok > mmqs_token_limit()) {
+        launch_mmq32(mmq32_params(A, B, ntok, tokpos, y, rows), act, nullptr, nullptr);
+        return;
+    }
+    const int pst = B ? 2 * rows : rows;
+    const QMat* mats[1] = {&A};
+    const int prow[1] = {0};
+    PartSum ps{};
+    ps.kp = launch_mmqs(mats, prow, 1, B != nullptr, rows, act, part, pst, nullptr);
+    ps.part = part;
+    ps.ntok = ntok;
+    ps.rows = rows;
+    ps.pstride = pst;
+    ps.out = y;
+    ps.ostride = rows;
+    ps.swiglu = B ? rows : 0;
+    launch_part_sum(ps, nullptr);
 }
 }  // namespace
 
@@ -136,52 +249,53 @@ int32_t mi_op_gemv(int32_t device, int32_t type, const void* raw, int32_t rows, 
 int32_t mi_op_dgemv(int32_t device, int32_t role, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t type2,
                     const void* raw2, int32_t rows2, const float* x, const float* resid, float* y) {
     try {
-        if (role < 0 || role > 5) throw Error("op_dgemv: role");
-        const bool wide = role == 5;
-        const bool addq = role == 4 || wide;
-        if (addq) role = 1;
-        const bool two = raw2 && rows2 > 0;
-        check_quant(type, K);
-        if (two) check_quant(type2, K);
-        if (role == 2 && (!two || type2 != type || rows2 != rows)) throw Error("op_dgemv: SwiGLU needs a pair");
-        if ((role == 1 || role == 3) && two) throw Error("op_dgemv: one matrix for this role");
-        if (role == 1 && !resid) throw Error("op_dgemv: residual role needs resid");
+        const DgemvOp op(role, type, rows, K, type2, raw2, rows2, resid != nullptr);
         MI_HIP(hipSetDevice(device));
         ensure_kernel_attributes(device);
         Keep keep;
         const QMat a = upload_qmat(type, raw, rows, K, keep);
         QMat b{};
-        if (two) b = upload_qmat(type2, raw2, rows2, K, keep);
-        const int out_rows = role == 0 ? rows + (two ? rows2 : 0) : rows;
-        Dev<float> dx(K, x), dy(out_rows), dr(out_rows, role == 1 ? resid : nullptr);
+        if (op.two) b = upload_qmat(type2, raw2, rows2, K, keep);
+        Dev<float> dx(K, x), dy(op.out_rows), dr(op.out_rows, op.role == 1 ? resid : nullptr);
         Dev<int> dtp(4);
         dtp.fill(0);
-        const int fmt = act_fmt({type, two ? type2 : type});
-        Dev<char> act(dv_act_bytes(K, fmt & 1, fmt >> 1));
-        launch_dv_quant(dx.p, ActOut{K, fmt & 1, fmt >> 1, act.p, nullptr, 1e-5f}, nullptr);
-        GemvParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.K = K;
-        p.act_in = addq ? nullptr : act.p;
-        p.x[0] = addq ? dx.p : nullptr;
-        p.act_q8k = fmt & 1;
-        p.act_q80 = fmt >> 1;
-        p.act_wide = wide;
-        p.tokpos = dtp.p;
-        p.head_dim = 128;
-        p.nseg = role == 0 && two ? 2 : 1;
-        const int epi[4] = {EPI_QKV, EPI_ADD, EPI_SWIGLU, EPI_STORE};
-        for (int s = 0; s < p.nseg; ++s) {
-            GemvSeg& g = p.seg[s];
-            g = seg_of(s == 0 ? a : b, role == 2 ? PAIR_AB : PAIR_ADJ, epi[role], dy.p + (s == 0 ? 0 : rows));
-            if (role == 2) g.B = b;
-            g.nq = g.A.rows;   // Q/K/V: every row a Q row, n_rot 0 (no rotation)
-            g.resid = role == 1 ? dr.p : nullptr;
-        }
-        if (!dgemv_supported(p)) throw Error("op_dgemv: no compiled variant for this launch");
-        launch_dgemv(p, nullptr);
+        Dev<char> act(dv_act_bytes(K, op.fmt & 1, op.fmt >> 1));
+        launch_dv_quant(dx.p, ActOut{K, op.fmt & 1, op.fmt >> 1, act.p, nullptr, 1e-5f}, nullptr);
+        launch_dgemv(op.params(a, b, act.p, dx.p, dtp.p, dr.p, dy.p), nullptr);
         MI_HIP(hipDeviceSynchronize());
         dy.download(y);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// Median device time (us) of mi_op_dgemv's launch of `role` (x already quantised, but for roles 4
+// and 5), over `iters` launches after a warm-up, each reading another copy of the planes.
+int32_t mi_op_dgemv_bench(int32_t device, int32_t role, int32_t type, const void* raw, int32_t rows, int32_t K,
+                          int32_t type2, const void* raw2, int32_t rows2, int32_t iters, float* median_us_out) {
+    try {
+        const DgemvOp op(role, type, rows, K, type2, raw2, rows2, true);
+        if (iters < 1 || !median_us_out) throw Error("op_dgemv_bench: arguments");
+        MI_HIP(hipSetDevice(device));
+        ensure_kernel_attributes(device);
+        Keep keep;
+        const QMat a0 = upload_qmat(type, raw, rows, K, keep);
+        QMat b0{};
+        if (op.two) b0 = upload_qmat(type2, raw2, rows2, K, keep);
+        const int copies = stream_copies(planes_bytes(a0) + (op.two ? planes_bytes(b0) : 0));
+        const std::vector<QMat> a = plane_copies(a0, copies, keep);
+        const std::vector<QMat> b = op.two ? plane_copies(b0, copies, keep) : std::vector<QMat>(copies, b0);
+        std::vector<float> hx(K);
+        for (int i = 0; i < K; ++i) hx[i] = 0.5f + 0.001f * (float)(i % 97);
+        Dev<float> dx(K, hx.data()), dy(op.out_rows), dr(op.out_rows);
+        dr.fill(0);
+        Dev<int> dtp(4);
+        dtp.fill(0);
+        Dev<char> act(dv_act_bytes(K, op.fmt & 1, op.fmt >> 1));
+        launch_dv_quant(dx.p, ActOut{K, op.fmt & 1, op.fmt >> 1, act.p, nullptr, 1e-5f}, nullptr);
+        *median_us_out = median_us(iters, copies + 2, [&](int i) {
+            launch_dgemv(op.params(a[i % copies], b[i % copies], act.p, dx.p, dtp.p, dr.p, dy.p), nullptr);
+        });
         return 0;
     }
     MI_TRY(-1)
@@ -304,46 +418,19 @@ int32_t mi_op_fgemv_bench(int32_t device, int32_t role, int32_t rows, int32_t K,
 }
 
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t iters,
-                         float* median_us) {
+                         float* median_us_out) {
     try {
         check_quant(type, K);
         MI_HIP(hipSetDevice(device));
         ensure_kernel_attributes(device);
         Keep keep;
         const QMat m0 = upload_qmat(type, raw, rows, K, keep);
-        // enough copies that consecutive launches stream from HBM, not the 256 MiB Infinity Cache
-        size_t mbytes = 0;
-        for (int k = 0; k < plane_count(type); ++k) mbytes += plane_bytes(type, rows, K, k);
-        const int copies = (int)std::min<size_t>(64, std::max<size_t>(1, (768ull << 20) / mbytes + 1));
-        std::vector<QMat> mats(copies, m0);
-        for (int c = 1; c < copies; ++c)
-            for (int k = 0; k < plane_count(type); ++k) {
-                keep.emplace_back(plane_bytes(type, rows, K, k));
-                keep.back().copy_device(m0.p[k]);
-                mats[c].p[k] = keep.back().p;
-            }
+        const int copies = stream_copies(planes_bytes(m0));
+        const std::vector<QMat> mats = plane_copies(m0, copies, keep);
         std::vector<float> hx(K);
         for (int i = 0; i < K; ++i) hx[i] = 0.5f + 0.001f * (float)(i % 97);
         Dev<float> dx(K, hx.data()), dy(rows);
-        hipEvent_t a, b;
-        MI_HIP(hipEventCreate(&a));
-        MI_HIP(hipEventCreate(&b));
-        std::vector<float> t;
-        for (int i = 0; i < copies + 2; ++i) launch_gemv(single_gemv(mats[i % copies], dx.p, dy.p), nullptr);
-        for (int i = 0; i < iters; ++i) {
-            const GemvParams p = single_gemv(mats[i % copies], dx.p, dy.p);
-            MI_HIP(hipEventRecord(a, nullptr));
-            launch_gemv(p, nullptr);
-            MI_HIP(hipEventRecord(b, nullptr));
-            MI_HIP(hipEventSynchronize(b));
-            float ms = 0;
-            MI_HIP(hipEventElapsedTime(&ms, a, b));
-            t.push_back(ms * 1000.0f);
-        }
-        hipEventDestroy(a);
-        hipEventDestroy(b);
-        std::sort(t.begin(), t.end());
-        *median_us = t.empty() ? 0.0f : t[t.size() / 2];
+        *median_us_out = median_us(iters, copies + 2, [&](int i) { launch_gemv(single_gemv(mats[i % copies], dx.p, dy.p), nullptr); });
         return 0;
     }
     MI_TRY(-1)
@@ -633,12 +720,15 @@ int32_t mi_op_attention_short(int32_t device, int32_t n_head, int32_t n_head_kv,
     MI_TRY(-1)
 }
 
-int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
-                   int32_t ntok, const float* x, float* y) {
+// mi_op_gemm, or with median_us_out its timed form: x absent, the launches after the activation's
+// quantisation timed over `iters` calls, each reading another MFMA-order copy of the matrices.
+static int32_t op_gemm(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
+                       int32_t ntok, const float* x, float* y, int32_t iters, float* median_us_out) {
     try {
-        if (!mmq32_supported(type)) throw Error("op_gemm: Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
+        if (!mmq32_supported(type)) throw Error("op_gemm: Q3_K / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
         if (ntok < 1 || ntok > UB_MAX) throw Error("op_gemm: 1..512 token rows");
         if (rows < 1 || K < 256 || K % 256) throw Error("op_gemm: bad shape");
+        if (median_us_out && iters < 1) throw Error("op_gemm_bench: iters");
         MI_HIP(hipSetDevice(device));
         ensure_kernel_attributes(device);
         Keep keep;
@@ -646,9 +736,18 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
         QMat B = A;
         const bool pair = raw_up != nullptr;
         if (pair) B = upload_qmat(type, raw_up, rows, K, keep);
-        swizzle(A, pair ? &B : nullptr, keep);
+        const int copies = median_us_out ? stream_copies(mmq32_copy_bytes(A, pair)) : 1;
+        std::vector<QMat> As(copies, A);
+        for (QMat& a : As) swizzle(a, pair ? &B : nullptr, keep);
         const size_t npad = (size_t)(ntok + 31) / 32 * 32;
+        std::vector<float> hx;
+        if (median_us_out) {
+            hx.resize((size_t)ntok * K);
+            for (size_t i = 0; i < hx.size(); ++i) hx[i] = 0.5f - 0.01f * (float)(i % 97);
+            x = hx.data();
+        }
         Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows), ddT(npad * (K / 32));
+        Dev<float> part(ntok <= mmqs_token_limit() ? (size_t)mmqs_parts(K) * ntok * (pair ? 2 * rows : rows) : 1);
         Dev<int8_t> dq(npad * K), dbs(npad * (K / 256) * 16);
         Dev<int> dtp((size_t)ntok * 4);
         dtp.fill(0);
@@ -657,33 +756,28 @@ int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* ra
         qa.x = dx.p;
         qa.x_stride = K;
         launch_quant_act(qa, act, nullptr);
-        // up to the short-batch limit: the short-batch GEMM (K-part sums, added by part_sum) as the
-        // engine's verification batches take it; MI_MMQS_MAX=0: the tiled GEMM for every count
-        if (ntok <= mmqs_token_limit()) {
-            const int pst = pair ? 2 * rows : rows;
-            Dev<float> part((size_t)mmqs_parts(K) * ntok * pst);
-            const QMat* mats[1] = {&A};
-            const int prow[1] = {0};
-            const int kp = launch_mmqs(mats, prow, 1, pair, rows, act, part.p, pst, nullptr);
-            PartSum ps{};
-            ps.part = part.p;
-            ps.kp = kp;
-            ps.ntok = ntok;
-            ps.rows = rows;
-            ps.pstride = pst;
-            ps.out = dy.p;
-            ps.ostride = rows;
-            ps.swiglu = pair ? rows : 0;
-            launch_part_sum(ps, nullptr);
-            MI_HIP(hipDeviceSynchronize());
-        } else {
-            launch_mmq32(mmq32_params(A, pair ? &B : nullptr, ntok, dtp.p, dy.p, rows), act, nullptr, nullptr);
+        auto launch = [&](int i) { gemm_launches(As[i % copies], pair ? &B : nullptr, ntok, act, part.p, dtp.p, dy.p); };
+        if (median_us_out) {
+            *median_us_out = median_us(iters, copies + 2, launch);
+            return 0;
         }
+        launch(0);
         MI_HIP(hipDeviceSynchronize());
         dy.download(y);
         return 0;
     }
     MI_TRY(-1)
+}
+
+int32_t mi_op_gemm(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
+                   int32_t ntok, const float* x, float* y) {
+    return op_gemm(device, type, raw, raw_up, rows, K, ntok, x, y, 0, nullptr);
+}
+
+int32_t mi_op_gemm_bench(int32_t device, int32_t type, const void* raw, const void* raw_up, int32_t rows, int32_t K,
+                         int32_t ntok, int32_t iters, float* median_us_out) {
+    if (!median_us_out) return -1;
+    return op_gemm(device, type, raw, raw_up, rows, K, ntok, nullptr, nullptr, iters, median_us_out);
 }
 
 int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t rows, int32_t K, int32_t ntok,
@@ -835,7 +929,7 @@ int32_t mi_op_moe_gemm(int32_t device, int32_t mode, int32_t type, const void* r
     try {
         if (!raw || !x || !sel || !y) throw Error("op_moe_gemm: null argument");
         if (mode != 0 && mode != 1) throw Error("op_moe_gemm: mode 0 (tiled) or 1 (short)");
-        if (!mmq32_supported(type) || is_legacy_quant(type)) throw Error("op_moe_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
+        if (!mmq32_supported(type) || is_legacy_quant(type) || type == T_Q3_K) throw Error("op_moe_gemm: Q4_K / Q5_K / Q6_K / Q8_0 only");
         if (mode == 1 && !mmqs_grouped_supported(type)) throw Error("op_moe_gemm: the short form takes Q4_K / Q5_K / Q6_K experts");
         if (ntok < 1 || ntok > (mode == 1 ? MMQS_MAX : UB_MAX)) throw Error("op_moe_gemm: 1..512 tokens (short form: 1..64)");
         if (n_expert < 2 || n_expert > MOE_GROUP_MAXE) throw Error("op_moe_gemm: 2..16 experts");
@@ -910,7 +1004,7 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
                          const int32_t* sel, const float* selw, const float* addend, float* h_out, float* x_out) {
     try {
         if (!gate || !up || !down || !x || !norm_w || !sel || !selw || !h_out || !x_out) throw Error("op_moe_decode: null argument");
-        if (!is_quant(type) || is_legacy_quant(type)) throw Error("op_moe_decode: unsupported quant type");
+        if (!is_quant(type) || is_legacy_quant(type) || type == T_Q3_K) throw Error("op_moe_decode: unsupported quant type");
         if (n_expert < 1 || n_embd < 256 || n_embd % 256 || n_ff < 256 || n_ff % 256) throw Error("op_moe_decode: bad shape");
         for (int k = 0; k < 2; ++k)
             if (sel[k] < 0 || sel[k] >= n_expert) throw Error("op_moe_decode: expert out of range");

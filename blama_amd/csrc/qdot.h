@@ -548,6 +548,91 @@ template <> struct Kq<T_Q5_0> {
     }
 };
 
+// Q3_K (vec_dot_q3_K_q8_K): 2-bit plane qs, third-bit mask hmask, sixteen 6-bit scales in 12 bytes.
+// The kernels give a superblock 8 lanes; the 64-byte qs plane has four 16-byte pieces, so lanes 2c
+// and 2c + 1 read piece c (one request per line) and split its four 2-bit fields: lane j = 2c + sp
+// owns the shifts 2 sp and 2 sp + 1.  With n = j >> 2 (the 128-weight half) and lh = (j >> 1) & 1
+// (mask bytes 16 lh..) that is 32 weights, 128 n + 64 sp + 16 lh.. and the 16 that follow 32 further
+// on: the scale groups g0 = 8 n + 4 sp + lh and g0 + 2, the AR of two 16-byte runs 32 bytes apart.
+// Both fields come out of whole dwords pre-shifted by a per-lane amount: q + 4 = (Q & 3) | mask bit
+// << 2 in 0..7, and sum(q a) = sum((q + 4) a) - 4 bsum exactly, as Q6_K takes its - 32.  The scale
+// bytes of g0 and g0 + 2 are bytes lh and lh + 2 of one header dword (x for sp 0, y for sp 1; nibble
+// n) and their top bits bytes lh and lh + 2 of dword z at bit 2 (2 n + sp): shifts that depend on
+// the lane only, no branch (ScaleSel).  |dot - 4 bsum| <= 16 * 4 * 127 and |scale| <= 32: 24-bit
+// multiplies are exact.
+template <> struct PlaneBytes<T_Q3_K> { static constexpr int b[4] = {64, 32, 16, 0}; };
+template <> struct Kq<T_Q3_K> {
+    static constexpr int LPS = 8;
+    struct Ld { u32x4 qs, hm, hdr; };
+    __device__ static Ld load(const uint8_t* const* rp, int sb, int j) {
+        Ld l;
+        l.qs = ldg16(rp[0] + sb * 64 + (j >> 1) * 16);
+        l.hm = ldg16(rp[1] + sb * 32 + ((j >> 1) & 1) * 16);
+        l.hdr = ldg16(rp[2] + sb * 16);
+        return l;
+    }
+    __device__ static Ld bload(const uint8_t* const* rp, int sb, int j, bool park) {
+        Ld l;
+        l.qs = bld16(rp[0], oob(sb * 64 + (j >> 1) * 16, park));
+        l.hm = bld16(rp[1], oob(sb * 32 + ((j >> 1) & 1) * 16, park));
+        l.hdr = bld16(rp[2], oob(sb * 16, park));
+        return l;
+    }
+    using AR = Kq<T_Q6_K>::AR;
+    __device__ static AR act(const Act& a, int sb, int j) {
+        const int n = j >> 2, lh = (j >> 1) & 1, sp = j & 1;
+        const int8_t* ab = a.q8k + sb * 256 + 128 * n + 64 * sp + 16 * lh;
+        const int g0 = 8 * n + 4 * sp + lh;
+        AR r;
+        r.alo = *reinterpret_cast<const i32x4*>(ab);
+        r.ahi = *reinterpret_cast<const i32x4*>(ab + 32);
+        r.bs_lo = a.bsum[sb * 16 + g0];
+        r.bs_hi = a.bsum[sb * 16 + g0 + 2];
+        r.dx = a.dk[sb];
+        return r;
+    }
+    struct ScaleSel {
+        unsigned qsh, hsh, lsh, tsh;
+        bool hi;
+        __device__ explicit ScaleSel(int j) {
+            const unsigned n = j >> 2, lh = (j >> 1) & 1, sp = j & 1;
+            qsh = 4 * sp;               // the lane's two 2-bit fields of every qs byte
+            hsh = 4 * n + 2 * sp;       // ... and their two mask bits
+            lsh = 8 * lh + 4 * n;       // low nibbles: scales[4 sp + lh] and [.. + 2], nibble n
+            tsh = 8 * lh + 4 * n + 2 * sp;   // top bits: scales[8 + lh] and [10 + lh], bits 2 (2 n + sp)..
+            hi = sp != 0;
+        }
+    };
+    __device__ static float dot(const Ld& l, const AR& r, int j) {
+        const ScaleSel q(j);
+        const i32x4 alo = r.alo, ahi = r.ahi;
+        int dlo = 0, dhi = 0;
+#define Q3L(c) (((l.qs.c >> q.qsh) & 0x03030303u) | (((l.hm.c >> q.hsh) << 2) & 0x04040404u))
+#define Q3H(c) (((l.qs.c >> (q.qsh + 2)) & 0x03030303u) | (((l.hm.c >> q.hsh) << 1) & 0x04040404u))
+        dlo = dot4((int)Q3L(x), alo.x, dlo);
+        dlo = dot4((int)Q3L(y), alo.y, dlo);
+        dlo = dot4((int)Q3L(z), alo.z, dlo);
+        dlo = dot4((int)Q3L(w), alo.w, dlo);
+        dhi = dot4((int)Q3H(x), ahi.x, dhi);
+        dhi = dot4((int)Q3H(y), ahi.y, dhi);
+        dhi = dot4((int)Q3H(z), ahi.z, dhi);
+        dhi = dot4((int)Q3H(w), ahi.w, dhi);
+#undef Q3L
+#undef Q3H
+        const unsigned lo4 = ((q.hi ? l.hdr.y : l.hdr.x) >> q.lsh) & 0x000F000Fu;
+        const unsigned sc = lo4 | (((l.hdr.z >> q.tsh) & 0x00030003u) << 4);
+        int S = __mul24((int)(sc & 0xFF) - 32, dlo - 4 * r.bs_lo) +
+                __mul24((int)(sc >> 16) - 32, dhi - 4 * r.bs_hi);
+        // the superblock's integer sum over its 8 lanes (|S| <= 256 * 4 * 128 * 32 < 2^24), so that
+        // it meets d * d8 in one product as in vec_dot_q3_K_q8_K: lane 0 of the 8 carries it
+        S += dpp_i<0xB1, 0xf>(S);    // quad_perm [1,0,3,2]
+        S += dpp_i<0x4E, 0xf>(S);    // quad_perm [2,3,0,1]
+        S += dpp_i<0x141, 0xf>(S);   // row_half_mirror: the other quad of the 8
+        const float d = h2f(l.hdr.w) * r.dx;
+        return (j & 7) == 0 ? d * (float)S : 0.0f;
+    }
+};
+
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 
 // every storing wave, before its workgroup signals a hand-off (invisible to the compiler's waits)

@@ -128,6 +128,10 @@ _SIGS = {
     "mi_op_attention_short": (C.c_int32, [C.c_int32] * 6 + [_P] * 6 + [C.c_int32] + [_P] * 4),
     "mi_op_gemv_bench": (C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_float)]),
+    "mi_op_dgemv_bench": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P,
+                                      C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    "mi_op_gemm_bench": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_float)]),
     "mi_op_gemm": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_attention_batch": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           _P, _P, _P, _P, _P, _P, _P]),
@@ -561,6 +565,24 @@ def op_gemv_bench(type_: int, raw: np.ndarray, rows: int, K: int, iters: int = 1
     raw = np.ascontiguousarray(raw, np.uint8)
     us = C.c_float()
     _check(lib().mi_op_gemv_bench(device, type_, _ptr(raw), rows, K, iters, C.byref(us)), "op_gemv_bench")
+    return us.value
+
+
+def op_dgemv_bench(role: int, type_: int, raw: np.ndarray, rows: int, K: int, type2: int = -1, raw2=None,
+                   rows2: int = 0, iters: int = 100, device: int = 0) -> float:
+    """Median microseconds of mi_op_dgemv's launch of `role`, each launch on another copy of the planes."""
+    us = C.c_float()
+    _check(lib().mi_op_dgemv_bench(device, role, type_, _ptr(raw), rows, K, type2, None if raw2 is None else _ptr(raw2),
+                                   rows2 if raw2 is not None else 0, iters, C.byref(us)), "op_dgemv_bench")
+    return us.value
+
+
+def op_gemm_bench(type_: int, raw: np.ndarray, rows: int, K: int, ntok: int, raw_up=None, iters: int = 100,
+                  device: int = 0) -> float:
+    """Median microseconds of mi_op_gemm's launches over ntok rows (quantising the activation not included)."""
+    us = C.c_float()
+    _check(lib().mi_op_gemm_bench(device, type_, _ptr(raw), None if raw_up is None else _ptr(raw_up), rows, K, ntok,
+                                  iters, C.byref(us)), "op_gemm_bench")
     return us.value
 
 

@@ -24,6 +24,7 @@ from . import gguf
 
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
 Q4_0, Q5_0 = 2, 6
+Q3_K = 11
 
 
 @dataclass(frozen=True)
@@ -132,6 +133,20 @@ LEGACY_CONFIGS = {
     "tinyllama-1.1b-q5_0": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q5_0"),
 }
 
+# llama-quantize's Q3_K_S / Q3_K_M files (general.file_type 11 / 12): Q3_K matrices with a Q6_K head;
+# _M keeps attn_v, attn_output and part of ffn_down at Q4_K / Q5_K (tensor_types).  A table of their
+# own, as LEGACY_CONFIGS: heads of 64 (the streaming decode step) and of 32 (the gemv_kernel step).
+# Four layers, so that the _M mix has both attn_v types and a Q3_K ffn_down.
+Q3K_CONFIGS = {
+    "tiny-q3_k_s": LlamaConfig("tiny-q3_k_s", 512, 256, 4, 4, 2, 512, 256, 10000.0, 1e-5, "Q3_K_S"),
+    "tiny-q3_k_m": LlamaConfig("tiny-q3_k_m", 512, 256, 4, 4, 2, 512, 256, 10000.0, 1e-5, "Q3_K_M"),
+    "tiny-hd32-q3_k_s": LlamaConfig("tiny-hd32-q3_k_s", 384, 256, 2, 8, 4, 768, 256, 10000.0, 1e-6, "Q3_K_S"),
+    "tiny-hd32-q3_k_m": LlamaConfig("tiny-hd32-q3_k_m", 384, 256, 2, 8, 4, 768, 256, 10000.0, 1e-6, "Q3_K_M"),
+    # benchmark shapes (scripts/q3_k_bench.py)
+    "tinyllama-1.1b-q3_k_s": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q3_K_S"),
+    "tinyllama-1.1b-q4_k": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q4_K"),
+}
+
 
 def use_more_bits(i: int, n: int) -> bool:
     # llama-quant.cpp use_more_bits
@@ -178,7 +193,7 @@ def _gpt2_shapes(cfg) -> dict:
 def tensor_types(cfg: LlamaConfig) -> dict:
     """name -> ggml type for every weight (the Q*_K_M mixes of llama_tensor_get_type)."""
     base = {"Q4_K_M": Q4_K, "Q5_K_M": Q5_K, "Q6_K": Q6_K, "Q8_0": Q8_0, "Q4_K": Q4_K,
-            "Q5_K": Q5_K, "F16": F16, "Q4_0": Q4_0, "Q5_0": Q5_0}[cfg.ftype]
+            "Q5_K": Q5_K, "F16": F16, "Q4_0": Q4_0, "Q5_0": Q5_0, "Q3_K_S": Q3_K, "Q3_K_M": Q3_K}[cfg.ftype]
     if cfg.arch == "gpt2":
         return _gpt2_types(cfg, base)
     if base == F16:   # the unquantised file convert_hf_to_gguf writes: every matrix F16, the rest F32
@@ -206,6 +221,10 @@ def tensor_types(cfg: LlamaConfig) -> dict:
             if cfg.ftype == "Q4_K_M":
                 t[p + "attn_output.weight"] = Q5_K
         down = Q6_K if (mixed and use_more_bits(i, n)) else base
+        if cfg.ftype == "Q3_K_M":   # llama_tensor_get_type, LLAMA_FTYPE_MOSTLY_Q3_K_M
+            t[p + "attn_v.weight"] = Q5_K if i < 2 else Q4_K
+            t[p + "attn_output.weight"] = Q4_K
+            down = Q5_K if i < n // 16 else Q4_K if use_more_bits(i, n) else Q3_K
         if cfg.n_expert:
             t[p + "ffn_gate_inp.weight"] = F32
             t[p + "ffn_gate_exps.weight"] = base
@@ -268,6 +287,16 @@ def _pack_scales_k4(sc: np.ndarray, m: np.ndarray) -> np.ndarray:
     return s
 
 
+def _pack_scales_q3(sc6: np.ndarray) -> np.ndarray:
+    """(n, 16) 6-bit scales -> block_q3_K's scales[12]: the low nibbles of scales 0..7 / 8..15 in the
+    low / high nibbles of bytes 0..7, the top two bits of scale s in byte 8 + (s & 3) at bit 2 (s >> 2)."""
+    s = np.zeros((sc6.shape[0], 12), np.uint8)
+    for g in range(16):
+        s[:, g & 7] |= ((sc6[:, g] & 0xF) << (4 * (g >> 3))).astype(np.uint8)
+        s[:, 8 + (g & 3)] |= ((sc6[:, g] >> 4) << (2 * (g >> 2))).astype(np.uint8)
+    return s
+
+
 def fill_quant(view: np.ndarray, t: int, rng, std: float = 0.03):
     """Fill a tensor's bytes with valid random blocks whose dequantised values
     are roughly zero-mean with standard deviation ``std``."""
@@ -309,6 +338,12 @@ def fill_quant(view: np.ndarray, t: int, rng, std: float = 0.03):
         elif t in (Q4_0, Q5_0):   # uniform 4- / 5-bit values around 8 / 16: std = d * levels / sqrt(12)
             d = (std / ((16 if t == Q4_0 else 32) / np.sqrt(12.0))) * rng.uniform(0.8, 1.2, n)
             b[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
+        elif t == Q3_K:   # uniform q in -4..3, scales +-(8..31): std = d * 19.5 * 8 / sqrt(12)
+            mag = rng.integers(8, 32, size=(n, 16), dtype=np.int32)
+            sgn = rng.integers(0, 2, size=(n, 16), dtype=np.int32) * 2 - 1
+            b[:, 96:108] = _pack_scales_q3(32 + mag * sgn)
+            d = (std / (19.5 * 8 / np.sqrt(12.0))) * rng.uniform(0.8, 1.2, n)
+            b[:, 108:110] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
         else:
             raise NotImplementedError(t)
 
@@ -383,6 +418,37 @@ def quantize_q6_K_rows(X):
     return out
 
 
+def pack_q3_K(q, sc6, d16) -> np.ndarray:
+    """block_q3_K (110 B) from q (n, 256) in -4..3, 6-bit scales sc6 (n, 16) and f16 d (n,): q + 4 is
+    stored as two bits in qs[32 n + l] at 2 j and the third in hmask[l] at bit 4 n + j (weight
+    128 n + 32 j + l)."""
+    q = np.asarray(q, np.int32) + 4
+    n = q.shape[0]
+    out = np.zeros((n, 110), np.uint8)
+    for h in range(2):
+        for j in range(4):
+            e = q[:, 128 * h + 32 * j:128 * h + 32 * j + 32]
+            out[:, 32 + 32 * h:64 + 32 * h] |= ((e & 3) << (2 * j)).astype(np.uint8)
+            out[:, 0:32] |= ((e >> 2) << (4 * h + j)).astype(np.uint8)
+    out[:, 96:108] = _pack_scales_q3(np.asarray(sc6, np.int32))
+    out[:, 108:110] = np.asarray(d16, np.float16).view(np.uint8).reshape(n, 2)
+    return out
+
+
+def quantize_q3_K_rows(X):
+    """(n, 256) superblocks -> block_q3_K: per-16 scale amax / 4 as sc6 = 32 + 1..31 of d = max scale
+    / 31, q = the level nearest x / (d sc) in -4..3."""
+    X = X.reshape(-1, 256)
+    n = X.shape[0]
+    s = np.abs(X.reshape(n, 16, 16)).max(2) / 4.0
+    d16 = _f16(s.max(1) / 31.0)
+    d = d16.astype(np.float32)
+    sc = np.clip(np.rint(np.divide(s, d[:, None], out=np.zeros_like(s), where=d[:, None] > 0)), 1, 31).astype(np.int32)
+    eff = np.repeat(d[:, None] * sc, 16, axis=1)
+    q = np.clip(np.rint(np.divide(X, eff, out=np.zeros_like(X), where=eff > 0)), -4, 3).astype(np.int32)
+    return pack_q3_K(q, sc + 32, d16)
+
+
 def quantize_q45_K_rows(X, q5: bool):
     X = X.reshape(-1, 256)
     n = X.shape[0]
@@ -429,6 +495,8 @@ def quantize_rows(X, t: int) -> np.ndarray:
         return quantize_q45_K_rows(X, t == Q5_K).reshape(-1)
     if t in (Q4_0, Q5_0):
         return quantize_q45_0_rows(X, t == Q5_0).reshape(-1)
+    if t == Q3_K:
+        return quantize_q3_K_rows(X).reshape(-1)
     if t == F32:
         return X.reshape(-1).view(np.uint8)
     if t == F16:
@@ -583,7 +651,8 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     w.add_str("general.architecture", arch)
     w.add_str("general.name", f"synthetic {cfg.name} {cfg.ftype}")
     w.add_u32("general.file_type", {"Q8_0": 7, "Q4_K_M": 15, "Q5_K_M": 17, "Q6_K": 18,
-                                    "Q4_K": 15, "Q5_K": 17, "F16": 1, "Q4_0": 2, "Q5_0": 8}[cfg.ftype])
+                                    "Q4_K": 15, "Q5_K": 17, "F16": 1, "Q4_0": 2, "Q5_0": 8,
+                                    "Q3_K_S": 11, "Q3_K_M": 12}[cfg.ftype])
     w.add_u32(f"{arch}.context_length", cfg.n_ctx_train)
     w.add_u32(f"{arch}.embedding_length", cfg.n_embd)
     w.add_u32(f"{arch}.block_count", cfg.n_layer)

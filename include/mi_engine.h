@@ -42,9 +42,10 @@ const char* mi_last_error(void);
 /* Weight types served: quantised models (layer matrices, output head and token_embd each one of
  * Q4_K / Q5_K / Q6_K / Q8_0 and, in a dense LLaMA-graph model, Q4_0 / Q5_0: llama-quantize's Q4_0 and
  * Q5_0 files -- head Q6_K -- and the tensors it stores as Q4_0 / Q5_0 inside a k-quant file; Q4_0 and
- * Q5_0 matrices take Q8_0 activations as Q8_0 ones do.  Refused with the tensor and the type by name,
- * vocab_only included: Q4_1, Q5_1 (Q8_1 activations), Q2_K, Q3_K, the IQ and TQ types, and a Q4_0 /
- * Q5_0 matrix in a MoE, GPT-2 or BERT model),
+ * Q5_0 matrices take Q8_0 activations as Q8_0 ones do; and Q3_K, id 11: llama-quantize's Q3_K_S /
+ * Q3_K_M / Q3_K_L files, Q8_K activations as the other k-quants.  Refused with the tensor and the type
+ * by name, vocab_only included: Q4_1, Q5_1 (Q8_1 activations), Q2_K, the IQ and TQ types, and a Q4_0 /
+ * Q5_0 / Q3_K matrix in a MoE, GPT-2 or BERT model),
  * BERT encoders (F16), and unquantised dense LLaMA-graph models (general.architecture "llama",
  * no experts) whose matrices -- token_embd, output and the seven per layer -- are all F16 with F32
  * norm weights and rope_freqs; without output.weight the head is token_embd (tied models such as
@@ -475,6 +476,16 @@ int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_di
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);
+/* The same of mi_op_dgemv's launch of `role` (0..5; x a fixed ramp, quantised before the timed
+ * launches but in roles 4 and 5, the residual zero), every launch reading another copy of the planes
+ * so that it streams from HBM. */
+int32_t mi_op_dgemv_bench(int32_t device, int32_t role, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
+                          int32_t type2, const void* raw_blocks2, int32_t rows2, int32_t iters, float* median_us);
+/* The same of mi_op_gemm's launches after the activation's quantisation (the short-batch GEMM with
+ * its part sum, or the tiled GEMM) over ntok rows of a fixed ramp, every call reading another
+ * MFMA-order copy. */
+int32_t mi_op_gemm_bench(int32_t device, int32_t type, const void* raw_blocks, const void* raw_up, int32_t rows,
+                         int32_t K, int32_t ntok, int32_t iters, float* median_us);
 
 #ifdef __cplusplus
 }
