@@ -12,7 +12,7 @@ namespace mi {
 // ggml_type ids (llama.cpp b5187 ggml.h) -- the GGUF tensor type field.
 enum GgmlType : int {
     T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q8_0 = 8, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
-    T_BF16 = 30,
+    T_IQ4_NL = 20, T_IQ4_XS = 23, T_BF16 = 30,
 };
 // ggml's name of a tensor type id (ggml.c type_traits), for messages; "type N" for ids past the table
 inline std::string type_name(int t) {
@@ -28,27 +28,29 @@ constexpr int QK_K = 256;
 
 // Bytes of one GGUF block and the elements it covers.
 inline int block_elems(int t) {
-    return (t == T_F32 || t == T_F16) ? 1 : (t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 ? 32 : 256);
+    return (t == T_F32 || t == T_F16) ? 1 : (t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL ? 32 : 256);
 }
 inline int block_bytes(int t) {
     switch (t) {
     case T_F32: return 4; case T_F16: return 2; case T_Q8_0: return 34;
     case T_Q4_0: return 18; case T_Q5_0: return 22;
     case T_Q3_K: return 110;
+    case T_IQ4_NL: return 18; case T_IQ4_XS: return 136;
     case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
     default: return 0;
     }
 }
 inline bool is_quant(int t) {
-    return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K;
+    return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K ||
+           t == T_IQ4_NL || t == T_IQ4_XS;
 }
 // The 32-weight-block types with an f16 scale per block (Q4_0, Q5_0: llama-quantize's classic outputs).
 inline bool is_legacy_quant(int t) { return t == T_Q4_0 || t == T_Q5_0; }
 // The types only the dense LLaMA kernels read: refused in MoE, GPT-2 and BERT models (Model::check_types).
-inline bool dense_only_quant(int t) { return is_legacy_quant(t) || t == T_Q3_K; }
-// Whether a matrix of this type takes Q8_0 activations (vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0);
-// the k-quants take Q8_K ones.
-inline bool takes_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0; }
+inline bool dense_only_quant(int t) { return is_legacy_quant(t) || t == T_Q3_K || t == T_IQ4_NL || t == T_IQ4_XS; }
+// Whether a matrix of this type takes Q8_0 activations (vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0 /
+// _iq4_nl_q8_0); the k-quants and IQ4_XS take Q8_K ones.
+inline bool takes_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL; }
 
 // On-device layout of a quantised matrix.  GGUF rows are arrays of blocks
 // whose sizes (144/176/210/34 B) are not all 16-B aligned; at load time each
@@ -69,11 +71,16 @@ inline bool takes_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0;
 //         piece, one request per line -- and owns the shifts 2 (j & 1) and 2 (j & 1) + 1 of it: 32
 //         weights in the 16-weight scale groups 8 n + 4 (j & 1) + ((j >> 1) & 1) and that + 2, against
 //         two 16-byte activation runs 32 bytes apart (qdot.h, Kq<T_Q3_K>).
+//   IQ4_NL: p0 qs[128]  p1 f16 d[8]               (Q4_0's planes; a nibble indexes the codebook kvalues_iq4nl)
+//   IQ4_XS: p0 qs[128]  p1 hdr[16] = {f16 d, u16 scales_h, u8 scales_l[4], 8 zero bytes}
+//         Sub-block j (32 weights) is the qs bytes 16 j..: byte i holds the codebook index of weight
+//         32 j + i (low nibble) and of weight 32 j + 16 + i (high nibble); its 6-bit scale is nibble j
+//         of scales_l | bits 2 j.. of scales_h << 4.  Lane j of a superblock's 8 owns sub-block j.
 constexpr int kPlanePadSb = 16;  // tail padding (superblocks) after every plane (ring GEMV over-reads)
 inline int plane_count(int t) {
     switch (t) { case T_Q4_K: return 2; case T_Q5_K: return 3; case T_Q6_K: return 4;
                  case T_Q8_0: return 2; case T_Q4_0: return 2; case T_Q5_0: return 3; case T_Q3_K: return 3;
-                 default: return 0; }
+                 case T_IQ4_NL: return 2; case T_IQ4_XS: return 2; default: return 0; }
 }
 inline int plane_sb_bytes(int t, int p) {
     static const int q4k[] = {128, 16}, q5k[] = {128, 32, 16}, q6k[] = {128, 64, 16, 2}, q80[] = {256, 16};
@@ -81,7 +88,7 @@ inline int plane_sb_bytes(int t, int p) {
     switch (t) {
     case T_Q4_K: return q4k[p]; case T_Q5_K: return q5k[p]; case T_Q6_K: return q6k[p];
     case T_Q8_0: return q80[p]; case T_Q4_0: return q40[p]; case T_Q5_0: return q50[p];
-    case T_Q3_K: return q3k[p]; default: return 0;
+    case T_Q3_K: return q3k[p]; case T_IQ4_NL: return q40[p]; case T_IQ4_XS: return q4k[p]; default: return 0;
     }
 }
 

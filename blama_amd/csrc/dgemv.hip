@@ -365,6 +365,16 @@ DvFn dv_fn_role(int t0, int t1, int c) {
             if (t1 == T_Q5_K) return dv_fn_c<T_Q3_K, T_Q5_K, RW, ROLE, LORA>(c);
         }
         return nullptr;
+    // IQ4_NL: one type per launch (a Q5_K V takes Q8_K activations: its own launch); IQ4_XS: alone, or
+    // Q and K of it with V as Q4_K / Q5_K (llama-quantize's IQ4_XS file of a GQA model)
+    case T_IQ4_NL: return t1 >= 0 ? nullptr : dv_fn_c<T_IQ4_NL, -1, RW, ROLE, LORA>(c);
+    case T_IQ4_XS:
+        if (t1 < 0) return dv_fn_c<T_IQ4_XS, -1, RW, ROLE, LORA>(c);
+        if constexpr (dv_base(ROLE) == DV_QKV) {
+            if (t1 == T_Q4_K) return dv_fn_c<T_IQ4_XS, T_Q4_K, RW, ROLE, LORA>(c);
+            if (t1 == T_Q5_K) return dv_fn_c<T_IQ4_XS, T_Q5_K, RW, ROLE, LORA>(c);
+        }
+        return nullptr;
     default: return nullptr;
     }
 }
@@ -485,6 +495,8 @@ bool dgemv_supported(const GemvParams& p) {
     if (p.nseg == 2 && (dv_base(role) != DV_QKV || p.seg[1].epi != EPI_QKV)) return false;
     return dv_fn(role, g.A.type, p.nseg == 2 ? p.seg[1].A.type : -1, dv_chunks(p.K), lora) != nullptr;
 }
+
+bool dgemv_pair_supported(int t0, int t1, int K) { return dv_fn(DV_QKV, t0, t1, dv_chunks(K)) != nullptr; }
 
 void launch_dgemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (!p.act_in && !p.x[0]) throw Error("dgemv: no activation");

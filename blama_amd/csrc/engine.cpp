@@ -440,7 +440,9 @@ int Ctx::qkv_params(int l, ActSrc src, GemvParams out[3]) const {
     for (int g = 0; g < L.n_qkv; ++n) {
         p.nseg = 0;
         for (; g < L.n_qkv && p.nseg < GEMV_MAX_SEG; ++g) {
-            if (p.nseg == 1 && !gemv_pair_supported(p.seg[0].A.type, L.qkv[g].type)) break;
+            // (each step asks the kernel it launches: the streaming one has pairs gemv_kernel lacks)
+            const int t0 = p.seg[0].A.type, t1 = L.qkv[g].type;
+            if (p.nseg == 1 && !(src == ACT_PRO ? gemv_pair_supported(t0, t1) : dgemv_pair_supported(t0, t1, p.K))) break;
             GemvSeg& sg = p.seg[p.nseg++];
             sg = seg_of(L.qkv[g], PAIR_ADJ, EPI_QKV, q);
             sg.nq = L.qkv_nq[g];

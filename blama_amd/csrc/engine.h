@@ -119,9 +119,10 @@ struct Model {
     // dense LLaMA graph, alone (llama-quantize's Q4_0 / Q5_0 files, head Q6_K) or inside a k-quant
     // file.  check_types reads the header only: true when a matrix has one of the two types; refuses,
     // with the tensor and the type's name, such a matrix in a MoE, GPT-2 or BERT model and a matrix of
-    // a quantised type no kernel here reads (Q4_1, Q5_1 -- Q8_1 activations --, Q2_K, IQ*, TQ*).  Q3_K
-    // matrices (110-byte superblocks, Q8_K activations) are served and refused by the same rules
-    // (common.h dense_only_quant).  dense_only: the file has a matrix of such a type, so every tensor
+    // a quantised type no kernel here reads (Q4_1, Q5_1 -- Q8_1 activations --, Q2_K, TQ*, the IQ
+    // types but the two that follow).  Q3_K matrices (110-byte superblocks, Q8_K activations), IQ4_NL
+    // (18-byte blocks, Q8_0 activations) and IQ4_XS (136-byte superblocks, Q8_K activations) are served
+    // and refused by the same rules (common.h dense_only_quant).  dense_only: the file has a matrix of such a type, so every tensor
     // streams whole and a vocab-only load fills weight_bytes / type_bytes from the header.
     bool dense_only = false;
     bool check_types() const;

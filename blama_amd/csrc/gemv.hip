@@ -183,14 +183,29 @@ template <> struct GvAct<T_Q5_0> {
         return GvAct<T_Q4_0>::get(s, L, sb, j);
     }
 };
+template <> struct GvAct<T_IQ4_NL> {
+    __device__ static Kq<T_IQ4_NL>::AR get(const char* s, const GvLds& L, int sb, int j) {
+        return GvAct<T_Q4_0>::get(s, L, sb, j);
+    }
+};
+template <> struct GvAct<T_IQ4_XS> {   // lane j: sub-block j, the 32 activations 32 j.. (Kq<T_IQ4_XS>)
+    __device__ static Kq<T_IQ4_XS>::AR get(const char* s, const GvLds& L, int sb, int j) {
+        const char* ab = s + L.q8k + sb * GV_ASTR + 32 * j;
+        Kq<T_IQ4_XS>::AR r;
+        r.alo = *reinterpret_cast<const i32x4*>(ab);
+        r.ahi = *reinterpret_cast<const i32x4*>(ab + 16);
+        r.dx = reinterpret_cast<const float*>(s + L.dk)[sb];
+        return r;
+    }
+};
 
 // Which activation formats a workgroup of segment types (T0, T1) must build.
-template <int T> __host__ __device__ constexpr bool gv_q80() { return T == T_Q8_0 || T == T_Q4_0 || T == T_Q5_0; }
+template <int T> __host__ __device__ constexpr bool gv_q80() { return T == T_Q8_0 || T == T_Q4_0 || T == T_Q5_0 || T == T_IQ4_NL; }
 
 // Loads of one ring item row (Kq<T>::bload): the persistent prefill waits for everything but
 // these (vmcnt counts loads and stores in issue order).
 template <int T> __host__ __device__ constexpr int gv_nl() {
-    return T == T_Q4_K || T == T_Q4_0 ? 2 : T == T_Q5_K ? 3 : T == T_Q6_K ? 4 : 3;
+    return T == T_Q4_K || T == T_Q4_0 || T == T_IQ4_NL || T == T_IQ4_XS ? 2 : T == T_Q5_K ? 3 : T == T_Q6_K ? 4 : 3;
 }
 template <int N> __device__ __forceinline__ void wait_vm() {   // s_waitcnt vmcnt(N) only
     static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
@@ -977,6 +992,8 @@ GvFn gv_fn_rw(int t0, int t1, int kb, int tag) {
     case T_Q4_0: return gv_fn_same<T_Q4_0, RW>(t1, kb, tag);
     case T_Q5_0: return gv_fn_same<T_Q5_0, RW>(t1, kb, tag);
     case T_Q3_K: return gv_fn_same<T_Q3_K, RW>(t1, kb, tag);   // (a Q3_K_M layer's V of another type: its own launch)
+    case T_IQ4_NL: return gv_fn_same<T_IQ4_NL, RW>(t1, kb, tag);   // (an IQ4 file's Q5_K V likewise)
+    case T_IQ4_XS: return gv_fn_same<T_IQ4_XS, RW>(t1, kb, tag);
     case T_Q4_K: return gv_fn_pair<T_Q4_K, RW>(t1, kb, tag);
     case T_Q5_K: return gv_fn_pair<T_Q5_K, RW>(t1, kb, tag);
     case T_Q6_K: return t1 == T_Q6_K ? nullptr : gv_fn_pair<T_Q6_K, RW>(t1, kb, tag);
@@ -1035,7 +1052,7 @@ int gemv_grid(const GemvParams& p) {
 
 void init_kernel_attributes() {
     init_gemm_attributes();
-    const int types[7] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K};
+    const int types[9] = {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K, T_IQ4_NL, T_IQ4_XS};
     for (int rw = 1; rw <= 2; ++rw)
         for (int kb : {1, 2, 4})
             for (int t0 : types)

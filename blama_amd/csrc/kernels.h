@@ -160,8 +160,10 @@ size_t dv_act_bytes(int K, int q8k, int q80);         // bytes of a quantised ac
 // ev_start/ev_stop (optional): recorded at the kernel's own start and end (hipExtLaunchKernel)
 // -- the bench's in-kernel timing of one launch.
 void launch_gemv(const GemvParams& p, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-// whether one launch can carry segments of these two quant types
+// whether one launch can carry segments of these two quant types: gemv_kernel, and dgemv_kernel's
+// Q/K/V launch over rows of K (which also pairs Q3_K / IQ4_XS with a Q4_K / Q5_K V)
 bool gemv_pair_supported(int t1, int t2);
+bool dgemv_pair_supported(int t1, int t2, int K);
 // workgroups of a launch
 int gemv_grid(const GemvParams& p);
 void init_gemm_attributes();     // the batch GEMMs' and batch attention's LDS limits, and the device's CU count

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512) void gemm_t(const GemmParams P) {
 typedef void (*GemmFn)(const GemmParams);
 static GemmFn gemm_fn(int type, bool pre);
 void init_gemm_attributes() {
-    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K})
+    for (int t : {T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_Q4_0, T_Q5_0, T_Q3_K, T_IQ4_NL, T_IQ4_XS})
         for (bool pre : {false, true})
             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fn(t, pre)),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -266,6 +266,8 @@ static GemmFn gemm_fn(int type, bool pre) {
     case T_Q4_0: return pre ? gemm_t<T_Q4_0, 4, true> : gemm_t<T_Q4_0, 4, false>;
     case T_Q5_0: return pre ? gemm_t<T_Q5_0, 4, true> : gemm_t<T_Q5_0, 4, false>;
     case T_Q3_K: return pre ? gemm_t<T_Q3_K, 4, true> : gemm_t<T_Q3_K, 4, false>;
+    case T_IQ4_NL: return pre ? gemm_t<T_IQ4_NL, 4, true> : gemm_t<T_IQ4_NL, 4, false>;
+    case T_IQ4_XS: return pre ? gemm_t<T_IQ4_XS, 4, true> : gemm_t<T_IQ4_XS, 4, false>;
     default: return nullptr;
     }
 }
@@ -369,6 +371,21 @@ __device__ float dequant_elem(const QMat& M, long long row, int col) {
         const int sc6 = lo4 | (((sc[8 + (g & 3)] >> (2 * (g >> 2))) & 3) << 4);
         const float d = h2f(sc[12] | (sc[13] << 8));
         return (d * (float)(sc6 - 32)) * (float)q;
+    }
+    case T_IQ4_NL: {   // dequantize_row_iq4_nl: d * kv[nibble], element l of block blk
+        const int blk = i >> 5, l = i & 31;
+        const uint8_t b = M.p[0][sbi * 128 + blk * 16 + (l & 15)];
+        const uint8_t* dp = M.p[1] + sbi * 16 + blk * 2;
+        return h2f(dp[0] | (dp[1] << 8)) * (float)iq4_kv(l < 16 ? (b & 0xF) : (b >> 4));
+    }
+    case T_IQ4_XS: {   // dequantize_row_iq4_xs: (d * (ls - 32)) * kv[nibble], sub-block ib
+        const int ib = i >> 5, l = i & 31;
+        const uint8_t b = M.p[0][sbi * 128 + ib * 16 + (l & 15)];
+        const uint8_t* hd = M.p[1] + sbi * 16;
+        const int sh = hd[2] | (hd[3] << 8);
+        const int ls = ((hd[4 + ib / 2] >> (4 * (ib & 1))) & 0xF) | (((sh >> (2 * ib)) & 3) << 4);
+        const float dl = h2f(hd[0] | (hd[1] << 8)) * (float)(ls - 32);
+        return dl * (float)iq4_kv(l < 16 ? (b & 0xF) : (b >> 4));
     }
     case T_F32:
         return reinterpret_cast<const float*>(M.p[0])[row * M.K + col];
@@ -813,6 +830,18 @@ __global__ void repack_kernel(const uint8_t* raw, int type, long long nsb, uint8
             for (int k = 0; k < 32; ++k) p1[i * 32 + k] = b[k];
             for (int k = 0; k < 14; ++k) p2[i * 16 + k] = b[96 + k];
             p2[i * 16 + 14] = p2[i * 16 + 15] = 0;
+        } else if (type == T_IQ4_NL) {
+            const uint8_t* b = raw + i * 144;   // 8 blocks of 18: f16 d, qs[16]
+            for (int blk = 0; blk < 8; ++blk) {
+                p1[i * 16 + blk * 2] = b[blk * 18];
+                p1[i * 16 + blk * 2 + 1] = b[blk * 18 + 1];
+                for (int k = 0; k < 16; ++k) p0[i * 128 + blk * 16 + k] = b[blk * 18 + 2 + k];
+            }
+        } else if (type == T_IQ4_XS) {
+            const uint8_t* b = raw + i * 136;   // f16 d, u16 scales_h, scales_l[4], qs[128]
+            for (int k = 0; k < 128; ++k) p0[i * 128 + k] = b[8 + k];
+            for (int k = 0; k < 8; ++k) p1[i * 16 + k] = b[k];
+            for (int k = 8; k < 16; ++k) p1[i * 16 + k] = 0;
         }
     }
 }

@@ -18,6 +18,8 @@
 //     superblock); the min terms sum_j m_j * bsum_j are two more MFMAs (bsum = 64 hi + lo);
 //   * Q3_K: the same once-per-row-tile decode into ONE plane of the negated scaled weights
 //     -q (sc6 - 32) in -128..+124 (q3k_span), one MFMA per span, the sign taken back in the update;
+//   * IQ4_XS: the once-per-row-tile decode through the codebook into the plane pair hi / lo of
+//     w = (ls - 32) kv = 64 hi + lo (iq4xs_span), then Q6_K's two MFMAs per span;
 //   * Q6_K: the scaled hi/lo operands of the MFMA-order copy, accumulated by the MFMA; Q8_0:
 //     one MFMA per 32-block and a float update per block (vec_dot_q8_0_q8_0's order);
 //   * per 32x32 tile the integer sums are the contract's exact int32 values, and the float update
@@ -36,6 +38,7 @@
 namespace mi {
 namespace mmq {
 
+// (the IQ4_NL copy holds the looked-up int8 weights, iq4_kv: the Q8_0 tile)
 __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* dst) {
     const int nb = A.nb;
     const long long tile = blockIdx.x;   // rt * nb + sb
@@ -44,7 +47,7 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
     uint8_t* o = dst + tile * TB;
     for (int off = threadIdx.x; off < TB; off += blockDim.x) {
         int plane, c, byte;
-        if (A.type == T_Q4_0 || A.type == T_Q5_0) {
+        if (A.type == T_Q4_0 || A.type == T_Q5_0 || A.type == T_IQ4_NL) {
             const bool q5 = A.type == T_Q5_0;
             if (off < 8192) {   // element l = 16h + e of block jj as int8: the nibble (| the qh bit) - 8 (16)
                 const int jj = off >> 10, ln = (off >> 4) & 63, e = off & 15;
@@ -60,7 +63,7 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
                     const unsigned qh = hp[0] | (hp[1] << 8) | (hp[2] << 16) | ((unsigned)hp[3] << 24);
                     q |= (int)((qh >> l) & 1u) << 4;
                 }
-                o[off] = (uint8_t)(int8_t)(q - (q5 ? 16 : 8));
+                o[off] = A.type == T_IQ4_NL ? (uint8_t)iq4_kv(q) : (uint8_t)(int8_t)(q - (q5 ? 16 : 8));
                 continue;
             }
             plane = q5 ? 2 : 1; c = (off - 8192) >> 4; byte = (off - 8192) & 15;
@@ -88,6 +91,18 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
             } else {
                 plane = 2; c = (off - 5120) >> 4; byte = (off - 5120) & 15;
             }
+        } else if (A.type == T_IQ4_XS) {
+            if (off < 4096) {   // the nibbles of k-half h of spans 2 p (low) and 2 p + 1 (high)
+                const int p = off >> 10, ln = (off >> 4) & 63, e = off & 15;
+                const int cc = ln & 31, h = ln >> 5;
+                const QMat& M = (pair && cc >= 16) ? B : A;
+                long long row = pair ? 16LL * rt + (cc & 15) : 32LL * rt + cc;
+                if (row >= M.rows) row = M.rows - 1;
+                const uint8_t* q = M.p[0] + (row * nb + sb) * 128 + 32 * p + e;
+                o[off] = (uint8_t)(((q[0] >> (4 * h)) & 0xF) | (((q[16] >> (4 * h)) & 0xF) << 4));
+                continue;
+            }
+            plane = 1; c = (off - 4096) >> 4; byte = (off - 4096) & 15;
         } else if (A.type == T_Q3_K) {
             if (off < 2048) {
                 const int p = off >> 10, ln = (off >> 4) & 63, e = off & 15;
@@ -120,7 +135,7 @@ __global__ void swizzle_kernel(const QMat A, const QMat B, int pair, uint8_t* ds
         const QMat& M = (pair && c >= 16) ? B : A;
         long long row = pair ? 16LL * rt + (c & 15) : 32LL * rt + c;
         if (row >= M.rows) row = M.rows - 1;
-        const int pb = (A.type == T_Q4_0 || A.type == T_Q5_0) ? 16
+        const int pb = (A.type == T_Q4_0 || A.type == T_Q5_0 || A.type == T_IQ4_NL || A.type == T_IQ4_XS) ? 16
                      : A.type == T_Q3_K ? (plane == 0 ? 64 : plane == 1 ? 32 : 16)
                      : A.type == T_Q8_0 ? (plane == 0 ? 256 : 16)
                      : A.type == T_Q4_K ? (plane == 0 ? 128 : 16)
@@ -223,7 +238,7 @@ template <int T> struct M2 {
     static constexpr int NI = STAGE / 1024;                             // 1 KiB LDS-DMA pieces
     static constexpr int NIW = (NI + NW - 1) / NW;                      // per wave (some repeat)
     static constexpr int NPL = 2;                                       // K-quant operand planes
-    static constexpr int PLANES = (T == T_Q4_K || T == T_Q5_K) ? RT * NPL * 8 * 1024 : T == T_Q3_K ? RT * 8 * 1024 : 0;   // Q3_K: one plane
+    static constexpr int PLANES = (T == T_Q4_K || T == T_Q5_K || T == T_IQ4_XS) ? RT * NPL * 8 * 1024 : T == T_Q3_K ? RT * 8 * 1024 : 0;   // Q3_K: one plane
     static constexpr int lds(int nst) { return nst * STAGE + PLANES; }
 };
 
@@ -583,6 +598,58 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
                     for (int i = 0; i < 4; ++i) y[r][4 * g + i] = fmaf(dr * dx[i], (float)(-acc[4 * g + i]), y[r][4 * g + i]);
                 }
             }
+        } else if (T == T_IQ4_XS) {
+            // (1) decode: wave w of row tile wr turns piece w (spans 2w, 2w + 1) of its superblock into
+            //     the hi / lo operand planes of w = (ls - 32) kv = 64 hi + lo (iq4xs_span), once per
+            //     row tile;  (2) Q6_K's MFMAs on the plane pair: S = 64 ah + al
+            const lchar* wt = stg + wr * C::SLOT;
+            lchar* pl = (lchar*)(smem + NST * C::STAGE) + wr * (NPL * 8 * 1024) + lane * 16;
+            const u32x4 hd = lds_ld<u32x4>(wt + 4096 + col * 16);
+            {
+                const u32x4 wq = lds_ld<u32x4>(wt + w * 1024 + lane * 16);
+                v4i h0, l0, h1, l1;
+                iq4xs_span(wq, hd, 2 * w, h0, l0);
+                iq4xs_span(wq, hd, 2 * w + 1, h1, l1);
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (0 * 8 + 2 * w) * 1024) = h0;
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (1 * 8 + 2 * w) * 1024) = l0;
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (0 * 8 + 2 * w + 1) * 1024) = h1;
+                *reinterpret_cast<__attribute__((address_space(3))) v4i*>(pl + (1 * 8 + 2 * w + 1) * 1024) = l1;
+                __builtin_amdgcn_s_waitcnt((0xF) | (0x3 << 14) | (0x7 << 4));   // lgkmcnt(0): planes written
+                __builtin_amdgcn_s_barrier();
+            }
+            if (busy) {
+                constexpr int r = 0;
+                const lchar* plr = (const lchar*)pl;
+                v16i ah = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, al = ah;
+                v4i av[8], bh[8], bl[8];   // operands read first (counted LDS waits)
+#pragma unroll
+                for (int sp = 0; sp < 8; ++sp) {
+                    av[sp] = lds_ld<v4i>(A0 + sp * 1024);
+                    bh[sp] = lds_ld<v4i>(plr + (0 * 8 + sp) * 1024);
+                    bl[sp] = lds_ld<v4i>(plr + (1 * 8 + sp) * 1024);
+                }
+#pragma unroll
+                for (int sp = 0; sp < 8; ++sp) {
+                    if (NST == 2) {
+                        pin(av[sp]);
+                        pin(bh[sp]);
+                        pin(bl[sp]);
+                    }
+                    ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[sp], bh[sp], ah, 0, 0, 0);
+                    al = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[sp], bl[sp], al, 0, 0, 0);
+                }
+                const float dr = h2f(hd.x);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 dx4 = lds_ld<f32x4>(dTw + 32 * g);
+                    const float dx[4] = {dx4.x, dx4.y, dx4.z, dx4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int e = 4 * g + i;
+                        y[r][e] = fmaf(dr * dx[i], (float)(ah[e] * 64 + al[e]), y[r][e]);
+                    }
+                }
+            }
         } else {   // Q6_K: the 8 spans of w = 64*hi + lo, each operand accumulated by the MFMA
             if (busy) {
                 constexpr int r = 0;
@@ -654,7 +721,7 @@ void mmq2_t(const GemmParams P, const ActQ8 act, const float2* rope, const MmqSe
 
 bool mmq32_supported(int type) {
     return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0 || is_legacy_quant(type) ||
-           type == T_Q3_K;
+           type == T_Q3_K || type == T_IQ4_NL || type == T_IQ4_XS;
 }
 
 int mmq32_tile_bytes(int type) { return mmq::mmq32_tile_bytes_d(type); }
@@ -688,6 +755,7 @@ size_t mmq2_lds(int T, int nst) {
     case T_Q5_K: return mmq::M2<T_Q5_K>::lds(nst);
     case T_Q6_K: return mmq::M2<T_Q6_K>::lds(nst);
     case T_Q3_K: return mmq::M2<T_Q3_K>::lds(nst);
+    case T_IQ4_XS: return mmq::M2<T_IQ4_XS>::lds(nst);
     default: return mmq::M2<T_Q8_0>::lds(nst);
     }
 }
@@ -743,6 +811,7 @@ Mmq2Fn mmq2_fn(const MmqPlan& k) {
     case T_Q5_K: return mmq2_fn_t<T_Q5_K>(k);
     case T_Q6_K: return mmq2_fn_t<T_Q6_K>(k);
     case T_Q3_K: return mmq2_fn_t<T_Q3_K>(k);
+    case T_IQ4_XS: return mmq2_fn_t<T_IQ4_XS>(k);
     case T_Q8_0: return mmq2_fn_t<T_Q8_0>(k);
     default: return nullptr;
     }
@@ -762,7 +831,7 @@ int mmq_n_cu() {
 // Once per device (init_gemm_attributes): the LDS limit of every instantiation a plan can name, and
 // the device's CU count for the plans of its launches.
 void init_mmq2_attributes() {
-    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
+    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_IQ4_XS})
         for (int nst : {1, 2})
             for (int v = 0; v < 5; ++v) {   // plain, pair, pre, pair + pre, gx
                 MmqPlan k{};

@@ -20,6 +20,7 @@
 // (the k order inside an MFMA does not matter: A and B share it; scripts/exp_mfma_layout.cpp
 // checks the D map).  So every lane owns ONE weight row: its scales and mins are per-lane scalars.
 #pragma once
+#include "iq4.h"
 #include "kernels.h"
 #include <hip/hip_runtime.h>
 
@@ -116,12 +117,24 @@ __device__ __forceinline__ v16i mfma(v4i a, v4i b) {
 //         scaled weight q (sc6 - 32) reaches +128, so the kernels decode the NEGATED one,
 //         -q (sc6 - 32) in -128..+124, into an int8 operand (q3k_span): one MFMA per span, the
 //         exact int32 sum is minus the accumulator, taken back in the float update
+//   IQ4_NL  as Q4_0: the Q8_0 tile with qs[i] = kv[nibble], looked up once when the copy is built     8704 B
+//   IQ4_XS  [p 4][lane 64][16] | [c 32][16] header {f16 d, u16 scales_h, scales_l[4], pad}          4608 B
+//         Sub-block (= span) sp keeps both of its k-halves in the 16 qs bytes 16 sp.. (low / high
+//         nibbles), so the copy regroups the nibbles: byte e of piece p of lane (h, c) holds the
+//         codebook index of element 64 p + 16 h + e (span 2 p) in its low nibble and of element
+//         64 p + 32 + 16 h + e (span 2 p + 1) in its high one -- Q4_K's tile shape, one 16-byte load
+//         per two spans and lane.  The scaled weight w = (ls - 32) kv, |w| <= 4064, does not fit
+//         int8: the kernels decode it into the operand pair w = 64 hi + lo (hi -64..63, lo 0..63) of
+//         the Q6_K kernels (iq4xs_span), two MFMAs per span, exact int32 sums.
 __host__ __device__ constexpr int mmq32_tile_bytes_d(int type) {
     return type == T_Q4_K ? 4608 : type == T_Q5_K ? 5632 : type == T_Q6_K ? 16448 : type == T_Q3_K ? 3584
-         : (type == T_Q8_0 || type == T_Q4_0 || type == T_Q5_0) ? 8704 : 0;
+         : type == T_IQ4_XS ? 4608
+         : (type == T_Q8_0 || type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL) ? 8704 : 0;
 }
 // the operand format of a type's MFMA-order copy: the kernels' template type
-__host__ __device__ constexpr int mmq_op_type(int type) { return (type == T_Q4_0 || type == T_Q5_0) ? (int)T_Q8_0 : type; }
+__host__ __device__ constexpr int mmq_op_type(int type) {
+    return (type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL) ? (int)T_Q8_0 : type;
+}
 
 constexpr int MMQ_SEGS = 3;    // matrices (row segments) one launch carries
 typedef __attribute__((address_space(3))) char lchar;
@@ -171,6 +184,34 @@ __device__ __forceinline__ v4i q3k_span(const u32x4 qs, const u32x4 hm, const u3
         o[i] = (m02 & 0x00FF00FFu) | ((m13 & 0x00FF00FFu) << 8);
     }
     return v4i{(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
+}
+// IQ4_XS: the int8 MFMA operand pair of span sp for this lane's row and k-half: w = (ls - 32) kv =
+// 64 hi + lo.  qs: the lane's piece sp >> 1 of the regrouped copy (nibble sp & 1), hd: the row's
+// header.  The codebook comes back as u = kv + 128 (iq4_lut<128>, unsigned bytes), and
+// w = u s - 128 s with s = ls - 32 is formed modulo 2^16 in packed 16-bit lanes (v_pk_mad_u16):
+// |w| <= 4064, so the lane holds w's exact two's complement; lo = its bits 0..5, hi = bits 6..13.
+__device__ __forceinline__ void iq4xs_span(const u32x4 qs, const u32x4 hd, int sp, v4i& hi, v4i& lo) {
+    const int s = (int)(((hd.y >> (4 * sp)) & 0xFu) | (((hd.x >> (16 + 2 * sp)) & 3u) << 4)) - 32;
+    const u16x2 m = {(unsigned short)s, (unsigned short)s};
+    const u16x2 b = {(unsigned short)(-128 * s), (unsigned short)(-128 * s)};
+    const unsigned Q[4] = {qs.x, qs.y, qs.z, qs.w};
+    unsigned oh[4], ol[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned u = iq4_lut<128>((Q[i] >> (4 * (sp & 1))) & 0x0F0F0F0Fu);
+        const unsigned e02 = u & 0x00FF00FFu, e13 = (u >> 8) & 0x00FF00FFu;
+        u16x2 a02, a13;
+        __builtin_memcpy(&a02, &e02, 4);
+        __builtin_memcpy(&a13, &e13, 4);
+        const u16x2 r02 = a02 * m + b, r13 = a13 * m + b;
+        unsigned w02, w13;
+        __builtin_memcpy(&w02, &r02, 4);
+        __builtin_memcpy(&w13, &r13, 4);
+        ol[i] = (w02 & 0x003F003Fu) | ((w13 & 0x003F003Fu) << 8);
+        oh[i] = ((w02 >> 6) & 0x00FF00FFu) | (((w13 >> 6) & 0x00FF00FFu) << 8);
+    }
+    hi = v4i{(int)oh[0], (int)oh[1], (int)oh[2], (int)oh[3]};
+    lo = v4i{(int)ol[0], (int)ol[1], (int)ol[2], (int)ol[3]};
 }
 template <typename V>
 __device__ __forceinline__ V lds_ld(const lchar* p) { return *reinterpret_cast<const __attribute__((address_space(3))) V*>(p); }

@@ -68,6 +68,7 @@ template <> struct MsT<T_Q5_K> { static constexpr int NV = 6, D = 4; };    // qs
 template <> struct MsT<T_Q6_K> { static constexpr int NV = 16, D = 2; };   // hi [8] | lo [8] (+ d)
 template <> struct MsT<T_Q3_K> { static constexpr int NV = 4, D = 4; };    // qs [2] | hmask | header
 template <> struct MsT<T_Q8_0> { static constexpr int NV = 9, D = 2; };    // qs [8] | d [8 x f16]
+template <> struct MsT<T_IQ4_XS> { static constexpr int NV = 5, D = 4; };  // regrouped qs [4] | header
 template <int T> struct MsW {
     u32x4 v[MsT<T>::NV];
     unsigned d6;   // Q6_K: the row's d
@@ -77,7 +78,7 @@ __device__ __forceinline__ MsW<T> ms_load(const uint8_t* tile, int lane) {
     const int col = lane & 31;
     MsW<T> w;
     auto ld = [&](int off) { return __builtin_nontemporal_load(gp(reinterpret_cast<const u32x4*>(tile + off))); };
-    if (T == T_Q4_K || T == T_Q5_K) {
+    if (T == T_Q4_K || T == T_Q5_K || T == T_IQ4_XS) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) w.v[p] = ld(p * 1024 + lane * 16);
         if (T == T_Q5_K) w.v[4] = ld(4096 + lane * 16);
@@ -210,6 +211,35 @@ __device__ __forceinline__ void ms_sb(const MsW<T>& w, int s, const char* lds, i
                 for (int i = 0; i < 4; ++i) {
                     const int e = 4 * g + i;
                     y[t][e] = fmaf(dr * dx[i], (float)(-(acc[0][t][e] + acc[1][t][e])), y[t][e]);
+                }
+            }
+    } else if (T == T_IQ4_XS) {   // the hi / lo pair of w = (ls - 32) kv decoded in registers (iq4xs_span)
+        const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        v16i ah[NT], al[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ah[t] = al[t] = z;
+#pragma unroll
+        for (int sp = 0; sp < 8; ++sp) {
+            v4i bh, bl;
+            iq4xs_span(w.v[sp >> 1], w.v[4], sp, bh, bl);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const v4i a = act(t, sp);
+                ah[t] = mfma_acc(a, bh, ah[t]);
+                al[t] = mfma_acc(a, bl, al[t]);
+            }
+        }
+        const float dr = h2f(w.v[4].x);
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 d4 = dx4(DB + s * 256 + (t * 32 + 8 * g + 4 * h) * 4);
+                const float dx[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = 4 * g + i;
+                    y[t][e] = fmaf(dr * dx[i], (float)(ah[t][e] * 64 + al[t][e]), y[t][e]);
                 }
             }
     } else if (T == T_Q6_K) {
@@ -456,6 +486,25 @@ __device__ __forceinline__ void ms1_sb(const MsW<T>& w, const MsAct& A, int lane
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[4 * g + i] = fmaf(dr * dx[i], (float)(-acc[4 * g + i]), y[4 * g + i]);
         }
+    } else if (T == T_IQ4_XS) {
+        v16i ah = z, al = z;
+#pragma unroll
+        for (int sp = 0; sp < 8; ++sp) {
+            v4i bh, bl;
+            iq4xs_span(w.v[sp >> 1], w.v[4], sp, bh, bl);
+            ah = mfma_acc(A.a[sp], bh, ah);
+            al = mfma_acc(A.a[sp], bl, al);
+        }
+        const float dr = h2f(w.v[4].x);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float dx[4] = {A.dx[g].x, A.dx[g].y, A.dx[g].z, A.dx[g].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = 4 * g + i;
+                y[e] = fmaf(dr * dx[i], (float)(ah[e] * 64 + al[e]), y[e]);
+            }
+        }
     } else {   // Q6_K
         v16i ah = z, al = z;
 #pragma unroll
@@ -629,7 +678,7 @@ MmqsFn mmqs_fn_t(const MmqPlan& k) {
         if (k.grouped) return k.pair ? mmq::mmqs1_lean_t<T, true, true> : mmq::mmqs1_lean_t<T, false, true>;
         return k.pair ? mmq::mmqs1_lean_t<T, true, false> : mmq::mmqs1_lean_t<T, false, false>;
     }
-    if constexpr (T == T_Q3_K) {   // (dense models only: no grouped form)
+    if constexpr (T == T_Q3_K || T == T_IQ4_XS) {   // (dense models only: no grouped form)
         if (k.kernel != MK_SHORT1_LEAN || k.grouped) return nullptr;
         return k.pair ? mmq::mmqs1_lean_t<T, true, false> : mmq::mmqs1_lean_t<T, false, false>;
     }
@@ -647,6 +696,7 @@ MmqsFn mmqs_fn(const MmqPlan& k) {
     case T_Q5_K: return mmqs_fn_t<T_Q5_K>(k);
     case T_Q6_K: return mmqs_fn_t<T_Q6_K>(k);
     case T_Q3_K: return mmqs_fn_t<T_Q3_K>(k);
+    case T_IQ4_XS: return mmqs_fn_t<T_IQ4_XS>(k);
     case T_Q8_0: return mmqs_fn_t<T_Q8_0>(k);
     default: return nullptr;
     }
@@ -670,7 +720,7 @@ void mmqs_launch(const MmqShape& sh, mmq::MsArgs& M, const ActQ8& act, float* pa
 // Once per device (init_gemm_attributes): the LDS limit of every mmqs_t instantiation a plan can name
 // (the mmqs1 kernels use no LDS).
 void init_mmqs_attributes() {
-    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0})
+    for (int T : {T_Q3_K, T_Q4_K, T_Q5_K, T_Q6_K, T_Q8_0, T_IQ4_XS})
         for (int nt : {1, 2})
             for (bool pair : {false, true}) {
                 MmqPlan k{};

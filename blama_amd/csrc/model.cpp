@@ -231,14 +231,14 @@ bool Model::check_types() const {
                             : hp.n_expert > 0 ? "a MoE model" : nullptr;
             if (why)
                 throw Error("tensor " + t.name + ": " + type_name(ty) + " matrices are not served in " + why + " (" +
-                            (ty == T_Q3_K ? "Q3_K is" : "Q4_0 / Q5_0 are") + " read by the dense LLaMA kernels only)");
+                            (ty == T_Q3_K ? "Q3_K is" : ty == T_IQ4_NL || ty == T_IQ4_XS ? "IQ4_NL / IQ4_XS are" : "Q4_0 / Q5_0 are") + " read by the dense LLaMA kernels only)");
             if (t.ne[0] % 256)
                 throw Error("tensor " + t.name + ": a " + type_name(ty) + " matrix needs a row length that is a multiple of 256");
         } else if (ty != T_F32 && ty != T_F16 && ty != T_BF16 && !is_quant(ty) && block_bytes(ty) == 0) {
             const bool q81 = ty == 3 || ty == 7;   // Q4_1, Q5_1
             throw Error("tensor " + t.name + ": " + type_name(ty) + " matrices are not served" +
                         (q81 ? " (they take Q8_1 activations; requantise to Q4_0, Q5_0, Q8_0 or a k-quant)"
-                             : " (served: Q4_0, Q5_0, Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, or F16 throughout)"));
+                             : " (served: Q4_0, Q5_0, Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, or F16 throughout)"));
         }
     }
     return any;
@@ -412,7 +412,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     if (!bert) f16 = check_f16();
     if (vocab_only) {
         // an F16 model's weight bytes and type histogram are known from the header alone, and so
-        // are those of a file with Q4_0 / Q5_0 / Q3_K matrices (dense: every tensor streams whole)
+        // are those of a file with Q4_0 / Q5_0 / Q3_K / IQ4_NL / IQ4_XS matrices (dense: every tensor streams whole)
         if (f16 || dense_only) {
             for (const GgufTensor& t : gguf.tensors) account(t, 1);
             if (!gguf.tensor("output.weight")) weight_bytes += (long long)gguf.tensor("token_embd.weight")->nbytes;   // tied head

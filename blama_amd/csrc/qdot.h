@@ -3,6 +3,7 @@
 // superblock dot products (Kq<T>), which reproduce ggml b5187's vec_dot_q*_K_q8_K /
 // vec_dot_q8_0_q8_0 integer arithmetic bit for bit.
 #pragma once
+#include "iq4.h"
 #include "kernels.h"
 #include <hip/hip_runtime.h>
 
@@ -630,6 +631,84 @@ template <> struct Kq<T_Q3_K> {
         S += dpp_i<0x141, 0xf>(S);   // row_half_mirror: the other quad of the 8
         const float d = h2f(l.hdr.w) * r.dx;
         return (j & 7) == 0 ? d * (float)S : 0.0f;
+    }
+};
+
+// IQ4_NL (vec_dot_iq4_nl_q8_0): Q4_0's planes, lane map and activation; the nibbles go through the
+// codebook into signed bytes, so the block's integer is the plain dot (no offset term) and meets
+// fp16(d_x) * fp16(d_y) in one product -- the Q8_0 block with qs[i] = kv[nibble].
+template <> struct PlaneBytes<T_IQ4_NL> { static constexpr int b[4] = {128, 16, 0, 0}; };
+template <> struct Kq<T_IQ4_NL> {
+    static constexpr int LPS = 8;
+    using Ld = Kq<T_Q4_0>::Ld;
+    __device__ static Ld load(const uint8_t* const* rp, int sb, int j) { return Kq<T_Q4_0>::load(rp, sb, j); }
+    __device__ static Ld bload(const uint8_t* const* rp, int sb, int j, bool park) { return Kq<T_Q4_0>::bload(rp, sb, j, park); }
+    using AR = ArQ80S;
+    __device__ static AR act(const Act& a, int sb, int j) { return Kq<T_Q4_0>::act(a, sb, j); }
+    __device__ static float dot(const Ld& l, const AR& r, int j) {
+        int s = 0;
+        s = dot4((int)iq4_lut(l.qs.x & 0x0F0F0F0Fu), r.a0.x, s);
+        s = dot4((int)iq4_lut(l.qs.y & 0x0F0F0F0Fu), r.a0.y, s);
+        s = dot4((int)iq4_lut(l.qs.z & 0x0F0F0F0Fu), r.a0.z, s);
+        s = dot4((int)iq4_lut(l.qs.w & 0x0F0F0F0Fu), r.a0.w, s);
+        s = dot4((int)iq4_lut((l.qs.x >> 4) & 0x0F0F0F0Fu), r.a1.x, s);
+        s = dot4((int)iq4_lut((l.qs.y >> 4) & 0x0F0F0F0Fu), r.a1.y, s);
+        s = dot4((int)iq4_lut((l.qs.z >> 4) & 0x0F0F0F0Fu), r.a1.z, s);
+        s = dot4((int)iq4_lut((l.qs.w >> 4) & 0x0F0F0F0Fu), r.a1.w, s);
+        const float d = h2f(l.d) * r.d0;
+        return d * (float)s;
+    }
+};
+
+// IQ4_XS (vec_dot_iq4_xs_q8_K): lane j of a superblock's 8 owns sub-block j -- its 16 qs bytes (low
+// nibbles: weights 32 j.., high nibbles: weights 32 j + 16..) against the 32 activations 32 j.., and
+// its scale ls = nibble j of scales_l | bits 2 j.. of scales_h << 4, both by per-lane shifts of
+// header dwords.  |dot| <= 32 * 127 * 127 < 2^23 and |ls - 32| <= 32: one exact 24-bit multiply;
+// the 8 lanes' integers add by DPP (|S| <= 256 * 4064 * 127 < 2^31) and lane 0 forms
+// (d * d8) * (float)S once per superblock, as the CPU does.  The codebook is signed: no bsum term.
+template <> struct PlaneBytes<T_IQ4_XS> { static constexpr int b[4] = {128, 16, 0, 0}; };
+template <> struct Kq<T_IQ4_XS> {
+    static constexpr int LPS = 8;
+    using Ld = Kq<T_Q4_K>::Ld;   // qs, hdr = {f16 d | scales_h << 16, scales_l, 0, 0}
+    __device__ static Ld load(const uint8_t* const* rp, int sb, int j) {
+        Ld l;
+        l.qs = ldg16(rp[0] + sb * 128 + j * 16);
+        l.hdr = ldg16(rp[1] + sb * 16);
+        return l;
+    }
+    __device__ static Ld bload(const uint8_t* const* rp, int sb, int j, bool park) {
+        Ld l;
+        l.qs = bld16(rp[0], oob(sb * 128 + j * 16, park));
+        l.hdr = bld16(rp[1], oob(sb * 16, park));
+        return l;
+    }
+    struct AR { i32x4 alo, ahi; float dx; };
+    __device__ static AR act(const Act& a, int sb, int j) {
+        const int8_t* ab = a.q8k + sb * 256 + 32 * j;
+        AR r;
+        r.alo = *reinterpret_cast<const i32x4*>(ab);
+        r.ahi = *reinterpret_cast<const i32x4*>(ab + 16);
+        r.dx = a.dk[sb];
+        return r;
+    }
+    __device__ static float dot(const Ld& l, const AR& r, int j) {
+        int s = 0;
+        s = dot4((int)iq4_lut(l.qs.x & 0x0F0F0F0Fu), r.alo.x, s);
+        s = dot4((int)iq4_lut(l.qs.y & 0x0F0F0F0Fu), r.alo.y, s);
+        s = dot4((int)iq4_lut(l.qs.z & 0x0F0F0F0Fu), r.alo.z, s);
+        s = dot4((int)iq4_lut(l.qs.w & 0x0F0F0F0Fu), r.alo.w, s);
+        s = dot4((int)iq4_lut((l.qs.x >> 4) & 0x0F0F0F0Fu), r.ahi.x, s);
+        s = dot4((int)iq4_lut((l.qs.y >> 4) & 0x0F0F0F0Fu), r.ahi.y, s);
+        s = dot4((int)iq4_lut((l.qs.z >> 4) & 0x0F0F0F0Fu), r.ahi.z, s);
+        s = dot4((int)iq4_lut((l.qs.w >> 4) & 0x0F0F0F0Fu), r.ahi.w, s);
+        const unsigned jj = j & 7;
+        const int ls = (int)(((l.hdr.y >> (4 * jj)) & 0xFu) | (((l.hdr.x >> (16 + 2 * jj)) & 3u) << 4));
+        int S = __mul24(ls - 32, s);
+        S += dpp_i<0xB1, 0xf>(S);    // quad_perm [1,0,3,2]
+        S += dpp_i<0x4E, 0xf>(S);    // quad_perm [2,3,0,1]
+        S += dpp_i<0x141, 0xf>(S);   // row_half_mirror: the other quad of the 8
+        const float d = h2f(l.hdr.x) * r.dx;
+        return jj == 0 ? d * (float)S : 0.0f;
     }
 };
 

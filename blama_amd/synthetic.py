@@ -25,6 +25,9 @@ from . import gguf
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
 Q4_0, Q5_0 = 2, 6
 Q3_K = 11
+IQ4_NL, IQ4_XS = 20, 23
+# kvalues_iq4nl (ggml-common.h): the codebook a nibble of IQ4_NL / IQ4_XS indexes
+IQ4_KV = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int32)
 
 
 @dataclass(frozen=True)
@@ -147,6 +150,17 @@ Q3K_CONFIGS = {
     "tinyllama-1.1b-q4_k": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "Q4_K"),
 }
 
+# llama-quantize's IQ4_XS / IQ4_NL files (general.file_type 30 / 25): matrices of the type beside Q5_K
+# ones -- attn_v at a GQA ratio of 4 or more, ffn_down in the first eighth of the layers (here: the
+# first layer) -- with a Q6_K head and token_embd of the file's type.  GQA 4, heads of 64 (the
+# streaming decode step).
+IQ4_CONFIGS = {
+    "tiny-iq4_xs": LlamaConfig("tiny-iq4_xs", 512, 256, 2, 4, 1, 512, 256, 10000.0, 1e-5, "IQ4_XS"),
+    "tiny-iq4_nl": LlamaConfig("tiny-iq4_nl", 512, 256, 2, 4, 1, 512, 256, 10000.0, 1e-5, "IQ4_NL"),
+    # benchmark shape (scripts/iq4_bench.py; its Q4_K yardstick is Q3K_CONFIGS' tinyllama-1.1b-q4_k)
+    "tinyllama-1.1b-iq4_xs": LlamaConfig("TinyLlama-1.1B", 32000, 2048, 22, 32, 4, 5632, 2048, 10000.0, 1e-5, "IQ4_XS"),
+}
+
 
 def use_more_bits(i: int, n: int) -> bool:
     # llama-quant.cpp use_more_bits
@@ -193,7 +207,8 @@ def _gpt2_shapes(cfg) -> dict:
 def tensor_types(cfg: LlamaConfig) -> dict:
     """name -> ggml type for every weight (the Q*_K_M mixes of llama_tensor_get_type)."""
     base = {"Q4_K_M": Q4_K, "Q5_K_M": Q5_K, "Q6_K": Q6_K, "Q8_0": Q8_0, "Q4_K": Q4_K,
-            "Q5_K": Q5_K, "F16": F16, "Q4_0": Q4_0, "Q5_0": Q5_0, "Q3_K_S": Q3_K, "Q3_K_M": Q3_K}[cfg.ftype]
+            "Q5_K": Q5_K, "F16": F16, "Q4_0": Q4_0, "Q5_0": Q5_0, "Q3_K_S": Q3_K, "Q3_K_M": Q3_K,
+            "IQ4_XS": IQ4_XS, "IQ4_NL": IQ4_NL}[cfg.ftype]
     if cfg.arch == "gpt2":
         return _gpt2_types(cfg, base)
     if base == F16:   # the unquantised file convert_hf_to_gguf writes: every matrix F16, the rest F32
@@ -225,6 +240,11 @@ def tensor_types(cfg: LlamaConfig) -> dict:
             t[p + "attn_v.weight"] = Q5_K if i < 2 else Q4_K
             t[p + "attn_output.weight"] = Q4_K
             down = Q5_K if i < n // 16 else Q4_K if use_more_bits(i, n) else Q3_K
+        if cfg.ftype in ("IQ4_XS", "IQ4_NL"):   # llama_tensor_get_type, LLAMA_FTYPE_MOSTLY_IQ4_XS / _NL
+            if cfg.n_head // cfg.n_head_kv >= 4:
+                t[p + "attn_v.weight"] = Q5_K
+            if i < max(1, n // 8):
+                down = Q5_K
         if cfg.n_expert:
             t[p + "ffn_gate_inp.weight"] = F32
             t[p + "ffn_gate_exps.weight"] = base
@@ -297,6 +317,19 @@ def _pack_scales_q3(sc6: np.ndarray) -> np.ndarray:
     return s
 
 
+def _pack_scales_iq4(ls: np.ndarray) -> np.ndarray:
+    """(n, 8) 6-bit scales -> block_iq4_xs's u16 scales_h (bits 2 ib..: the top two bits of scale ib)
+    and scales_l[4] (nibble ib: its low four), 6 bytes."""
+    ls = np.asarray(ls, np.int32)
+    s = np.zeros((ls.shape[0], 6), np.uint8)
+    sh = np.zeros(ls.shape[0], np.uint16)
+    for ib in range(8):
+        sh |= ((ls[:, ib] >> 4) << (2 * ib)).astype(np.uint16)
+        s[:, 2 + ib // 2] |= ((ls[:, ib] & 0xF) << (4 * (ib % 2))).astype(np.uint8)
+    s[:, 0:2] = sh.astype("<u2").view(np.uint8).reshape(-1, 2)
+    return s
+
+
 def fill_quant(view: np.ndarray, t: int, rng, std: float = 0.03):
     """Fill a tensor's bytes with valid random blocks whose dequantised values
     are roughly zero-mean with standard deviation ``std``."""
@@ -344,6 +377,15 @@ def fill_quant(view: np.ndarray, t: int, rng, std: float = 0.03):
             b[:, 96:108] = _pack_scales_q3(32 + mag * sgn)
             d = (std / (19.5 * 8 / np.sqrt(12.0))) * rng.uniform(0.8, 1.2, n)
             b[:, 108:110] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
+        elif t == IQ4_NL:   # uniform codebook entries (rms 67.5)
+            d = (std / 67.5) * rng.uniform(0.8, 1.2, n)
+            b[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
+        elif t == IQ4_XS:   # ... times scales +-(8..31) (rms 20.7)
+            mag = rng.integers(8, 32, size=(n, 8), dtype=np.int32)
+            sgn = rng.integers(0, 2, size=(n, 8), dtype=np.int32) * 2 - 1
+            b[:, 2:8] = _pack_scales_iq4(32 + np.where(sgn > 0, mag, -mag))
+            d = (std / (67.5 * 20.7)) * rng.uniform(0.8, 1.2, n)
+            b[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(n, 2)
         else:
             raise NotImplementedError(t)
 
@@ -449,6 +491,59 @@ def quantize_q3_K_rows(X):
     return pack_q3_K(q, sc + 32, d16)
 
 
+def _pack_iq4_qs(idx) -> np.ndarray:
+    """(n, 32 k) codebook indices -> (n, 16 k) qs bytes: per 32 weights, index j in the low nibble of
+    byte j and index j + 16 in the high one."""
+    e = np.asarray(idx, np.int32).reshape(idx.shape[0], -1, 2, 16)
+    return (e[:, :, 0] | (e[:, :, 1] << 4)).astype(np.uint8).reshape(idx.shape[0], -1)
+
+
+def pack_iq4_nl(idx, d16) -> np.ndarray:
+    """block_iq4_nl (18 B) from codebook indices (n, 32) and f16 d (n,)."""
+    n = idx.shape[0]
+    out = np.empty((n, 18), np.uint8)
+    out[:, 0:2] = np.asarray(d16, np.float16).view(np.uint8).reshape(n, 2)
+    out[:, 2:18] = _pack_iq4_qs(idx)
+    return out
+
+
+def pack_iq4_xs(idx, ls, d16) -> np.ndarray:
+    """block_iq4_xs (136 B) from codebook indices (n, 256), 6-bit scales ls (n, 8) and f16 d (n,)."""
+    n = idx.shape[0]
+    out = np.empty((n, 136), np.uint8)
+    out[:, 0:2] = np.asarray(d16, np.float16).view(np.uint8).reshape(n, 2)
+    out[:, 2:8] = _pack_scales_iq4(ls)
+    out[:, 8:136] = _pack_iq4_qs(idx)
+    return out
+
+
+def _iq4_nearest(v):
+    """index of the codebook entry nearest to v (in codebook units)"""
+    return np.abs(v[..., None] - IQ4_KV.astype(np.float32)).argmin(-1).astype(np.int32)
+
+
+def quantize_iq4_nl_rows(X):
+    """(n, 32) blocks -> block_iq4_nl: d = amax / 127 (the codebook's largest magnitude), the entry
+    nearest x / d."""
+    X = X.reshape(-1, 32)
+    d16 = _f16(np.abs(X).max(1) / 127.0)
+    d = d16.astype(np.float32)
+    return pack_iq4_nl(_iq4_nearest(np.divide(X, d[:, None], out=np.zeros_like(X), where=d[:, None] > 0)), d16)
+
+
+def quantize_iq4_xs_rows(X):
+    """(n, 256) superblocks -> block_iq4_xs: per-32 scale amax / 127 as ls = 32 + 1..31 of d = max
+    scale / 31, the entry nearest x / (d (ls - 32))."""
+    X = X.reshape(-1, 256)
+    n = X.shape[0]
+    s = np.abs(X.reshape(n, 8, 32)).max(2) / 127.0
+    d16 = _f16(s.max(1) / 31.0)
+    d = d16.astype(np.float32)
+    sc = np.clip(np.rint(np.divide(s, d[:, None], out=np.zeros_like(s), where=d[:, None] > 0)), 1, 31).astype(np.int32)
+    eff = np.repeat(d[:, None] * sc, 32, axis=1)
+    return pack_iq4_xs(_iq4_nearest(np.divide(X, eff, out=np.zeros_like(X), where=eff > 0)), sc + 32, d16)
+
+
 def quantize_q45_K_rows(X, q5: bool):
     X = X.reshape(-1, 256)
     n = X.shape[0]
@@ -497,6 +592,10 @@ def quantize_rows(X, t: int) -> np.ndarray:
         return quantize_q45_0_rows(X, t == Q5_0).reshape(-1)
     if t == Q3_K:
         return quantize_q3_K_rows(X).reshape(-1)
+    if t == IQ4_NL:
+        return quantize_iq4_nl_rows(X).reshape(-1)
+    if t == IQ4_XS:
+        return quantize_iq4_xs_rows(X).reshape(-1)
     if t == F32:
         return X.reshape(-1).view(np.uint8)
     if t == F16:
@@ -652,7 +751,7 @@ def build_gguf(cfg: LlamaConfig, seed: int = 0, header_only: bool = False, vocab
     w.add_str("general.name", f"synthetic {cfg.name} {cfg.ftype}")
     w.add_u32("general.file_type", {"Q8_0": 7, "Q4_K_M": 15, "Q5_K_M": 17, "Q6_K": 18,
                                     "Q4_K": 15, "Q5_K": 17, "F16": 1, "Q4_0": 2, "Q5_0": 8,
-                                    "Q3_K_S": 11, "Q3_K_M": 12}[cfg.ftype])
+                                    "Q3_K_S": 11, "Q3_K_M": 12, "IQ4_NL": 25, "IQ4_XS": 30}[cfg.ftype])
     w.add_u32(f"{arch}.context_length", cfg.n_ctx_train)
     w.add_u32(f"{arch}.embedding_length", cfg.n_embd)
     w.add_u32(f"{arch}.block_count", cfg.n_layer)

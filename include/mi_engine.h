@@ -43,9 +43,12 @@ const char* mi_last_error(void);
  * Q4_K / Q5_K / Q6_K / Q8_0 and, in a dense LLaMA-graph model, Q4_0 / Q5_0: llama-quantize's Q4_0 and
  * Q5_0 files -- head Q6_K -- and the tensors it stores as Q4_0 / Q5_0 inside a k-quant file; Q4_0 and
  * Q5_0 matrices take Q8_0 activations as Q8_0 ones do; and Q3_K, id 11: llama-quantize's Q3_K_S /
- * Q3_K_M / Q3_K_L files, Q8_K activations as the other k-quants.  Refused with the tensor and the type
- * by name, vocab_only included: Q4_1, Q5_1 (Q8_1 activations), Q2_K, the IQ and TQ types, and a Q4_0 /
- * Q5_0 / Q3_K matrix in a MoE, GPT-2 or BERT model),
+ * Q3_K_M / Q3_K_L files, Q8_K activations as the other k-quants; and IQ4_NL, id 20, and IQ4_XS, id 23:
+ * llama-quantize's IQ4_NL / IQ4_XS files (file_type 25 / 30: such matrices beside Q5_K ones, head
+ * Q6_K), nibbles indexing the 16-entry codebook kvalues_iq4nl, IQ4_NL over Q8_0 activations and IQ4_XS
+ * over Q8_K ones.  Refused with the tensor and the type by name, vocab_only included: Q4_1, Q5_1 (Q8_1
+ * activations), Q2_K, the other IQ types and the TQ types, and a Q4_0 / Q5_0 / Q3_K / IQ4_NL / IQ4_XS
+ * matrix in a MoE, GPT-2 or BERT model),
  * BERT encoders (F16), and unquantised dense LLaMA-graph models (general.architecture "llama",
  * no experts) whose matrices -- token_embd, output and the seven per layer -- are all F16 with F32
  * norm weights and rope_freqs; without output.weight the head is token_embd (tied models such as
