@@ -13,6 +13,11 @@
 // encode_seqs (mi_encode_seqs) runs the same chain once over several sequences laid end to end:
 // the embedding takes each row's position inside its sequence, the norm and GEMM launches take all
 // rows, the attention is enc_seq.hip's segmented kernel, and one launch pools every sequence.
+//
+// nomic-bert (hp.nomic) runs the same chain on the kernels of enc_nomic.hip: no
+// position add, the call's rope table once, the fused Q|K|V launch with the NEOX rotation in its
+// epilogue, no biases (ENC_ADD), the gate/up pair launch for the FFN.  A sequence of more than
+// ENC_MAX_TOK tokens, of either architecture, runs its attention on enc_attn_long_kernel.
 #include "engine.h"
 
 #include <algorithm>
@@ -20,10 +25,33 @@
 
 namespace mi {
 
+EncGemmRope enc_rope_gemm_of(const __half* wqkv, const float* x, int ntok, int K, int n_head, int head_dim, int n_rot,
+                             const float2* rope, float* q, __half* k, __half* v) {
+    EncGemmRope g{};
+    g.w = wqkv;
+    g.x = x;
+    g.x_stride = K;
+    g.K = K;
+    g.ntok = ntok;
+    g.n_head = n_head;
+    g.head_dim = head_dim;
+    g.n_rot = n_rot;
+    g.rope = rope;
+    g.q = q;
+    g.k = k;
+    g.v = v;
+    g.out_stride = n_head * head_dim;
+    return g;
+}
+
+EncGemmPair enc_swiglu_gemm_of(const __half* gate, const __half* up, int rows, int K, const float* x, int ntok, float* out) {
+    return EncGemmPair{gate, up, rows, K, ntok, x, K, out, rows};
+}
+
 void Ctx::enc_init() {
     const HParams& hp = m->hp;
     enc = true;
-    enc_max = (int)std::min<uint32_t>({n_batch, (uint32_t)ENC_MAX_TOK, (uint32_t)hp.n_ctx_train});
+    enc_max = (int)std::min<uint32_t>({n_batch, (uint32_t)ENC_MAX_SEQ, (uint32_t)hp.n_ctx_train});
     if (enc_max < 1) throw Error("encoder context: no room for a token");
     init_enc_attributes();
     // the row buffers hold a multi-sequence call: up to n_batch rows, ENC_MAX_ROWS at the most
@@ -41,6 +69,7 @@ void Ctx::enc_init() {
     enc_k = mem.dev<__half>(rows * ne);
     enc_v = mem.dev<__half>(rows * ne);
     enc_pool = mem.dev<float>(rows * ne);
+    if (hp.nomic) enc_rope = mem.dev<float2>(rows * (size_t)(hp.n_rot / 2));
     // always in embeddings mode: [n_batch] token rows, the pooled row, the last token's row
     embeddings = true;
     embd = mem.dev<float>(((size_t)n_batch + 2) * ne);
@@ -85,38 +114,47 @@ void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_l
     e.n_embd = ne;
     e.tok = m->tok_embd.p[0];
     e.typ = m->tok_types.p[0];
-    e.pos = m->pos_embd.p[0];
+    e.pos = hp.nomic ? nullptr : m->pos_embd.p[0];   // nomic-bert: no table, Q and K are rotated instead
     e.tok_f16 = m->tok_embd.type == T_F16;
     e.typ_f16 = m->tok_types.type == T_F16;
     e.pos_f16 = m->pos_embd.type == T_F16;
     e.out = enc_a;
     launch_enc_embed(e, stream);
     norm(enc_a, m->embd_norm, m->embd_norm_b, enc_x);
+    // the call's rope table, once: each row at its position inside its sequence
+    if (hp.nomic) launch_enc_rope_table(d_pos, n, hp.n_rot, theta_scale(), hp.freq_scale, enc_rope, stream);
 
     for (int l = 0; l < hp.n_layer; ++l) {
         const EncLayer& L = m->enc_layers[l];
-        EncGemm g{};
-        g.m[0] = EncMat{L.wq, L.bq, ne, enc_q, nullptr};
-        g.m[1] = EncMat{L.wk, L.bk, ne, nullptr, enc_k};
-        g.m[2] = EncMat{L.wv, L.bv, ne, nullptr, enc_v};
-        g.nmat = 3;
-        g.epi = ENC_BIAS;
-        g.K = ne;
-        g.ntok = n;
-        g.x = enc_x;
-        g.x_stride = ne;
-        g.out_stride = ne;
-        launch_enc_gemm(g, stream);
+        if (hp.nomic) {
+            launch_enc_gemm_rope(enc_rope_gemm_of(L.wqkv, enc_x, n, ne, hp.n_head, hp.head_dim, hp.n_rot, enc_rope, enc_q, enc_k, enc_v),
+                                 stream);
+        } else {
+            EncGemm g{};
+            g.m[0] = EncMat{L.wq, L.bq, ne, enc_q, nullptr};
+            g.m[1] = EncMat{L.wk, L.bk, ne, nullptr, enc_k};
+            g.m[2] = EncMat{L.wv, L.bv, ne, nullptr, enc_v};
+            g.nmat = 3;
+            g.epi = ENC_BIAS;
+            g.K = ne;
+            g.ntok = n;
+            g.x = enc_x;
+            g.x_stride = ne;
+            g.out_stride = ne;
+            launch_enc_gemm(g, stream);
+        }
         if (seq_len)
             launch_enc_attn_seq(EncAttnSeq{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o,
                                            d_tiles, seq_len, n_seq},
                                 stream);
         else
             launch_enc_attn(EncAttn{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o}, stream);
-        gemm(ENC_RESID, enc_o, ne, ne, L.wo, L.bo, enc_x, enc_a);
+        // nomic-bert: no biases (ENC_ADD: the residual alone), h = silu(gate x) * (up x) in one launch
+        gemm(hp.nomic ? ENC_ADD : ENC_RESID, enc_o, ne, ne, L.wo, L.bo, enc_x, enc_a);
         norm(enc_a, L.attn_out_norm, L.attn_out_norm_b, enc_x1);
-        gemm(ENC_GELU, enc_x1, ne, nff, L.up, L.bup, nullptr, enc_h);
-        gemm(ENC_RESID, enc_h, nff, ne, L.down, L.bdown, enc_x1, enc_a);
+        if (hp.nomic) launch_enc_gemm_swiglu(enc_swiglu_gemm_of(L.gate, L.up, nff, ne, enc_x1, n, enc_h), stream);
+        else gemm(ENC_GELU, enc_x1, ne, nff, L.up, L.bup, nullptr, enc_h);
+        gemm(hp.nomic ? ENC_ADD : ENC_RESID, enc_h, nff, ne, L.down, L.bdown, enc_x1, enc_a);
         // the last layer's rows are the embeddings (no final norm): token t -> row t of embd
         norm(enc_a, L.layer_out_norm, L.layer_out_norm_b, l == hp.n_layer - 1 ? embd : enc_x);
     }
@@ -125,7 +163,7 @@ void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_l
 int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
     if (n > enc_max)
         throw Error("decode: an encoder call takes at most " + std::to_string(enc_max) +
-                    " tokens (min of n_batch, 512 and n_ctx_train), got " + std::to_string(n));
+                    " tokens (min of n_batch, 2048 and n_ctx_train), got " + std::to_string(n));
     const int ne = m->hp.n_embd;
     const bool pooled = pooling != MI_POOLING_NONE;
     embd_n = n;
@@ -160,7 +198,7 @@ int Ctx::encode_seqs(const int32_t* tokens, const int32_t* seq_len, int n_seq) {
     for (int s = 0; s < n_seq; ++s) {
         if (seq_len[s] < 1 || seq_len[s] > enc_max)
             throw Error("encode_seqs: sequence " + std::to_string(s) + " has " + std::to_string(seq_len[s]) +
-                        " tokens; a sequence takes 1 to " + std::to_string(enc_max) + " (min of n_batch, 512 and n_ctx_train)");
+                        " tokens; a sequence takes 1 to " + std::to_string(enc_max) + " (min of n_batch, 2048 and n_ctx_train)");
         total += seq_len[s];
         if (total > enc_rows)
             throw Error("encode_seqs: the call holds more than " + std::to_string(enc_rows) +

@@ -47,6 +47,8 @@ __device__ __forceinline__ void widen8(const void* tab, int f16, long long i, fl
 }
 
 // ------------------------------------------------------------------ embedding ---
+// POS false: no position table (nomic-bert), x[t] = tok_embd[token t] + token_types[0]
+template <bool POS>
 __global__ __launch_bounds__(256) void enc_embed_kernel(const EncEmbed P) {
     const int t = blockIdx.x;
     const long long tok = P.tokens[t], pos = P.positions ? P.positions[t] : t;
@@ -55,9 +57,9 @@ __global__ __launch_bounds__(256) void enc_embed_kernel(const EncEmbed P) {
         float a[8], b[8], c[8];
         widen8(P.tok, P.tok_f16, tok * P.n_embd + d, a);
         widen8(P.typ, P.typ_f16, d, b);
-        widen8(P.pos, P.pos_f16, pos * P.n_embd + d, c);
+        if (POS) widen8(P.pos, P.pos_f16, pos * P.n_embd + d, c);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = c[e] + (a[e] + b[e]);
+        for (int e = 0; e < 8; ++e) a[e] = POS ? c[e] + (a[e] + b[e]) : a[e] + b[e];
         *reinterpret_cast<float4*>(out + d) = float4{a[0], a[1], a[2], a[3]};
         *reinterpret_cast<float4*>(out + d + 4) = float4{a[4], a[5], a[6], a[7]};
     }
@@ -280,8 +282,9 @@ size_t attn_lds(int ntok, int hd) {
 }  // namespace enc
 
 void launch_enc_embed(const EncEmbed& p, hipStream_t s) {
-    if (p.ntok < 1 || p.n_embd < 8 || p.n_embd % 8 || !p.tokens || !p.tok || !p.typ || !p.pos || !p.out) throw Error("enc embed: unsupported shape");
-    hipLaunchKernelGGL(enc::enc_embed_kernel, dim3(p.ntok), dim3(256), 0, s, p);
+    if (p.ntok < 1 || p.n_embd < 8 || p.n_embd % 8 || !p.tokens || !p.tok || !p.typ || !p.out) throw Error("enc embed: unsupported shape");
+    if (p.pos) hipLaunchKernelGGL(enc::enc_embed_kernel<true>, dim3(p.ntok), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(enc::enc_embed_kernel<false>, dim3(p.ntok), dim3(256), 0, s, p);
     MI_HIP(hipGetLastError());
 }
 
@@ -322,9 +325,15 @@ void init_enc_attributes() {
 }
 
 void launch_enc_attn(const EncAttn& p, hipStream_t s) {
-    if (p.ntok < 1 || p.ntok > ENC_MAX_TOK) throw Error("enc attention: 1 to 512 tokens");
+    if (p.ntok < 1 || p.ntok > ENC_MAX_SEQ) throw Error("enc attention: 1 to 2048 tokens");
     if (!enc_attn_supported(p.head_dim)) throw Error("enc attention: head_dim 32 or 64");
     if (p.n_head < 1 || p.kv_stride % 8 || !p.q || !p.k || !p.v || !p.out) throw Error("enc attention: unsupported shape");
+    if (p.ntok > ENC_MAX_TOK) {   // no [32][n] score matrix fits: the long kernel, the call as one sequence
+        launch_enc_attn_long(EncAttnSeq{p.q, p.k, p.v, p.q_stride, p.kv_stride, p.out_stride, p.n_head, p.head_dim, p.ntok, p.scale,
+                                        p.out, nullptr, nullptr, 1},
+                             (p.ntok + 31) / 32, s);
+        return;
+    }
     const dim3 grid(p.n_head, (p.ntok + 31) / 32), block(64 * enc::AW);
     const size_t lds = enc::attn_lds(p.ntok, p.head_dim);
     if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_kernel<32>, grid, block, lds, s, p);

@@ -219,12 +219,13 @@ void init_attn_seq_attributes() {
 
 }  // namespace enc
 
-int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles) {
-    int start = 0, nt = 0;
+int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long) {
+    int start = 0, n_short = 0, nl = 0;
     for (int s = 0; s < n_seq; ++s) {
         const int len = seq_len[s];
-        if (len < 1 || len > ENC_MAX_TOK)
-            throw Error("encoder sequences: sequence " + std::to_string(s) + " has " + std::to_string(len) + " tokens (1 to 512)");
+        if (len < 1 || len > ENC_MAX_SEQ)
+            throw Error("encoder sequences: sequence " + std::to_string(s) + " has " + std::to_string(len) + " tokens (1 to 2048)");
+        (len > ENC_MAX_TOK ? nl : n_short) += (len + 31) / 32;
         const float inv = 1.0f / (float)len;
         int bits;
         std::memcpy(&bits, &inv, sizeof bits);
@@ -232,14 +233,23 @@ int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles) {
             int* q = seqs + 4 * s;
             q[0] = start, q[1] = len, q[2] = bits, q[3] = 0;
         }
+        start += len;
+    }
+    if (n_long) *n_long = nl;
+    if (!tiles) return n_short + nl;
+    // the short sequences' tiles from 0, the long sequences' from n_short, each group in sequence order
+    int at[2] = {0, n_short};
+    start = 0;
+    for (int s = 0; s < n_seq; ++s) {
+        const int len = seq_len[s];
+        int& nt = at[len > ENC_MAX_TOK];
         for (int off = 0; off < len; off += 32, ++nt) {
-            if (!tiles) continue;
             int* t = tiles + 4 * nt;
             t[0] = start, t[1] = len, t[2] = off, t[3] = s;
         }
         start += len;
     }
-    return nt;
+    return n_short + nl;
 }
 
 void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s) {
@@ -247,19 +257,28 @@ void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s) {
     if (p.n_head < 1 || p.n_seq < 1 || !p.seq_len || !p.tiles || !p.q || !p.k || !p.v || !p.out)
         throw Error("enc attention: unsupported shape");
     if (p.kv_stride % 8 || p.q_stride % 4 || p.out_stride % 4) throw Error("enc attention: kv_stride % 8, q_stride % 4, out_stride % 4");
-    const int n_tiles = enc_seq_lists(p.seq_len, p.n_seq, nullptr, nullptr);   // throws on a length outside 1 .. 512
+    int n_long = 0;
+    const int n_tiles = enc_seq_lists(p.seq_len, p.n_seq, nullptr, nullptr, &n_long);   // throws on a length outside 1 .. 2048
     long long total = 0;
-    int longest = 0;
+    int longest = 0;   // of the sequences this file's kernel takes
     for (int i = 0; i < p.n_seq; ++i) {
         total += p.seq_len[i];
-        longest = std::max(longest, p.seq_len[i]);
+        if (p.seq_len[i] <= ENC_MAX_TOK) longest = std::max(longest, p.seq_len[i]);
     }
     if (total != p.ntok) throw Error("enc attention: the sequence lengths do not sum to ntok");
-    const dim3 grid(p.n_head, n_tiles), block(64 * enc::SW);
-    const size_t lds = enc::attn_seq_lds(longest, p.head_dim);
-    if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_seq_kernel<32>, grid, block, lds, s, p);
-    else hipLaunchKernelGGL(enc::enc_attn_seq_kernel<64>, grid, block, lds, s, p);
-    MI_HIP(hipGetLastError());
+    const int n_short = n_tiles - n_long;
+    if (n_short) {
+        const dim3 grid(p.n_head, n_short), block(64 * enc::SW);
+        const size_t lds = enc::attn_seq_lds(longest, p.head_dim);
+        if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_seq_kernel<32>, grid, block, lds, s, p);
+        else hipLaunchKernelGGL(enc::enc_attn_seq_kernel<64>, grid, block, lds, s, p);
+        MI_HIP(hipGetLastError());
+    }
+    if (n_long) {   // the long sequences' tiles follow the short ones' in the list
+        EncAttnSeq l = p;
+        l.tiles = p.tiles + 4 * n_short;
+        launch_enc_attn_long(l, n_long, s);
+    }
 }
 
 void launch_enc_pool_seq(const EncPoolSeq& p, hipStream_t s) {

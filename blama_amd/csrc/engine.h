@@ -64,6 +64,7 @@ struct HParams {
     float eps = 1e-5f, rope_base = 10000.0f, freq_scale = 1.0f;
     int arch = 0;                       // ARCH_LLAMA (llm_build_llama), ARCH_GPT2 (llm_build_gpt2) or ARCH_BERT (llm_build_bert)
     int pooling_type = -1;              // {arch}.pooling_type (llama_pooling_type), -1: the GGUF has none
+    bool nomic = false;                 // ARCH_BERT from general.architecture "nomic-bert": NEOX RoPE, gated FFN, no biases
 };
 enum { ARCH_LLAMA = 0, ARCH_GPT2 = 1, ARCH_BERT = 2 };
 
@@ -90,7 +91,14 @@ struct EncLayer {
     const float *bq = nullptr, *bk = nullptr, *bv = nullptr, *bo = nullptr, *bup = nullptr, *bdown = nullptr;
     const float *attn_out_norm = nullptr, *attn_out_norm_b = nullptr;     // attn_output_norm
     const float *layer_out_norm = nullptr, *layer_out_norm_b = nullptr;   // layer_output_norm
+    // nomic-bert: the fused attn_qkv [3 n_embd][n_embd] (Q rows, K rows, V rows) instead of wq / wk /
+    // wv, ffn_gate beside ffn_up, and no bias
+    const __half *wqkv = nullptr, *gate = nullptr;
 };
+// The two launches only a nomic-bert layer has, as enc_pass and the op entry points build them
+EncGemmRope enc_rope_gemm_of(const __half* wqkv, const float* x, int ntok, int K, int n_head, int head_dim, int n_rot,
+                             const float2* rope, float* q, __half* k, __half* v);
+EncGemmPair enc_swiglu_gemm_of(const __half* gate, const __half* up, int rows, int K, const float* x, int ntok, float* out);
 
 struct Model {
     HParams hp;
@@ -115,6 +123,10 @@ struct Model {
     // adapters on an F16 model are out of scope: Lora::load refuses it.
     bool f16 = false;
     bool check_f16() const;
+    // A nomic-bert file's tensor table (the header only, so a vocab-only load refuses too): the five
+    // matrices per layer present, F16 and of the graph's shapes (a missing ffn_gate named as such), no
+    // projection bias, no position_embd.weight.  Refused with the tensor's name and the reason.
+    void check_nomic() const;
     // Q4_0 / Q5_0 matrices (32-weight blocks, f16 scale, Q8_0 activations as Q8_0's): served in a
     // dense LLaMA graph, alone (llama-quantize's Q4_0 / Q5_0 files, head Q6_K) or inside a k-quant
     // file.  check_types reads the header only: true when a matrix has one of the two types; refuses,
@@ -331,7 +343,7 @@ struct Ctx {
     // (set_embeddings refuses to turn it off), so every entry point that touches a decoder buffer
     // must either check `embeddings` (the logits reads do) or check `enc` first.
     bool enc = false;
-    int enc_max = 0;                    // tokens a call may hold: min(n_batch, ENC_MAX_TOK, n_ctx_train)
+    int enc_max = 0;                    // tokens a sequence may hold: min(n_batch, ENC_MAX_SEQ, n_ctx_train)
     int enc_rows = 0;                   // token rows the buffers hold: min(n_batch, ENC_MAX_ROWS)
     // a call's upload, packed: n token ids; for mi_encode_seqs also n positions and the int4 lists
     // of enc_seq_lists (sequences, tiles; each of at most n entries) -- at most kEncInts x enc_rows ints
@@ -343,6 +355,7 @@ struct Ctx {
     int* enc_upload_slot();             // the next pinned slot (waits for the ring's copies on wrap)
     float *enc_x = nullptr, *enc_a = nullptr, *enc_x1 = nullptr, *enc_q = nullptr, *enc_o = nullptr, *enc_h = nullptr;
     __half *enc_k = nullptr, *enc_v = nullptr;   // [enc_rows][n_embd] f16 K / V of the layer
+    float2* enc_rope = nullptr;         // nomic-bert: [enc_rows][n_rot / 2] (cos, sin) of the call's rows
     float* enc_pool = nullptr;          // [enc_rows][n_embd] the pooled row of each sequence of mi_encode_seqs
     int enc_nseq = 0;                   // sequences of the last call when it was mi_encode_seqs, else 0
     void enc_init();

@@ -621,10 +621,11 @@ struct EmbdPool {
 void launch_embd_pool(const EmbdPool& p, hipStream_t s);
 
 // ---- encoder models (enc.hip): llm_build_bert, b5187 ----
-constexpr int ENC_MAX_TOK = 512;   // tokens of one sequence (llama.cpp: n_ubatch >= n_tokens for non-causal attention)
+constexpr int ENC_MAX_TOK = 512;   // tokens of a sequence the short attention kernels take (a tile's scores stay in LDS)
+constexpr int ENC_MAX_SEQ = 2048;  // tokens of one sequence: past ENC_MAX_TOK on enc_attn_long_kernel (enc_nomic.hip)
 constexpr int ENC_MAX_ROWS = 8192; // token rows of one call: the sequences of mi_encode_seqs laid end to end
 // out[t] = pos[p] + (tok[tokens[t]] + typ[0]), p = positions ? positions[t] : t: the tables F16
-// (*_f16) or F32 rows of n_embd
+// (*_f16) or F32 rows of n_embd.  pos == nullptr (nomic-bert: rotary positions): out[t] = tok[tokens[t]] + typ[0]
 struct EncEmbed {
     const int* tokens;     // [ntok]
     const int* positions;  // [ntok], or null: the row is the position
@@ -658,6 +659,7 @@ struct EncGemm {
 void launch_enc_gemm(const EncGemm& p, hipStream_t s);
 // Bidirectional attention of ntok tokens over themselves: q f32 [ntok][q_stride], k / v f16
 // [ntok][kv_stride], head h at columns h * head_dim; out f32 [ntok][out_stride].  head_dim 32 or 64.
+// 1 <= ntok <= ENC_MAX_SEQ: up to ENC_MAX_TOK on enc_attn_kernel, past it on enc_attn_long_kernel.
 struct EncAttn {
     const float* q;
     const __half *k, *v;
@@ -672,14 +674,18 @@ void launch_enc_attn(const EncAttn& p, hipStream_t s);
 
 // ---- several sequences per encoder call (enc_seq.hip) ----
 // The call's sequences lie end to end: sequence s owns rows [start_s, start_s + len_s), 1 <= len_s <=
-// ENC_MAX_TOK, and a token attends to the tokens of its own sequence only.  The device lists are
+// ENC_MAX_SEQ, and a token attends to the tokens of its own sequence only.  The device lists are
 // built on the host by enc_seq_lists and uploaded with the tokens:
 //   seqs  [n_seq]   int4 {start, len, bits of 1.0f / len, 0}
 //   tiles [n_tiles] int4 {start, len, offset of the 32-query tile inside the sequence, s}
-// Tiles are counted per sequence (ceil(len / 32) each), so n_tiles <= the call's tokens.
-// Returns n_tiles; throws when a length is outside 1 .. ENC_MAX_TOK (naming the sequence).
-int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles);
-// Attention as EncAttn's, per sequence, on v_mfma_f32_32x32x16_f16; a workgroup per (head, tile).
+// Tiles are counted per sequence (ceil(len / 32) each), so n_tiles <= the call's tokens.  The tiles
+// of the sequences of at most ENC_MAX_TOK tokens come first, in sequence order, then the *n_long
+// tiles of the longer ones: each group is one launch of its own kernel.
+// Returns n_tiles; throws when a length is outside 1 .. ENC_MAX_SEQ (naming the sequence).
+int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long = nullptr);
+// Attention as EncAttn's, per sequence, on v_mfma_f32_32x32x16_f16; a workgroup per (head, tile):
+// enc_attn_seq_kernel for the sequences of at most ENC_MAX_TOK tokens, enc_attn_long_kernel for the
+// longer ones, chosen per sequence by its length alone.
 // A sequence's output rows have the same bits whatever else the call holds.
 struct EncAttnSeq {
     const float* q;        // [ntok][q_stride]
@@ -703,5 +709,39 @@ struct EncPoolSeq {
     float* out;            // [n_seq][K]
 };
 void launch_enc_pool_seq(const EncPoolSeq& p, hipStream_t s);
+
+// ---- nomic-bert (enc_nomic.hip): NEOX RoPE, the gated FFN, sequences past ENC_MAX_TOK ----
+// ggml_rope_cache_init (ext_factor 0, mscale 1) per token row: out [ntok][n_rot / 2] (cos, sin) at
+// position pos[t], or t when pos is null
+void launch_enc_rope_table(const int* pos, int ntok, int n_rot, float theta_scale, float freq_scale, float2* out, hipStream_t s);
+bool enc_rope_supported(int head_dim, int n_rot);   // head_dim 32 or 64; n_rot % 16 == 0, 16 <= n_rot <= head_dim
+// The fused Q|K|V projection with ggml_rope_ext (NEOX) on Q and K in its epilogue: w [3 n_embd][K]
+// (Q rows, K rows, V rows; n_embd = n_head x head_dim), x as EncGemm's; q f32, k (rotated) and v f16,
+// all [ntok][out_stride].  Pair ic < n_rot / 2 of a head: out[ic] = x[ic] cos - x[ic + n_rot / 2] sin,
+// out[ic + n_rot / 2] = x[ic] sin + x[ic + n_rot / 2] cos, (cos, sin) = rope[t][ic]; rows from n_rot are copied.
+struct EncGemmRope {
+    const __half* w;
+    const float* x;        // [ntok][x_stride]
+    int x_stride, K, ntok;
+    int n_head, head_dim, n_rot;
+    const float2* rope;    // [ntok][n_rot / 2], launch_enc_rope_table
+    float* q;
+    __half *k, *v;
+    int out_stride;        // % 8 == 0
+};
+void launch_enc_gemm_rope(const EncGemmRope& p, hipStream_t s);
+// out[t][r] = silu(gate[r] . f16(x[t])) * (up[r] . f16(x[t])): both F16 [rows][K], one launch, no parts
+struct EncGemmPair {
+    const __half *gate, *up;
+    int rows, K, ntok;
+    const float* x;        // [ntok][x_stride]
+    int x_stride;
+    float* out;            // [ntok][out_stride]
+    int out_stride;
+};
+void launch_enc_gemm_swiglu(const EncGemmPair& p, hipStream_t s);
+// enc_attn_long_kernel over n_tiles entries of p.tiles (device), or, p.tiles null, over the
+// (p.ntok + 31) / 32 tiles of one sequence of p.ntok tokens.  p.seq_len / p.n_seq are not read.
+void launch_enc_attn_long(const EncAttnSeq& p, int n_tiles, hipStream_t s);
 
 }  // namespace mi

@@ -213,6 +213,30 @@ bool Model::check_f16() const {
     return true;
 }
 
+void Model::check_nomic() const {
+    if (gguf.tensor("position_embd.weight"))
+        throw Error("tensor position_embd.weight: a nomic-bert model has no position table (its positions are rotary)");
+    const long long E = hp.n_embd, F = hp.n_ff;
+    const struct { const char* name; long long rows, K; } mats[5] = {
+        {"attn_qkv", 3 * E, E}, {"attn_output", E, E}, {"ffn_up", F, E}, {"ffn_gate", F, E}, {"ffn_down", E, F}};
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const std::string b = "blk." + std::to_string(l) + ".";
+        for (const auto& m : mats) {
+            const std::string n = b + m.name + ".weight";
+            const GgufTensor* t = gguf.tensor(n);
+            if (!t)
+                throw Error("GGUF: missing tensor " + n + (std::string(m.name) == "ffn_gate"
+                            ? " (nomic-bert's FFN is gated: silu(gate x) * (up x))" : ""));
+            if (t->type != T_F16)
+                throw Error("tensor " + n + ": a nomic-bert matrix must be F16 (ggml type " + std::to_string(t->type) + " is not served)");
+            if (t->n_dims != 2 || t->ne[0] != m.K || t->ne[1] != m.rows)
+                throw Error("tensor " + n + ": expected " + std::to_string(m.rows) + " x " + std::to_string(m.K) + " (rows x K)");
+            if (gguf.tensor(b + m.name + ".bias"))
+                throw Error("tensor " + b + m.name + ".bias: a projection bias is not served in a nomic-bert model (its graph has none)");
+        }
+    }
+}
+
 bool Model::check_types() const {
     bool any = false;
     // (a MoE model: its expert tensors first, so that the message names one of them)
@@ -351,10 +375,11 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     vocab_only = p.vocab_only != 0;
     gguf.parse(data, size);
     const std::string arch = gguf.get_str("general.architecture", "");
-    if (arch != "llama" && arch != "gpt2" && arch != "bert")
-        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama, gpt2 and bert graphs)");
-    hp.arch = arch == "gpt2" ? ARCH_GPT2 : arch == "bert" ? ARCH_BERT : ARCH_LLAMA;
-    const bool bert = hp.arch == ARCH_BERT;
+    if (arch != "llama" && arch != "gpt2" && arch != "bert" && arch != "nomic-bert")
+        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama, gpt2, bert and nomic-bert graphs)");
+    hp.nomic = arch == "nomic-bert";   // llm_build_bert's nomic branch: an encoder like BERT to every caller
+    hp.arch = arch == "gpt2" ? ARCH_GPT2 : arch == "bert" || hp.nomic ? ARCH_BERT : ARCH_LLAMA;
+    const bool bert = hp.arch == ARCH_BERT, nomic = hp.nomic;
     auto key = [&](const char* k) { return arch + "." + k; };
     hp.n_embd = (int)gguf.get_int(key("embedding_length"), 0);
     hp.n_layer = (int)gguf.get_int(key("block_count"), 0);
@@ -382,8 +407,8 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     hp.head_dim = hp.n_embd / hp.n_head;
     hp.n_rot = hp.arch == ARCH_GPT2 ? 0 : (int)gguf.get_int(key("rope.dimension_count"), hp.head_dim);
     if (hp.arch == ARCH_GPT2 && hp.n_expert) throw Error("gpt2: no MoE");
-    if (bert) {   // llm_build_bert: no RoPE, every head its own K / V, no experts, no output head
-        hp.n_rot = 0;
+    if (bert) {   // llm_build_bert: no RoPE (nomic-bert: NEOX), every head its own K / V, no experts, no output head
+        if (!nomic) hp.n_rot = 0;
         hp.n_head_kv = hp.n_head;
         hp.n_expert = hp.n_expert_used = 0;
         if (gguf.get_int(key("attention.causal"), 0) != 0)
@@ -393,6 +418,13 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         if (hp.n_ff % 32) throw Error("bert: feed_forward_length " + std::to_string(hp.n_ff) + " is not a multiple of 32");
         if (hp.n_embd % hp.n_head || !enc_attn_supported(hp.head_dim))
             throw Error("bert: head_dim " + std::to_string(hp.head_dim) + " is not served (32 or 64)");
+        if (nomic && (hp.n_rot < 2 || hp.n_rot % 2 || hp.n_rot > hp.head_dim))
+            throw Error("nomic-bert: " + key("rope.dimension_count") + " " + std::to_string(hp.n_rot) +
+                        " must be even and at most head_dim " + std::to_string(hp.head_dim));
+        if (nomic && !enc_rope_supported(hp.head_dim, hp.n_rot))   // (enc_nomic.hip: both partners of a pair in one lane)
+            throw Error("nomic-bert: " + key("rope.dimension_count") + " " + std::to_string(hp.n_rot) +
+                        " is not served (the fused Q|K|V launch rotates a multiple of 16 dimensions)");
+        if (nomic) check_nomic();
     }
 
     if (const GgufValue* tv = gguf.get("tokenizer.ggml.tokens")) tokens = tv->arr_s;
@@ -493,7 +525,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     };
     const bool gpt2 = hp.arch == ARCH_GPT2;
     const int i_te = add("token_embd.weight", true, 1);
-    const int i_pe = gpt2 || bert ? add("position_embd.weight", true, 1) : -1;
+    const int i_pe = gpt2 || (bert && !nomic) ? add("position_embd.weight", true, 1) : -1;
     const int i_on = bert ? -1 : add("output_norm.weight", true, 1);
     const int i_onb = gpt2 ? add("output_norm.bias", true, 1) : -1;
     int i_out = bert ? -1 : add("output.weight", false, 1);
@@ -504,6 +536,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     // multiple of a k-quant's 256 -- and tables, F32 biases and LayerNorms
     struct BertIdx {
         int w[6], b[6], an, anb, on, onb;   // q, k, v, o, up, down
+        int qkv = -1, gate = -1;            // nomic-bert: attn_qkv for q, k, v; ffn_gate; no b[]
     };
     std::vector<BertIdx> bi(bert ? hp.n_layer : 0);
     int i_tt = -1, i_en = -1, i_enb = -1;
@@ -529,8 +562,10 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             if (t->ne[0] != hp.n_embd || t->ne[1] < rows_min) throw Error("tensor " + t->name + ": unexpected shape");
         };
         table(i_te, 1);
-        table(i_pe, 1);
-        hp.n_ctx_train = (int)std::min<long long>(hp.n_ctx_train, plan[i_pe].t->ne[1]);   // the position table ends here
+        if (!nomic) {
+            table(i_pe, 1);
+            hp.n_ctx_train = (int)std::min<long long>(hp.n_ctx_train, plan[i_pe].t->ne[1]);   // the position table ends here
+        }
         i_tt = add("token_types.weight", true, 1);
         table(i_tt, 1);
         i_en = bert_vec("token_embd_norm.weight", hp.n_embd);
@@ -541,7 +576,13 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         for (int l = 0; l < hp.n_layer; ++l) {
             const std::string b = "blk." + std::to_string(l) + ".";
             BertIdx& x = bi[l];
-            for (int k = 0; k < 6; ++k) {
+            if (nomic) {   // (types, shapes and the absent biases: check_nomic)
+                x.qkv = add(b + "attn_qkv.weight", true, 1);
+                x.gate = add(b + "ffn_gate.weight", true, 1);
+                for (int k = 3; k < 6; ++k) x.w[k] = add(b + mats[k] + ".weight", true, 1);
+                for (int i : {x.qkv, x.gate, x.w[3], x.w[4], x.w[5]}) weight_bytes += (long long)plan[i].t->nbytes;
+            }
+            for (int k = 0; k < 6 && !nomic; ++k) {
                 x.w[k] = bert_mat(b + mats[k] + ".weight", mrows[k], mK[k]);
                 x.b[k] = bert_vec(b + mats[k] + ".bias", mrows[k]);
                 weight_bytes += (long long)plan[x.w[k]].t->nbytes;
@@ -672,10 +713,15 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
         for (int l = 0; l < hp.n_layer; ++l) {
             EncLayer& L = enc_layers[l];
             const BertIdx& x = bi[l];
-            L.wq = f16p(x.w[0]); L.wk = f16p(x.w[1]); L.wv = f16p(x.w[2]);
             L.wo = f16p(x.w[3]); L.up = f16p(x.w[4]); L.down = f16p(x.w[5]);
-            L.bq = f32p(x.b[0]); L.bk = f32p(x.b[1]); L.bv = f32p(x.b[2]);
-            L.bo = f32p(x.b[3]); L.bup = f32p(x.b[4]); L.bdown = f32p(x.b[5]);
+            if (nomic) {
+                L.wqkv = f16p(x.qkv);
+                L.gate = f16p(x.gate);
+            } else {
+                L.wq = f16p(x.w[0]); L.wk = f16p(x.w[1]); L.wv = f16p(x.w[2]);
+                L.bq = f32p(x.b[0]); L.bk = f32p(x.b[1]); L.bv = f32p(x.b[2]);
+                L.bo = f32p(x.b[3]); L.bup = f32p(x.b[4]); L.bdown = f32p(x.b[5]);
+            }
             L.attn_out_norm = f32p(x.an); L.attn_out_norm_b = f32p(x.anb);
             L.layer_out_norm = f32p(x.on); L.layer_out_norm_b = f32p(x.onb);
         }

@@ -1072,14 +1072,15 @@ int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int3
     MI_TRY(-1)
 }
 
-// Bidirectional attention of ntok tokens over themselves (enc.hip enc_attn_kernel): q f32 [ntok][n_head *
-// head_dim], k / v f16 of the same shape -> out f32; scale 1 / sqrtf(head_dim).
+// Bidirectional attention of ntok tokens over themselves (enc.hip enc_attn_kernel; past 512 tokens
+// enc_nomic.hip enc_attn_long_kernel): q f32 [ntok][n_head * head_dim], k / v f16 of the same shape -> out
+// f32; scale 1 / sqrtf(head_dim).
 int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok, const float* q,
                             const uint16_t* k_f16, const uint16_t* v_f16, float* out) {
     try {
         if (!q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc: null argument");
-        if (n_head < 1 || ntok < 1 || ntok > ENC_MAX_TOK || !enc_attn_supported(head_dim))
-            throw Error("op_attention_enc: head_dim 32 or 64, 1 <= ntok <= 512");
+        if (n_head < 1 || ntok < 1 || ntok > ENC_MAX_SEQ || !enc_attn_supported(head_dim))
+            throw Error("op_attention_enc: head_dim 32 or 64, 1 <= ntok <= 2048");
         MI_HIP(hipSetDevice(device));
         init_enc_attributes();
         const int ne = n_head * head_dim;
@@ -1102,7 +1103,7 @@ int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_di
     try {
         if (!seq_len || !q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc_seqs: null argument");
         if (n_head < 1 || n_seq < 1 || !enc_attn_supported(head_dim)) throw Error("op_attention_enc_seqs: head_dim 32 or 64, n_seq >= 1");
-        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 512
+        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 2048
         enc_seq_lists(seq_len, n_seq, nullptr, tiles.data());
         long long ntok = 0;
         for (int s = 0; s < n_seq; ++s) ntok += seq_len[s];
@@ -1119,6 +1120,54 @@ int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_di
                             nullptr);
         MI_HIP(hipDeviceSynchronize());
         dout.download(out);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// The fused Q|K|V launch of a nomic-bert layer (enc_nomic.hip enc_gemm_rope_kernel): w [3 n_embd][K], n_embd
+// = n_head * head_dim; row t rotated (NEOX, n_rot dimensions of every Q and K head) at positions[t] by the
+// rope table of launch_enc_rope_table.  q f32, k / v f16 bits, all [ntok][n_embd].
+int32_t mi_op_gemm_f16_rope(int32_t device, const uint16_t* w_f16, int32_t n_head, int32_t head_dim, int32_t n_rot, int32_t K,
+                            int32_t ntok, const float* x, const int32_t* positions, float freq_base, float freq_scale,
+                            float* q, uint16_t* k_f16, uint16_t* v_f16) {
+    try {
+        if (!w_f16 || !x || !positions || !q || !k_f16 || !v_f16) throw Error("op_gemm_f16_rope: null argument");
+        if (n_head < 1 || !enc_rope_supported(head_dim, n_rot))
+            throw Error("op_gemm_f16_rope: head_dim 32 or 64, n_rot a multiple of 16 and at most head_dim");
+        if (K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_ROWS) throw Error("op_gemm_f16_rope: K % 32, 1 <= ntok <= 8192");
+        MI_HIP(hipSetDevice(device));
+        const int ne = n_head * head_dim;
+        const size_t n = (size_t)ntok * ne;
+        Dev<__half> dw((size_t)3 * ne * K, f16(w_f16)), dk(n), dv(n);
+        Dev<float> dx((size_t)ntok * K, x), dq(n);
+        Dev<int> dp(ntok, positions);
+        Dev<float2> drope((size_t)ntok * (n_rot / 2));
+        launch_enc_rope_table(dp.p, ntok, n_rot, std::pow(freq_base, -2.0f / (float)n_rot), freq_scale, drope.p, nullptr);
+        launch_enc_gemm_rope(enc_rope_gemm_of(dw.p, dx.p, ntok, K, n_head, head_dim, n_rot, drope.p, dq.p, dk.p, dv.p), nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dq.download(q);
+        dk.download(reinterpret_cast<__half*>(k_f16));
+        dv.download(reinterpret_cast<__half*>(v_f16));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// The gate/up pair launch of a nomic-bert layer (enc_nomic.hip enc_gemm_swiglu_kernel):
+// y[t][r] = silu(gate[r] . f16(x[t])) * (up[r] . f16(x[t])).
+int32_t mi_op_gemm_f16_swiglu(int32_t device, const uint16_t* gate_f16, const uint16_t* up_f16, int32_t rows, int32_t K,
+                              int32_t ntok, const float* x, float* y) {
+    try {
+        if (!gate_f16 || !up_f16 || !x || !y) throw Error("op_gemm_f16_swiglu: null argument");
+        if (rows < 32 || rows % 32 || K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_ROWS)
+            throw Error("op_gemm_f16_swiglu: rows % 32, K % 32, 1 <= ntok <= 8192");
+        MI_HIP(hipSetDevice(device));
+        Dev<__half> dg((size_t)rows * K, f16(gate_f16)), du((size_t)rows * K, f16(up_f16));
+        Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows);
+        launch_enc_gemm_swiglu(enc_swiglu_gemm_of(dg.p, du.p, rows, K, dx.p, ntok, dy.p), nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dy.download(y);
         return 0;
     }
     MI_TRY(-1)

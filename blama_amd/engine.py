@@ -145,6 +145,9 @@ _SIGS = {
     "mi_op_gemm_f16": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "mi_op_attention_enc": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mi_op_attention_enc_seqs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "mi_op_gemm_f16_rope": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                        C.c_float, C.c_float, _P, _P, _P]),
+    "mi_op_gemm_f16_swiglu": (C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_moe_decode": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                      C.c_float, _P, _P, _P, _P, _P]),
 }
@@ -904,3 +907,34 @@ def op_attention_enc_seqs(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, seq_l
     _check(lib().mi_op_attention_enc_seqs(device, n_head, hd, lens.size, _ptr(lens), _ptr(q), _ptr(k16), _ptr(v16),
                                           _ptr(out)), "op_attention_enc_seqs")
     return out
+
+
+def op_gemm_f16_rope(w16: np.ndarray, x: np.ndarray, positions, n_head: int, head_dim: int, n_rot: int,
+                     freq_base: float = 10000.0, freq_scale: float = 1.0, device: int = 0):
+    """mi_op_gemm_f16_rope: w16 (3 * n_head * head_dim, K) float16 (Q rows, K rows, V rows), x (ntok, K) f32,
+    positions (ntok,) -> q (ntok, n_embd) f32, k and v (ntok, n_embd) float16; Q and K rotated NEOX-style."""
+    w16 = np.ascontiguousarray(w16, np.float16)
+    x = np.ascontiguousarray(x, np.float32)
+    pos = np.ascontiguousarray(positions, np.int32)
+    ne, (ntok, K) = n_head * head_dim, x.shape
+    if w16.shape != (3 * ne, K) or pos.shape != (ntok,):
+        raise EngineError(f"op_gemm_f16_rope: w16 {w16.shape} / positions {pos.shape} do not fit x {x.shape}")
+    q = np.empty((ntok, ne), np.float32)
+    k16, v16 = np.empty((ntok, ne), np.float16), np.empty((ntok, ne), np.float16)
+    _check(lib().mi_op_gemm_f16_rope(device, _ptr(w16), n_head, head_dim, n_rot, K, ntok, _ptr(x), _ptr(pos), freq_base,
+                                     freq_scale, _ptr(q), _ptr(k16), _ptr(v16)), "op_gemm_f16_rope")
+    return q, k16, v16
+
+
+def op_gemm_f16_swiglu(gate16: np.ndarray, up16: np.ndarray, x: np.ndarray, device: int = 0) -> np.ndarray:
+    """mi_op_gemm_f16_swiglu: gate16 / up16 (rows, K) float16, x (ntok, K) f32 -> silu(gate x) * (up x), (ntok, rows) f32."""
+    gate16 = np.ascontiguousarray(gate16, np.float16)
+    up16 = np.ascontiguousarray(up16, np.float16)
+    x = np.ascontiguousarray(x, np.float32)
+    rows, K = gate16.shape
+    if up16.shape != (rows, K) or x.shape[1] != K:
+        raise EngineError("op_gemm_f16_swiglu: gate16, up16 and x do not fit")
+    y = np.empty((x.shape[0], rows), np.float32)
+    _check(lib().mi_op_gemm_f16_swiglu(device, _ptr(gate16), _ptr(up16), rows, K, x.shape[0], _ptr(x), _ptr(y)),
+           "op_gemm_f16_swiglu")
+    return y

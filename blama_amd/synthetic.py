@@ -1056,3 +1056,96 @@ def build_bert_gguf(cfg: BertConfig, seed: int = 0, vocab: dict | None = None, h
         view[:] = v.astype(np.float16 if t == F16 else np.float32).view(np.uint8)
 
     return w.to_bytes(fill=fill)
+
+
+# ---- nomic-bert encoder models (llm_build_bert's nomic branch: nomic-embed-text's shape, F16) ----
+
+@dataclass(frozen=True)
+class NomicConfig(BertConfig):
+    freq_base: float = 1000.0         # nomic-embed-text writes 1000
+    n_rot: int = 0                    # > 0: written as nomic-bert.rope.dimension_count (default head_dim)
+
+
+NOMIC_CONFIGS = {
+    # nomic-embed-text's head geometry (head_dim 64, MEAN pooling, freq_base 1000, 2048 trained positions)
+    # at 2 layers and small widths; n_ff no multiple of 128 (a partial workgroup of row tiles)
+    "nomic-s": NomicConfig("nomic-s", 300, 128, 2, 2, 320, 2048, pooling_type=1),
+    # head_dim 32, three heads (a partial workgroup of heads in the Q|K|V launch), half of each head rotated
+    "nomic-h32": NomicConfig("nomic-h32", 300, 96, 2, 3, 256, 2048, n_rot=16),
+}
+
+
+def nomic_tensor_shapes(cfg: NomicConfig) -> dict:
+    d, f = cfg.n_embd, cfg.n_ff
+    s = {"token_embd.weight": (d, cfg.n_vocab), "token_types.weight": (d, cfg.n_token_types),
+         "token_embd_norm.weight": (d,), "token_embd_norm.bias": (d,)}
+    for i in range(cfg.n_layer):
+        p = f"blk.{i}."
+        s[p + "attn_qkv.weight"] = (d, 3 * d)
+        s[p + "attn_output.weight"] = (d, d)
+        s[p + "attn_output_norm.weight"] = (d,)
+        s[p + "attn_output_norm.bias"] = (d,)
+        s[p + "ffn_up.weight"] = (d, f)
+        s[p + "ffn_gate.weight"] = (d, f)
+        s[p + "ffn_down.weight"] = (f, d)
+        s[p + "layer_output_norm.weight"] = (d,)
+        s[p + "layer_output_norm.bias"] = (d,)
+    return s
+
+
+def build_nomic_gguf(cfg: NomicConfig, seed: int = 0, header_only: bool = False, types: dict | None = None, drop=(),
+                     extra: dict | None = None, rope_scaling: str | None = None) -> np.ndarray:
+    """A synthetic nomic-bert GGUF (general.architecture "nomic-bert", llama.cpp b5187's keys and tensor
+    names): the fused attn_qkv (Q rows, K rows, V rows), ffn_gate beside ffn_up, no biases and no position
+    table.  types / drop as build_bert_gguf; extra: {tensor name: shape} added as F16 (2-D) or F32 tensors
+    (for the loader's refusals); rope_scaling: written as nomic-bert.rope.scaling.type."""
+    vocab = bert_vocab(cfg.n_vocab)
+    w = gguf.GGUFWriter()
+    w.add_str("general.architecture", "nomic-bert")
+    w.add_str("general.name", f"synthetic {cfg.name} F16")
+    w.add_u32("general.file_type", 1)
+    w.add_u32("nomic-bert.context_length", cfg.n_ctx_train)
+    w.add_u32("nomic-bert.embedding_length", cfg.n_embd)
+    w.add_u32("nomic-bert.block_count", cfg.n_layer)
+    w.add_u32("nomic-bert.feed_forward_length", cfg.n_ff)
+    w.add_u32("nomic-bert.attention.head_count", cfg.n_head)
+    w.add_f32("nomic-bert.attention.layer_norm_epsilon", cfg.eps)
+    w.add_bool("nomic-bert.attention.causal", False)
+    w.add_f32("nomic-bert.rope.freq_base", cfg.freq_base)
+    if cfg.n_rot:
+        w.add_u32("nomic-bert.rope.dimension_count", cfg.n_rot)
+    if rope_scaling is not None:
+        w.add_str("nomic-bert.rope.scaling.type", rope_scaling)
+    if cfg.pooling_type >= 0:
+        w.add_u32("nomic-bert.pooling_type", cfg.pooling_type)
+    w.add_str("tokenizer.ggml.model", "bert")
+    w.add_array("tokenizer.ggml.tokens", gguf.T_STRING, vocab["tokens"])
+    w.add_array("tokenizer.ggml.token_type", gguf.T_INT32, vocab["types"])
+    w.add_u32("tokenizer.ggml.token_type_count", cfg.n_token_types)
+    w.add_u32("tokenizer.ggml.cls_token_id", vocab["cls"])
+    w.add_u32("tokenizer.ggml.seperator_token_id", vocab["sep"])
+    w.add_u32("tokenizer.ggml.unknown_token_id", vocab["unk"])
+    w.add_u32("tokenizer.ggml.padding_token_id", vocab["pad"])
+    shapes = {**nomic_tensor_shapes(cfg), **(extra or {})}
+    ttypes = {n: (F16 if len(s) == 2 else F32) for n, s in shapes.items()}
+    ttypes.update(types or {})
+    for name, shape in shapes.items():
+        if name not in drop:
+            w.add_tensor(name, ttypes[name], shape)
+    if header_only:
+        return np.frombuffer(w.header_bytes()[0], np.uint8).copy()
+
+    def fill(name, t, shape, view):
+        rng = _rng(seed, name)
+        n = int(np.prod(shape))
+        if name.endswith("norm.weight"):
+            v = rng.uniform(0.8, 1.2, n)
+        elif name.endswith(".bias"):
+            v = rng.standard_normal(n) * 0.05
+        else:   # attn_qkv's Q and K rows at 0.6 / sqrt(d) as _bert_std draws them, its V rows at 1 / sqrt(d)
+            v = rng.standard_normal(n) * _bert_std(cfg, name)
+            if name.endswith("attn_qkv.weight"):
+                v[:2 * cfg.n_embd * cfg.n_embd] *= 0.6
+        view[:] = v.astype(np.float16 if t == F16 else np.float32).view(np.uint8)
+
+    return w.to_bytes(fill=fill)

@@ -224,14 +224,22 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * head_dim 32 or 64; llm_build_bert).  A context on one holds no KV cache and is ALWAYS in
  * embeddings mode, created with the model's pooling type (NONE when the key is absent).  Every
  * mi_decode call is one stateless bidirectional pass: its n tokens take positions 0 .. n - 1, use
- * token type 0 and attend to each other only; n <= min(n_batch, 512, n_ctx_train), more is refused
+ * token type 0 and attend to each other only; n <= min(n_batch, 2048, n_ctx_train), more is refused
  * (< 0, with a message), as are token ids outside the vocabulary.  out_mode, pooling and the rows of
  * mi_embeddings are as above.  On such a context: mi_ctx_set_embeddings(ctx, 0, ..) < 0 (no output
  * head); mi_kv_pos_max is -1 and mi_kv_n_cells 0 always; mi_kv_clear is a no-op; mi_kv_seq_* and
  * mi_ctx_apply_cvec < 0; mi_state_size / mi_state_get / mi_state_set return 0; mi_logits NULL,
- * mi_topk / mi_gather / mi_gather_rows < 0; mi_lora_load on the model is refused.  Not served:
- * quantised or F32 BERT matrices, the nomic / jina variants (RoPE, gated FFN, attention-norm
- * tensors), RANK pooling, token types other than 0.
+ * mi_topk / mi_gather / mi_gather_rows < 0; mi_lora_load on the model is refused.
+ * general.architecture "nomic-bert" (nomic-embed-text v1 / v1.5; llm_build_bert's nomic branch) is
+ * served as such an encoder: no position table -- Q and K are rotated NEOX-style (pair i, i + n_rot / 2;
+ * nomic-bert.rope.freq_base, rope.dimension_count a multiple of 16, linear scaling or none) in the
+ * epilogue of the fused attn_qkv launch --, a gated FFN silu(gate x) * (up x) in one pair launch, no
+ * projection biases.  Its files must hold F16 attn_qkv / attn_output / ffn_up / ffn_gate / ffn_down
+ * matrices and neither a projection bias nor position_embd.weight; anything else is refused at load
+ * (vocab-only too) with the tensor's name.  A sequence of more than 512 tokens (either architecture)
+ * runs its attention on the long-sequence kernel of enc_nomic.hip; shorter ones run the code and
+ * give the bits they always did.  Not served: quantised or F32 encoder matrices, the jina variants
+ * (ALiBi, GELU-PAR), nomic-bert-moe, dynamic NTK scaling, RANK pooling, token types other than 0.
  *
  * Several sequences in one call (an encoder context only): mi_encode_seqs runs ONE pass over n_seq
  * sequences laid end to end in tokens -- sequence s has seq_len[s] tokens at positions 0 ..
@@ -240,7 +248,7 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * n_seq is.  A sequence's rows have the same bits alone and in any batch of sequences.  Refused (< 0,
  * with a message naming the sequence; n_batch is truncated to n_ctx as for every context, so create the
  * context with n_ctx >= the rows a call should hold): a context that is no encoder, n_seq < 1, a length < 1 or >
- * min(512, n_ctx_train), a total above min(n_batch, 8192), a token id outside the vocabulary.
+ * min(n_batch, 2048, n_ctx_train), a total above min(n_batch, 8192), a token id outside the vocabulary.
  * Pooled context: mi_embeddings_seq(ctx, s) is sequence s's row (MEAN = sum_t row_t * (1.0f / len_s)
  * in token order, CLS the first row, LAST the last), and mi_embeddings is refused until the next
  * mi_decode.  Pooling NONE: mi_embeddings(ctx, row) is the row of token `row` of the concatenation
@@ -466,16 +474,33 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
  * rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 8192. */
 int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int32_t K, int32_t ntok,
                        const float* x, const float* bias, const float* resid, int32_t epilogue, float* y);
-/* The encoder pass's bidirectional attention (enc.hip): every token over all ntok <= 512 tokens, no
- * mask, scale 1 / sqrtf(head_dim); q / out: f32 [ntok][n_head * head_dim], k / v: f16 bits of the same
- * shape; head_dim 32 or 64. */
+/* The encoder pass's bidirectional attention (enc.hip; past 512 tokens the long-sequence MFMA kernel
+ * of enc_nomic.hip): every token over all ntok <= 2048 tokens, no mask, scale 1 / sqrtf(head_dim);
+ * q / out: f32 [ntok][n_head * head_dim], k / v: f16 bits of the same shape; head_dim 32 or 64. */
 int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok,
                             const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
 /* The segmented attention of mi_encode_seqs (enc_seq.hip, v_mfma_f32_32x32x16_f16): n_seq sequences laid
- * end to end, sequence s of 1 <= seq_len[s] <= 512 tokens, every token over the tokens of its own
- * sequence only; shapes and scale as mi_op_attention_enc with ntok = the sum of the lengths (<= 8192). */
+ * end to end, sequence s of 1 <= seq_len[s] <= 2048 tokens, every token over the tokens of its own
+ * sequence only; shapes and scale as mi_op_attention_enc with ntok = the sum of the lengths (<= 8192).
+ * A sequence of more than 512 tokens runs on the long-sequence kernel (enc_nomic.hip) in the same call;
+ * the kernel is chosen by the sequence's own length alone. */
 int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
                                  const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
+/* The fused Q|K|V launch of a nomic-bert layer (enc_nomic.hip): the F16 GEMM of mi_op_gemm_f16 over w
+ * [3 n_embd][K] f16 bits (Q rows, K rows, V rows; n_embd = n_head * head_dim) with ggml_rope_ext in
+ * mode NEOX in its epilogue: in every Q and K head, for ic < n_rot / 2, out[ic] = y[ic] cos - y[ic +
+ * n_rot / 2] sin and out[ic + n_rot / 2] = y[ic] sin + y[ic + n_rot / 2] cos with (cos, sin) of
+ * freq_scale * positions[t] * freq_base^(-2 ic / n_rot) (theta iterated in f32 as ggml_rope_cache_init
+ * does); dimensions from n_rot are copied.  x: [ntok][K]; q: f32, k_f16 / v_f16: f16 bits, all
+ * [ntok][n_embd].  head_dim 32 or 64, n_rot a multiple of 16 and <= head_dim, K % 32 == 0, ntok <= 8192. */
+int32_t mi_op_gemm_f16_rope(int32_t device, const uint16_t* w_f16, int32_t n_head, int32_t head_dim, int32_t n_rot, int32_t K,
+                            int32_t ntok, const float* x, const int32_t* positions, float freq_base, float freq_scale,
+                            float* q, uint16_t* k_f16, uint16_t* v_f16);
+/* The gate/up pair launch of a nomic-bert layer (enc_nomic.hip): y[t][r] = silu(g) * u, g and u the F16
+ * GEMMs of mi_op_gemm_f16 (epilogue 0) of gate_f16 and up_f16 ([rows][K] f16 bits) over x [ntok][K],
+ * silu(g) = g / (1 + expf(-g)); y: [ntok][rows]; rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 8192. */
+int32_t mi_op_gemm_f16_swiglu(int32_t device, const uint16_t* gate_f16, const uint16_t* up_f16, int32_t rows, int32_t K,
+                              int32_t ntok, const float* x, float* y);
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);
