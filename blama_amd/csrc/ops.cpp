@@ -220,6 +220,63 @@ void gemm_launches(const QMat& A, const QMat* B, int ntok, const ActQ8& act, flo
     ps.swiglu = B ? rows : 0;
     launch_part_sum(ps, nullptr);
 }
+
+// The first nrow rows of a batch activation (ActQ8, still on the device) back in token order.  q in
+// MFMA-fragment order: element 32 j + 16 h + e of superblock sb of token t; dT [scale][npad]; the
+// 32-element sums byte-split as 64 * hi (bytes 0-7) + lo (bytes 8-15).  Outputs (each nullable):
+// q [nrow][K], d [nrow][K / 256] (Q8_K) or [nrow][K / 32] (Q8_0), and for Q8_K the sums 64 * hi + lo
+// and their raw bytes, [nrow][K / 256][8] each.
+void unpack_act(const ActQ8& a, int nrow, int8_t* q, float* d, int32_t* bsums, int8_t* hi, int8_t* lo) {
+    const int K = a.K, nb = K / 256, nd = a.q80 ? K / 32 : nb;   // nd: scales per row
+    const size_t npad = (size_t)a.npad;
+    if (q) {
+        std::vector<int8_t> hq(npad * K);
+        MI_HIP(hipMemcpy(hq.data(), a.q, hq.size(), hipMemcpyDeviceToHost));
+        for (int t = 0; t < nrow; ++t)
+            for (int sb = 0; sb < nb; ++sb)
+                for (int j = 0; j < 8; ++j)
+                    for (int h = 0; h < 2; ++h)
+                        std::memcpy(q + (size_t)t * K + sb * 256 + 32 * j + 16 * h,
+                                    hq.data() + (((size_t)(t / 32) * nb + sb) * 8 + j) * 1024 + (h * 32 + t % 32) * 16, 16);
+    }
+    if (d) {
+        std::vector<float> hd(npad * nd);
+        MI_HIP(hipMemcpy(hd.data(), a.dT, hd.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int t = 0; t < nrow; ++t)
+            for (int b = 0; b < nd; ++b) d[(size_t)t * nd + b] = hd[(size_t)b * npad + t];
+    }
+    if (a.q80 || (!bsums && !hi && !lo)) return;
+    std::vector<int8_t> hb(npad * nb * 16);
+    MI_HIP(hipMemcpy(hb.data(), a.bsb, hb.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t < nrow; ++t)
+        for (int sb = 0; sb < nb; ++sb) {
+            const int8_t* b = hb.data() + (((size_t)(t / 32) * nb + sb) * 32 + t % 32) * 16;
+            const size_t o = ((size_t)t * nb + sb) * 8;
+            for (int j = 0; j < 8; ++j) {
+                if (bsums) bsums[o + j] = 64 * (int)b[j] + (int)b[8 + j];
+                if (hi) hi[o + j] = b[j];
+                if (lo) lo[o + j] = b[8 + j];
+            }
+        }
+}
+
+// A published activation (act_layout(K, wk, w0), on the device) unpacked: q8k[K], bsums[K/256][16],
+// dk[K/256]; q80[K], d0[K/32] -- a format's buffers all given, or none of them.
+void unpack_published(const Dev<char>& act, int K, int wk, int w0, int8_t* q8k, int32_t* bsums, float* dk, int8_t* q80,
+                      float* d0) {
+    std::vector<char> h(act.n);
+    act.download(h.data());
+    const ActLayout L = act_layout(K, wk, w0);
+    if (wk && q8k) {
+        std::memcpy(q8k, h.data() + L.q8k, (size_t)K);
+        std::memcpy(bsums, h.data() + L.bsum, (size_t)L.nb * 16 * sizeof(int32_t));
+        std::memcpy(dk, h.data() + L.dk, (size_t)L.nb * sizeof(float));
+    }
+    if (w0 && q80) {
+        std::memcpy(q80, h.data() + L.q80, (size_t)K);
+        std::memcpy(d0, h.data() + L.d0, (size_t)L.nb * 8 * sizeof(float));
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -676,7 +733,7 @@ int32_t mi_op_attention_short(int32_t device, int32_t n_head, int32_t n_head_kv,
         }
         const bool q80 = quant == 2;
         const size_t npad = (size_t)(ntok + 31) / 32 * 32;
-        const int nb = K / 256, nd = q80 ? K / 32 : nb;   // scales per row
+        const int nb = K / 256;
         Dev<float> dq((size_t)ntok * K, q), dout((size_t)ntok * K), ddT(quant ? npad * (K / 32) : 1);
         Dev<int8_t> dqa(quant ? npad * K : 1), dbs(quant ? npad * nb * 16 : 1);
         Dev<__half> dkc(kvn, f16(k_f16)), dvc(kvn, f16(v_f16));
@@ -696,25 +753,7 @@ int32_t mi_op_attention_short(int32_t device, int32_t n_head, int32_t n_head_kv,
         MI_HIP(hipDeviceSynchronize());
         dout.download(out);
         if (!quant) return plan.kernel;
-        // the MFMA-fragment order back to token order: element 32 j + 16 h + e of superblock sb
-        std::vector<int8_t> hq(dqa.n), hb(dbs.n);
-        std::vector<float> hd(ddT.n);
-        dqa.download(hq.data());
-        dbs.download(hb.data());
-        ddT.download(hd.data());
-        for (int t = 0; t < ntok; ++t)
-            for (int sb = 0; sb < nb; ++sb) {
-                for (int j = 0; j < 8; ++j)
-                    for (int h = 0; h < 2; ++h)
-                        std::memcpy(q_out + (size_t)t * K + sb * 256 + 32 * j + 16 * h,
-                                    hq.data() + (((size_t)(t / 32) * nb + sb) * 8 + j) * 1024 + (h * 32 + t % 32) * 16, 16);
-                if (q80) continue;
-                // the 32-element sums, byte-split: 64 * hi (bytes 0-7) + lo (bytes 8-15)
-                const int8_t* b = hb.data() + (((size_t)(t / 32) * nb + sb) * 32 + t % 32) * 16;
-                for (int j = 0; j < 8; ++j) bsums_out[((size_t)t * nb + sb) * 8 + j] = 64 * (int)b[j] + (int)b[8 + j];
-            }
-        for (int t = 0; t < ntok; ++t)   // dT [scale][npad] -> [ntok][scale]
-            for (int b = 0; b < nd; ++b) d_out[(size_t)t * nd + b] = hd[(size_t)b * npad + t];
+        unpack_act(a.act_q8, ntok, q_out, d_out, bsums_out, nullptr, nullptr);
         return plan.kernel;
     }
     MI_TRY(-1)
@@ -784,7 +823,7 @@ int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t r
                         const float* x, const float* norm_w, const float* norm_b, float eps, const float* bias,
                         const float* resid, int32_t epilogue, float* y, int8_t* q_out, float* d_out) {
     try {
-        if (!mmq32_supported(type)) throw Error("op_gemm_bias: Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 only");
+        if (!mmq32_supported(type)) throw Error("op_gemm_bias: Q3_K / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0 / Q5_0 / IQ4_NL / IQ4_XS only");
         if (ntok < 1 || ntok > UB_MAX) throw Error("op_gemm_bias: 1..512 token rows");
         if (rows < 1 || K < 256 || K % 256) throw Error("op_gemm_bias: bad shape");
         if (epilogue < 0 || epilogue > 2 || (epilogue == 1 && !resid)) throw Error("op_gemm_bias: epilogue 0 / 1 (with resid) / 2");
@@ -797,7 +836,7 @@ int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t r
         swizzle(A, nullptr, keep);
         const bool q80 = takes_q80(type);
         const size_t npad = (size_t)(ntok + 31) / 32 * 32;
-        const int nb = K / 256, nd = q80 ? K / 32 : nb;   // scales per row
+        const int nb = K / 256;
         Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows), ddT(npad * (K / 32));
         Dev<float> dnw(K, norm_w), dnb(K, norm_b), dbias(rows, bias), dres((size_t)ntok * rows, epilogue == 1 ? resid : nullptr);
         Dev<int8_t> dq(npad * K), dbs(npad * nb * 16);
@@ -822,22 +861,7 @@ int32_t mi_op_gemm_bias(int32_t device, int32_t type, const void* raw, int32_t r
         launch_mmq32(p, act, nullptr, nullptr);
         MI_HIP(hipDeviceSynchronize());
         dy.download(y);
-        if (q_out) {   // the MFMA-fragment order back to token order: element 32 j + 16 h + e of superblock sb
-            std::vector<int8_t> hq(dq.n);
-            dq.download(hq.data());
-            for (int t = 0; t < ntok; ++t)
-                for (int sb = 0; sb < nb; ++sb)
-                    for (int j = 0; j < 8; ++j)
-                        for (int h = 0; h < 2; ++h)
-                            std::memcpy(q_out + (size_t)t * K + sb * 256 + 32 * j + 16 * h,
-                                        hq.data() + (((size_t)(t / 32) * nb + sb) * 8 + j) * 1024 + (h * 32 + t % 32) * 16, 16);
-        }
-        if (d_out) {   // dT [scale][npad] -> [ntok][scale]
-            std::vector<float> hd(ddT.n);
-            ddT.download(hd.data());
-            for (int t = 0; t < ntok; ++t)
-                for (int b = 0; b < nd; ++b) d_out[(size_t)t * nd + b] = hd[(size_t)b * npad + t];
-        }
+        unpack_act(act, ntok, q_out, d_out, nullptr, nullptr, nullptr);
         return 0;
     }
     MI_TRY(-1)
@@ -1168,6 +1192,215 @@ int32_t mi_op_gemm_f16_swiglu(int32_t device, const uint16_t* gate_f16, const ui
         launch_enc_gemm_swiglu(enc_swiglu_gemm_of(dg.p, du.p, rows, K, dx.p, ntok, dy.p), nullptr);
         MI_HIP(hipDeviceSynchronize());
         dy.download(y);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// ---- the kernels between the batch GEMMs (quant_act.hip), and dv_quant_kernel with its norm ----
+// launch_quant_act in any of its modes; every one of the npad rows comes back in token order.  Only
+// what the launcher does not check itself is checked here (the buffers' bounds).
+int32_t mi_op_quant_act(int32_t device, int32_t K, int32_t ntok, const float* x, int32_t x_stride, int32_t n_x_rows,
+                        const float* norm_w, const float* norm_b, float eps, const int32_t* rows, const float* part,
+                        int32_t nks, int32_t swiglu, const float* addend, int32_t q80, int8_t* q_out, float* d_out,
+                        int32_t* bsums_out, int8_t* hi_out, int8_t* lo_out, float* x_out) {
+    try {
+        if (K < 1 || ntok < 1 || ntok > 4 * UB_MAX) throw Error("op_quant_act: bad shape");
+        if (q80 != 0 && q80 != 1) throw Error("op_quant_act: q80 0 (Q8_K) or 1 (Q8_0)");
+        if (!q_out || !d_out || (!q80 && (!bsums_out || !hi_out || !lo_out))) throw Error("op_quant_act: null output");
+        if (x) {
+            if (x_stride < K || x_stride % 4) throw Error("op_quant_act: x_stride must cover K, in whole float4s");
+            if (n_x_rows < (rows ? 1 : ntok)) throw Error("op_quant_act: too few x rows");
+            for (int t = 0; rows && t < ntok; ++t)
+                if (rows[t] >= n_x_rows) throw Error("op_quant_act: row index outside x");
+        }
+        MI_HIP(hipSetDevice(device));
+        const bool nks_ok = nks >= 1 && nks <= 64;   // (else the launcher refuses: nothing of part is read)
+        const size_t npad = (size_t)(ntok + 31) / 32 * 32, nb = K / 256;
+        Dev<float> dx(x ? (size_t)n_x_rows * x_stride : 1, x), dnw(K, norm_w), dnb(K, norm_b), dadd(K, addend);
+        Dev<float> dpart(part && nks_ok ? (size_t)nks * ntok * (swiglu ? 2 : 1) * K : 1, nks_ok ? part : nullptr);
+        Dev<int> drows(ntok, rows);
+        Dev<float> ddT(npad * (K / 32 + 1));
+        Dev<int8_t> dq(npad * K), dbs(npad * (nb + 1) * 16);
+        // what the launch does not write stays recognisable: NaN floats, quants and sum bytes of -128
+        ddT.fill(0xFF);
+        dq.fill(0x80);
+        dbs.fill(0x80);
+        const ActQ8 act{dq.p, ddT.p, dbs.p, K, ntok, (int)npad, q80};
+        QuantAct qa{};
+        qa.x = x ? dx.p : nullptr;
+        qa.x_stride = x_stride;
+        qa.norm_w = norm_w ? dnw.p : nullptr;
+        qa.norm_b = norm_b ? dnb.p : nullptr;
+        qa.eps = eps;
+        qa.rows = rows ? drows.p : nullptr;
+        qa.part = part ? dpart.p : nullptr;
+        qa.nks = nks;
+        qa.swiglu = swiglu;
+        qa.addend = addend ? dadd.p : nullptr;
+        launch_quant_act(qa, act, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        unpack_act(act, (int)npad, q_out, d_out, bsums_out, hi_out, lo_out);
+        if (x && x_out) dx.download(x_out);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// rms_norm(x) * norm_w quantised and multiplied the decode step's two ways: inlaunch 0, dv_quant_kernel
+// with the norm and then the DV_QKV / DV_SWIGLU launch over what it published; inlaunch 1, the launch
+// given x itself (DV_QKVN / DV_SWIGLUN).  rows 0: dv_quant_kernel alone, in the formats of `fmt`.
+int32_t mi_op_dgemv_norm(int32_t device, int32_t inlaunch, int32_t role, int32_t type, const void* raw, int32_t rows,
+                         int32_t K, int32_t type2, const void* raw2, int32_t rows2, const float* x, const float* norm_w,
+                         float eps, float* y, int32_t fmt, int8_t* q8k, int32_t* bsums, float* dk, int8_t* q80, float* d0) {
+    try {
+        if (!x || !norm_w) throw Error("op_dgemv_norm: null argument");
+        if (K < 256 || K % 256) throw Error("op_dgemv_norm: K must be a multiple of 256");
+        if (inlaunch != 0 && inlaunch != 1) throw Error("op_dgemv_norm: inlaunch 0 or 1");
+        if ((q8k != nullptr) != (bsums != nullptr) || (q8k != nullptr) != (dk != nullptr) || (q80 != nullptr) != (d0 != nullptr))
+            throw Error("op_dgemv_norm: a format's buffers go together");
+        if (inlaunch && (q8k || q80)) throw Error("op_dgemv_norm: the in-launch form publishes no activation");
+        const bool gemv = rows > 0;
+        if (!gemv && (inlaunch || fmt < 1 || fmt > 3)) throw Error("op_dgemv_norm: quantise only: inlaunch 0, fmt 1 .. 3");
+        if (gemv && (!raw || !y || (role != 0 && role != 2))) throw Error("op_dgemv_norm: role 0 (Q/K/V) or 2 (SwiGLU)");
+        MI_HIP(hipSetDevice(device));
+        ensure_kernel_attributes(device);
+        Dev<float> dx(K, x), dn(K, norm_w);
+        if (!gemv) {
+            Dev<char> act(dv_act_bytes(K, fmt & 1, fmt >> 1));
+            act.fill(0x80);
+            launch_dv_quant(dx.p, ActOut{K, fmt & 1, fmt >> 1, act.p, dn.p, eps}, nullptr);
+            MI_HIP(hipDeviceSynchronize());
+            unpack_published(act, K, fmt & 1, fmt >> 1, q8k, bsums, dk, q80, d0);
+            return fmt;
+        }
+        const DgemvOp op(role, type, rows, K, type2, raw2, rows2, false);
+        const int wk = op.fmt & 1, w0 = op.fmt >> 1;
+        Keep keep;
+        const QMat a = upload_qmat(type, raw, rows, K, keep);
+        QMat b{};
+        if (op.two) b = upload_qmat(type2, raw2, rows2, K, keep);
+        Dev<float> dy(op.out_rows);
+        Dev<int> dtp(4);
+        Dev<char> act(dv_act_bytes(K, wk, w0));
+        dy.fill(0xFF);
+        dtp.fill(0);
+        act.fill(0x80);
+        GemvParams p = op.params(a, b, act.p, dx.p, dtp.p, nullptr, dy.p);
+        if (inlaunch) {   // the fp32 row and its norm instead of a quantised activation
+            p.act_in = nullptr;
+            p.x[0] = dx.p;
+            p.norm_w = dn.p;
+            p.eps = eps;
+            if (!dgemv_supported(p)) throw Error("op_dgemv_norm: no compiled in-launch variant for this launch");
+        } else {
+            launch_dv_quant(dx.p, ActOut{K, wk, w0, act.p, dn.p, eps}, nullptr);
+        }
+        launch_dgemv(p, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dy.download(y);
+        if (!inlaunch) unpack_published(act, K, wk, w0, q8k, bsums, dk, q80, d0);
+        return op.fmt;
+    }
+    MI_TRY(-1)
+}
+
+// launch_rope_table, then launch_qkv_finish over the parts of a short batch's Q / K / V GEMMs, into
+// caches of n_ctx cells (K and V rows alike: nk == nv) that come back whole.
+int32_t mi_op_qkv_finish(int32_t device, int32_t ntok, int32_t kp, const float* part, int32_t pstride, int32_t nq,
+                         int32_t nk, int32_t nv, int32_t head_dim, int32_t n_rot, float theta_scale, float freq_scale,
+                         const float* freq_factors, const int32_t* tok_pos, const int32_t* tok_cell, int32_t n_ctx,
+                         float* q_out, uint16_t* k_out, uint16_t* v_out, int32_t* cell_pos_out, float* rope_out) {
+    try {
+        if (!part || !tok_pos || !tok_cell || !q_out || !k_out || !v_out || !cell_pos_out || !rope_out)
+            throw Error("op_qkv_finish: null argument");
+        if (ntok < 1 || ntok > MMQS_MAX || kp < 1 || kp > 64) throw Error("op_qkv_finish: 1..64 tokens, 1..64 parts");
+        if (nq < 1 || nk < 1 || nk != nv || head_dim < 1 || n_rot < 0 || n_rot % 2 || n_ctx < 1)
+            throw Error("op_qkv_finish: bad shape (K and V rows alike, n_rot even)");
+        if (pstride < nq + nk + nv || pstride % 2) throw Error("op_qkv_finish: pstride must cover the rows, and be even");
+        for (int t = 0; t < ntok; ++t) {
+            if (tok_cell[t] < 0 || tok_cell[t] >= n_ctx) throw Error("op_qkv_finish: token cell outside the cache");
+            if (t && tok_cell[t] <= tok_cell[t - 1]) throw Error("op_qkv_finish: token cells must ascend");
+        }
+        MI_HIP(hipSetDevice(device));
+        std::vector<int> tp((size_t)ntok * 4, 0);
+        for (int t = 0; t < ntok; ++t) {
+            tp[t * 4 + 1] = tok_pos[t];
+            tp[t * 4 + 2] = tok_cell[t];
+        }
+        const size_t nrope = (size_t)ntok * (n_rot / 2);
+        Dev<float> dpart((size_t)kp * ntok * pstride, part), dq((size_t)ntok * nq), dff(std::max(n_rot / 2, 1), freq_factors);
+        Dev<__half> dkc((size_t)n_ctx * nk), dvc((size_t)n_ctx * nk);
+        Dev<int> dcp(n_ctx), dtp(tp.size(), tp.data());
+        Dev<float2> drope(std::max<size_t>(nrope, 1));
+        // what the launches do not write stays recognisable: NaN floats and halves, cell positions 0x80808080
+        dq.fill(0xFF);
+        dkc.fill(0xFF);
+        dvc.fill(0xFF);
+        drope.fill(0xFF);
+        dcp.fill(0x80);
+        launch_rope_table(dtp.p, ntok, n_rot, theta_scale, freq_scale, freq_factors ? dff.p : nullptr, drope.p, nullptr);
+        QkvFinish F{};
+        F.part = dpart.p;
+        F.pstride = pstride;
+        F.kp = kp;
+        F.ntok = ntok;
+        F.nq = nq;
+        F.nk = nk;
+        F.nv = nv;
+        F.q = dq.p;
+        F.q_stride = nq;
+        F.kcache = dkc.p;
+        F.vcache = dvc.p;
+        F.kv_dim = nk;
+        F.cell_pos = dcp.p;
+        F.tokpos = dtp.p;
+        F.rope = drope.p;
+        F.n_rot = n_rot;
+        F.head_dim = head_dim;
+        launch_qkv_finish(F, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dq.download(q_out);
+        dkc.download(reinterpret_cast<__half*>(k_out));
+        dvc.download(reinterpret_cast<__half*>(v_out));
+        dcp.download(cell_pos_out);
+        if (nrope) MI_HIP(hipMemcpy(rope_out, drope.p, nrope * sizeof(float2), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// launch_part_sum with every PartSum field.  alias: resid is uploaded into the output buffer and read
+// from there (rstride == ostride); otherwise out starts as NaNs.
+int32_t mi_op_part_sum(int32_t device, const float* part, int32_t kp, int32_t ntok, int32_t rows, int32_t pstride,
+                       const float* resid, int32_t rstride, int32_t alias, int32_t ostride, int32_t swiglu,
+                       const float* addend, float* out) {
+    try {
+        if (!part || !out) throw Error("op_part_sum: null argument");
+        if (ntok < 1 || ntok > 4 * UB_MAX || kp < 1 || kp > 64 || rows < 1 || pstride < 1 || swiglu < 0)
+            throw Error("op_part_sum: bad shape");
+        if (ostride < rows || (resid && rstride < rows)) throw Error("op_part_sum: a stride shorter than the rows");
+        if (alias && (!resid || rstride != ostride)) throw Error("op_part_sum: aliasing takes resid, rstride == ostride");
+        MI_HIP(hipSetDevice(device));
+        const size_t no = (size_t)ntok * ostride;
+        Dev<float> dpart((size_t)kp * ntok * pstride, part), dres(resid && !alias ? (size_t)ntok * rstride : 1, alias ? nullptr : resid);
+        Dev<float> dout(no, alias ? resid : nullptr), dadd(rows, addend);
+        if (!alias) dout.fill(0xFF);
+        PartSum ps{};
+        ps.part = dpart.p;
+        ps.kp = kp;
+        ps.ntok = ntok;
+        ps.rows = rows;
+        ps.pstride = pstride;
+        ps.resid = !resid ? nullptr : alias ? dout.p : dres.p;
+        ps.rstride = rstride;
+        ps.out = dout.p;
+        ps.ostride = ostride;
+        ps.swiglu = swiglu;
+        ps.addend = addend ? dadd.p : nullptr;
+        launch_part_sum(ps, nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dout.download(out);
         return 0;
     }
     MI_TRY(-1)

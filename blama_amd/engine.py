@@ -148,6 +148,13 @@ _SIGS = {
     "mi_op_gemm_f16_rope": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                         C.c_float, C.c_float, _P, _P, _P]),
     "mi_op_gemm_f16_swiglu": (C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mi_op_quant_act": (C.c_int32, [C.c_int32] * 3 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P, C.c_int32,
+                                    C.c_int32, _P, C.c_int32] + [_P] * 6),
+    "mi_op_dgemv_norm": (C.c_int32, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
+                                     C.c_float, _P, C.c_int32] + [_P] * 5),
+    "mi_op_qkv_finish": (C.c_int32, [C.c_int32] * 3 + [_P] + [C.c_int32] * 6 + [C.c_float, C.c_float] + [_P] * 3 +
+                         [C.c_int32] + [_P] * 5),
+    "mi_op_part_sum": (C.c_int32, [C.c_int32, _P] + [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [_P, _P]),
     "mi_op_moe_decode": (C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                      C.c_float, _P, _P, _P, _P, _P]),
 }
@@ -938,3 +945,116 @@ def op_gemm_f16_swiglu(gate16: np.ndarray, up16: np.ndarray, x: np.ndarray, devi
     _check(lib().mi_op_gemm_f16_swiglu(device, _ptr(gate16), _ptr(up16), rows, K, x.shape[0], _ptr(x), _ptr(y)),
            "op_gemm_f16_swiglu")
     return y
+
+
+def _opt(a, dtype=np.float32):
+    return None if a is None else np.ascontiguousarray(a, dtype)
+
+
+def _optr(a):
+    return None if a is None else _ptr(a)
+
+
+def op_quant_act(K: int, ntok: int, x=None, norm_w=None, norm_b=None, eps: float = 1e-5, rows=None, part=None,
+                 swiglu: bool = False, addend=None, q80: bool = False, device: int = 0) -> dict:
+    """mi_op_quant_act: launch_quant_act in any mode.  x (n_x_rows, x_stride) f32 or None (swiglu); rows (ntok,)
+    int; part (nks, ntok, K) or, with swiglu, (nks, ntok, 2 K).  Returns a dict over all npad rows in token
+    order: q (npad, K) int8, d (npad, K // 256 or K // 32) f32, for Q8_K bsums / hi / lo (npad, K // 256, 8),
+    and x: the rows after the call (the part mode's write-back)."""
+    x, norm_w, norm_b, part, addend = _opt(x), _opt(norm_w), _opt(norm_b), _opt(part), _opt(addend)
+    rows = _opt(rows, np.int32)
+    if x is not None and x.ndim != 2:
+        raise ValueError("op_quant_act: x is (rows, stride)")
+    if rows is not None and rows.shape != (ntok,):
+        raise ValueError("op_quant_act: rows is (ntok,)")
+    for a in (norm_w, norm_b, addend):
+        if a is not None and a.shape != (K,):
+            raise ValueError("op_quant_act: norm_w / norm_b / addend are (K,)")
+    if part is not None and (part.ndim != 3 or part.shape[1:] != (ntok, (2 if swiglu else 1) * K)):
+        raise ValueError("op_quant_act: part is (nks, ntok, K), with swiglu (nks, ntok, 2 K)")
+    npad, nb = (ntok + 31) // 32 * 32, max(K // 256, 1)
+    r = {"q": np.empty((npad, max(K, 1)), np.int8), "d": np.empty((npad, max(K // 32, 1) if q80 else nb), np.float32),
+         "x": None if x is None else np.empty_like(x)}
+    if not q80:
+        r.update(bsums=np.empty((npad, nb, 8), np.int32), hi=np.empty((npad, nb, 8), np.int8),
+                 lo=np.empty((npad, nb, 8), np.int8))
+    n_x_rows, x_stride = (0, 0) if x is None else x.shape
+    _check(lib().mi_op_quant_act(device, K, ntok, _optr(x), x_stride, n_x_rows, _optr(norm_w), _optr(norm_b), eps,
+                                 _optr(rows), _optr(part), 0 if part is None else part.shape[0], int(bool(swiglu)),
+                                 _optr(addend), int(bool(q80)), _ptr(r["q"]), _ptr(r["d"]), _optr(r.get("bsums")),
+                                 _optr(r.get("hi")), _optr(r.get("lo")), _optr(r["x"])), "op_quant_act")
+    return r
+
+
+def op_dgemv_norm(inlaunch: bool, role: int, type_: int, raw, rows: int, K: int, x: np.ndarray, norm_w: np.ndarray,
+                  eps: float = 1e-5, type2: int = -1, raw2=None, rows2: int = 0, fmt: int = 0, want_act: bool = False,
+                  device: int = 0) -> dict:
+    """mi_op_dgemv_norm: rms_norm(x) * norm_w through dv_quant_kernel and the DV_QKV (role 0) / DV_SWIGLU (role
+    2) launch, or with inlaunch through the launch that norms and quantises x itself.  rows 0 (raw None):
+    the quantiser alone, in the formats of fmt (ATTN_FMT_*).  Returns a dict: y (or None), fmt, and with
+    want_act (not inlaunch) the published activation: q8k (K // 256, 256), bsums (K // 256, 16), dk; q80
+    (K // 32, 32), d0."""
+    x, norm_w = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(norm_w, np.float32)
+    if x.shape != (K,) or norm_w.shape != (K,):
+        raise ValueError("op_dgemv_norm: x and norm_w are (K,)")
+    raw = None if raw is None else np.ascontiguousarray(raw)
+    raw2 = None if raw2 is None else np.ascontiguousarray(raw2)
+    if raw is None:
+        rows = 0
+    out_rows = rows + (rows2 if role == 0 and raw2 is not None else 0)
+    r = {"y": np.empty(out_rows, np.float32) if rows else None}
+    if want_act or not rows:
+        r.update(q8k=np.empty((K // 256, 256), np.int8), bsums=np.empty((K // 256, 16), np.int32),
+                 dk=np.empty(K // 256, np.float32), q80=np.empty((K // 32, 32), np.int8), d0=np.empty(K // 32, np.float32))
+    p = lambda name: _optr(r.get(name))
+    r["fmt"] = _check(lib().mi_op_dgemv_norm(
+        device, int(bool(inlaunch)), role, type_, _optr(raw), rows, K, type2, _optr(raw2), rows2 if raw2 is not None else 0,
+        _ptr(x), _ptr(norm_w), eps, p("y"), fmt, p("q8k"), p("bsums"), p("dk"), p("q80"), p("d0")), "op_dgemv_norm")
+    if not r["fmt"] & ATTN_FMT_Q8K:
+        for k in ("q8k", "bsums", "dk"):
+            r.pop(k, None)
+    if not r["fmt"] & ATTN_FMT_Q80:
+        for k in ("q80", "d0"):
+            r.pop(k, None)
+    return r
+
+
+def op_qkv_finish(part: np.ndarray, nq: int, nk: int, nv: int, head_dim: int, n_rot: int, theta_scale: float,
+                  tok_pos, tok_cell, n_ctx: int, freq_scale: float = 1.0, freq_factors=None, device: int = 0) -> dict:
+    """mi_op_qkv_finish: part (kp, ntok, pstride) f32, rows [Q | K | V].  Returns a dict: q (ntok, nq) f32, k / v
+    (n_ctx, nk) f16 (the whole caches), cell_pos (n_ctx,) int32, rope (ntok, n_rot // 2, 2) f32 (cos, sin);
+    what the launches left untouched is NaN (cell_pos: 0x80808080 as int32)."""
+    part = np.ascontiguousarray(part, np.float32)
+    kp, ntok, pstride = part.shape
+    tpos, tc = np.ascontiguousarray(tok_pos, np.int32), np.ascontiguousarray(tok_cell, np.int32)
+    if tpos.shape != (ntok,) or tc.shape != (ntok,):
+        raise ValueError("op_qkv_finish: tok_pos and tok_cell are (ntok,)")
+    ff = _opt(freq_factors)
+    if ff is not None and ff.shape != (n_rot // 2,):
+        raise ValueError("op_qkv_finish: freq_factors is (n_rot // 2,)")
+    r = {"q": np.empty((ntok, max(nq, 1)), np.float32), "k": np.empty((max(n_ctx, 1), max(nk, 1)), np.float16),
+         "v": np.empty((max(n_ctx, 1), max(nk, 1)), np.float16), "cell_pos": np.empty(max(n_ctx, 1), np.int32),
+         "rope": np.empty((ntok, max(n_rot, 0) // 2, 2), np.float32)}
+    _check(lib().mi_op_qkv_finish(device, ntok, kp, _ptr(part), pstride, nq, nk, nv, head_dim, n_rot, theta_scale,
+                                  freq_scale, _optr(ff), _ptr(tpos), _ptr(tc), n_ctx, _ptr(r["q"]), _ptr(r["k"]),
+                                  _ptr(r["v"]), _ptr(r["cell_pos"]), _ptr(r["rope"])), "op_qkv_finish")
+    return r
+
+
+def op_part_sum(part: np.ndarray, rows: int, resid=None, alias: bool = False, ostride: int | None = None, swiglu: int = 0,
+                addend=None, device: int = 0) -> np.ndarray:
+    """mi_op_part_sum: part (kp, ntok, pstride) f32 -> out (ntok, ostride) f32 (ostride defaults to rows); resid
+    (ntok, rstride); alias: resid is the output buffer.  Elements past `rows` of a row are NaN (aliased: resid's)."""
+    part = np.ascontiguousarray(part, np.float32)
+    kp, ntok, pstride = part.shape
+    resid, addend = _opt(resid), _opt(addend)
+    if resid is not None and (resid.ndim != 2 or resid.shape[0] != ntok):
+        raise ValueError("op_part_sum: resid is (ntok, rstride)")
+    if addend is not None and addend.shape != (rows,):
+        raise ValueError("op_part_sum: addend is (rows,)")
+    ostride = rows if ostride is None else ostride
+    out = np.empty((ntok, max(ostride, 1)), np.float32)
+    _check(lib().mi_op_part_sum(device, _ptr(part), kp, ntok, rows, pstride, _optr(resid),
+                                0 if resid is None else resid.shape[1], int(bool(alias)), ostride, swiglu, _optr(addend),
+                                _ptr(out)), "op_part_sum")
+    return out

@@ -431,6 +431,49 @@ int32_t mi_op_fgemv(int32_t device, int32_t role, const uint16_t* w_f16, int32_t
  * matrix bytes one launch reads.  rows even. */
 int32_t mi_op_fgemv_bench(int32_t device, int32_t role, int32_t rows, int32_t K, int32_t iters, float* median_us,
                           int64_t* bytes);
+/* ---- the kernels between the batch GEMMs (quant_act.hip), and the decode step's normed quantiser ----
+ * launch_quant_act in any of its modes over ntok token rows of K elements (npad = ntok rounded up to
+ * 32 rows are written).  x [n_x_rows][x_stride] (NULL with swiglu); norm_w (RMSNorm) / norm_w and norm_b
+ * (LayerNorm), eps; rows (nullable): token t reads x row rows[t], < 0 a padding row; part (nullable):
+ * [nks][ntok][K] split-K parts, x = (((p0 + p1) + ...) + x) [+ addend[K]] written back and returned in
+ * x_out (nullable) -- or with swiglu 1 [nks][ntok][2 K] gate and up parts, the row silu(sum gate) *
+ * (sum up); q80 0: Q8_K, 1: Q8_0.  Outputs for all npad rows in token order: q_out[npad][K],
+ * d_out[npad][K / 256] (Q8_K) or [npad][K / 32] (Q8_0), and for Q8_K the 32-element sums
+ * bsums_out[npad][K / 256][8] = 64 * hi + lo with their stored bytes hi_out, lo_out (same shape).
+ * What the launch did not write keeps its fill: quants and sum bytes of -128, NaN scales. */
+int32_t mi_op_quant_act(int32_t device, int32_t K, int32_t ntok, const float* x, int32_t x_stride, int32_t n_x_rows,
+                        const float* norm_w, const float* norm_b, float eps, const int32_t* rows, const float* part,
+                        int32_t nks, int32_t swiglu, const float* addend, int32_t q80, int8_t* q_out, float* d_out,
+                        int32_t* bsums_out, int8_t* hi_out, int8_t* lo_out, float* x_out);
+/* rms_norm(x, eps) * norm_w quantised and multiplied as the streaming decode step does it.  role 0:
+ * Q/K/V rows without RoPE (a second matrix = a second segment), 2: the SwiGLU gate/up pair; matrices
+ * as mi_op_dgemv's.  inlaunch 0: the normed quantiser's own launch (dv_quant_kernel), then the GEMV
+ * launch over what it published; 1: the GEMV launch given x itself, every workgroup norming and
+ * quantising it.  With inlaunch 0 the published activation is also returned (a format's buffers all
+ * given or all NULL): q8k[K], bsums[K/256][16], dk[K/256]; q80[K], d0[K/32].  rows 0: the quantiser's
+ * launch alone, any K, in the formats of fmt (bit 0 Q8_K, bit 1 Q8_0); with a GEMV the matrices'
+ * types choose the formats and fmt is ignored.  Returns the formats written, or -1. */
+int32_t mi_op_dgemv_norm(int32_t device, int32_t inlaunch, int32_t role, int32_t type, const void* raw_blocks, int32_t rows,
+                         int32_t K, int32_t type2, const void* raw_blocks2, int32_t rows2, const float* x,
+                         const float* norm_w, float eps, float* y, int32_t fmt, int8_t* q8k, int32_t* bsums, float* dk,
+                         int8_t* q80, float* d0);
+/* A short batch's Q / K / V from the K-parts of their GEMMs: the rope table of the batch
+ * (ggml_rope_cache_init per token, theta_scale given), then part[kp][ntok][pstride] (rows [Q | K | V])
+ * summed in part order, Q and K rotated (rope NORM, the first n_rot of every head_dim), Q to
+ * q_out[ntok][nq], K / V as f16 into caches of n_ctx cells at tok_cell[t] (ascending), tok_pos[t]
+ * into cell_pos.  nk == nv.  k_out / v_out: the whole caches [n_ctx][nk]; cell_pos_out[n_ctx];
+ * rope_out[ntok][n_rot/2][2] (cos, sin).  Untouched elements keep their fill: NaN, cell_pos 0x80808080. */
+int32_t mi_op_qkv_finish(int32_t device, int32_t ntok, int32_t kp, const float* part, int32_t pstride, int32_t nq,
+                         int32_t nk, int32_t nv, int32_t head_dim, int32_t n_rot, float theta_scale, float freq_scale,
+                         const float* freq_factors, const int32_t* tok_pos, const int32_t* tok_cell, int32_t n_ctx,
+                         float* q_out, uint16_t* k_out, uint16_t* v_out, int32_t* cell_pos_out, float* rope_out);
+/* The sum of a short batch's parts: out[t][r] = ((p0 + p1) + ...) over part[kp][ntok][pstride], r < rows;
+ * swiglu > 0: silu(that of row r) * (that of row swiglu + r); then + resid[t * rstride + r] (nullable),
+ * then + addend[r] (nullable).  alias 1: resid is the output buffer itself (rstride == ostride).
+ * out: [ntok][ostride]; elements past `rows` keep their fill (NaN, or resid's when aliased). */
+int32_t mi_op_part_sum(int32_t device, const float* part, int32_t kp, int32_t ntok, int32_t rows, int32_t pstride,
+                       const float* resid, int32_t rstride, int32_t alias, int32_t ostride, int32_t swiglu,
+                       const float* addend, float* out);
 /* ---- the mixture-of-experts kernels, one at a time (build_moe_ffn: softmax gating, top-2) ----
  * The router of ntok token rows x[t * x_stride] (n_embd floats each, x_stride >= n_embd, a
  * multiple of 4): rms_norm(x, eps) * norm_w, logits against w [n_expert][n_embd] (F32), softmax,
