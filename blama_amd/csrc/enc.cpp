@@ -17,7 +17,12 @@
 // nomic-bert (hp.nomic) runs the same chain on the kernels of enc_nomic.hip: no
 // position add, the call's rope table once, the fused Q|K|V launch with the NEOX rotation in its
 // epilogue, no biases (ENC_ADD), the gate/up pair launch for the FFN.  A sequence of more than
-// ENC_MAX_TOK tokens, of either architecture, runs its attention on enc_attn_long_kernel.
+// ENC_MAX_TOK tokens, of any architecture, runs its attention on enc_attn_long_kernel.
+//
+// jina-bert-v2 (hp.jina) is BERT's chain with three differences: no position add,
+// the attention launches take the context's ALiBi slopes, and the FFN's first launch is the GELU-gated
+// pair launch of enc_jina.hip (no bias).  A sequence of more than ENC_MAX_LONG tokens, of any
+// architecture, runs its attention on enc_attn_xlong_kernel.
 #include "engine.h"
 
 #include <algorithm>
@@ -48,6 +53,13 @@ EncGemmPair enc_swiglu_gemm_of(const __half* gate, const __half* up, int rows, i
     return EncGemmPair{gate, up, rows, K, ntok, x, K, out, rows};
 }
 
+EncGemmPair enc_geglu_gemm_of(const __half* gate, const __half* up, int rows, int K, const float* x, int ntok, float* out,
+                              const unsigned short* gelu_tab) {
+    EncGemmPair g = enc_swiglu_gemm_of(gate, up, rows, K, x, ntok, out);
+    g.gelu_tab = gelu_tab;
+    return g;
+}
+
 void Ctx::enc_init() {
     const HParams& hp = m->hp;
     enc = true;
@@ -70,6 +82,12 @@ void Ctx::enc_init() {
     enc_v = mem.dev<__half>(rows * ne);
     enc_pool = mem.dev<float>(rows * ne);
     if (hp.nomic) enc_rope = mem.dev<float2>(rows * (size_t)(hp.n_rot / 2));
+    if (hp.jina) {
+        std::vector<float> sl((size_t)hp.n_head);
+        alibi_slopes(hp.n_head, kJinaMaxAlibiBias, sl.data());
+        enc_slopes = mem.dev<float>(sl.size());
+        MI_HIP(hipMemcpy(enc_slopes, sl.data(), sl.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     // always in embeddings mode: [n_batch] token rows, the pooled row, the last token's row
     embeddings = true;
     embd = mem.dev<float>(((size_t)n_batch + 2) * ne);
@@ -114,7 +132,7 @@ void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_l
     e.n_embd = ne;
     e.tok = m->tok_embd.p[0];
     e.typ = m->tok_types.p[0];
-    e.pos = hp.nomic ? nullptr : m->pos_embd.p[0];   // nomic-bert: no table, Q and K are rotated instead
+    e.pos = hp.nomic || hp.jina ? nullptr : m->pos_embd.p[0];   // nomic-bert: no table, Q and K are rotated instead; jina: ALiBi
     e.tok_f16 = m->tok_embd.type == T_F16;
     e.typ_f16 = m->tok_types.type == T_F16;
     e.pos_f16 = m->pos_embd.type == T_F16;
@@ -145,14 +163,15 @@ void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_l
         }
         if (seq_len)
             launch_enc_attn_seq(EncAttnSeq{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o,
-                                           d_tiles, seq_len, n_seq},
+                                           d_tiles, seq_len, n_seq, enc_slopes},
                                 stream);
         else
-            launch_enc_attn(EncAttn{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o}, stream);
+            launch_enc_attn(EncAttn{enc_q, enc_k, enc_v, ne, ne, ne, hp.n_head, hp.head_dim, n, kq_scale(), enc_o, enc_slopes}, stream);
         // nomic-bert: no biases (ENC_ADD: the residual alone), h = silu(gate x) * (up x) in one launch
         gemm(hp.nomic ? ENC_ADD : ENC_RESID, enc_o, ne, ne, L.wo, L.bo, enc_x, enc_a);
         norm(enc_a, L.attn_out_norm, L.attn_out_norm_b, enc_x1);
         if (hp.nomic) launch_enc_gemm_swiglu(enc_swiglu_gemm_of(L.gate, L.up, nff, ne, enc_x1, n, enc_h), stream);
+        else if (hp.jina) launch_enc_gemm_geglu(enc_geglu_gemm_of(L.gate, L.up, nff, ne, enc_x1, n, enc_h, m->gelu_tab), stream);
         else gemm(ENC_GELU, enc_x1, ne, nff, L.up, L.bup, nullptr, enc_h);
         gemm(hp.nomic ? ENC_ADD : ENC_RESID, enc_h, nff, ne, L.down, L.bdown, enc_x1, enc_a);
         // the last layer's rows are the embeddings (no final norm): token t -> row t of embd
@@ -163,7 +182,7 @@ void Ctx::enc_pass(int n, const int* d_pos, const int* d_tiles, const int* seq_l
 int Ctx::decode_enc(const int32_t* tokens, int n, bool all) {
     if (n > enc_max)
         throw Error("decode: an encoder call takes at most " + std::to_string(enc_max) +
-                    " tokens (min of n_batch, 2048 and n_ctx_train), got " + std::to_string(n));
+                    " tokens (min of n_batch, 8192 and n_ctx_train), got " + std::to_string(n));
     const int ne = m->hp.n_embd;
     const bool pooled = pooling != MI_POOLING_NONE;
     embd_n = n;
@@ -198,7 +217,7 @@ int Ctx::encode_seqs(const int32_t* tokens, const int32_t* seq_len, int n_seq) {
     for (int s = 0; s < n_seq; ++s) {
         if (seq_len[s] < 1 || seq_len[s] > enc_max)
             throw Error("encode_seqs: sequence " + std::to_string(s) + " has " + std::to_string(seq_len[s]) +
-                        " tokens; a sequence takes 1 to " + std::to_string(enc_max) + " (min of n_batch, 2048 and n_ctx_train)");
+                        " tokens; a sequence takes 1 to " + std::to_string(enc_max) + " (min of n_batch, 8192 and n_ctx_train)");
         total += seq_len[s];
         if (total > enc_rows)
             throw Error("encode_seqs: the call holds more than " + std::to_string(enc_rows) +

@@ -25,7 +25,9 @@
 //    arithmetic is attn_mfma.hip's: q rounded to f16, KQ summed in f32, scaled; the two-pass exact
 //    softmax (max, expf, the sum in double, p = e * (float)(1 / sum)); p rounded to f16; PV in f32.
 //    K and V of the head stream through LDS in 64-key chunks; the tile's scores stay in LDS
-//    ([32][n] f32) between the passes.
+//    ([32][n] f32) between the passes.  ALIBI (jina-bert-v2; enc_jina.hip states the arithmetic): the
+//    scaled score of (query i, key j) takes slopes[head] * -(float)|i - j| from the loop's own indices,
+//    and p is not rounded to f16 on its way to PV.
 #include "enc_common.h"
 #include "kernels.h"
 
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(64 * GW) void enc_gemm_f16_kernel(const EncGemm P) 
 constexpr int AW = 4;          // waves per workgroup: 8 of the tile's 32 queries each
 constexpr int CK = 64;         // keys per LDS chunk
 
-template <int HD>
+template <int HD, bool ALIBI>
 __global__ __launch_bounds__(64 * AW) void enc_attn_kernel(const EncAttn P) {
     constexpr int KS = HD + 8;           // halves per staged K / V row
     constexpr int NCH = HD / 8;          // 16-B pieces per row
@@ -217,7 +219,11 @@ __global__ __launch_bounds__(64 * AW) void enc_attn_kernel(const EncAttn P) {
         }
         if (c0 + lane < n) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) sc[(8 * w + j) * npad + c0 + lane] = s[j] * P.scale;
+            for (int j = 0; j < 8; ++j) {
+                float v = s[j] * P.scale;
+                if (ALIBI) v = v + P.slopes[head] * alibi_dist(t0 + 8 * w + j, c0 + lane);
+                sc[(8 * w + j) * npad + c0 + lane] = v;
+            }
         }
     }
     __syncthreads();
@@ -236,7 +242,8 @@ __global__ __launch_bounds__(64 * AW) void enc_attn_kernel(const EncAttn P) {
         }
         sum = wave_sum_d(sum);
         const float inv = (float)(1.0 / sum);
-        for (int c = lane; c < npad; c += 64) row[c] = c < n ? __half2float(__float2half_rn(row[c] * inv)) : 0.0f;
+        // (ALIBI: p stays f32 -- a peaked softmax's f16 rounding would be the pass's largest error; enc_seq.hip)
+        for (int c = lane; c < npad; c += 64) row[c] = c < n ? (ALIBI ? row[c] * inv : __half2float(__float2half_rn(row[c] * inv))) : 0.0f;
     }
     // ---- pass 3: PV, head dimension on the lane (HD 32: the two half-waves take alternate key quads) ----
     constexpr int HV = 64 / HD;          // half-waves sharing a head dimension
@@ -319,25 +326,32 @@ bool enc_attn_supported(int head_dim) { return head_dim == 32 || head_dim == 64;
 // the scores of a 512-token call need more dynamic LDS (81 KiB of the CU's 160) than the default limit
 void init_enc_attributes() {
     const int lds = (int)enc::attn_lds(ENC_MAX_TOK, 64);
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc::enc_attn_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc::enc_attn_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    for (const void* f : {reinterpret_cast<const void*>(enc::enc_attn_kernel<32, false>), reinterpret_cast<const void*>(enc::enc_attn_kernel<64, false>),
+                          reinterpret_cast<const void*>(enc::enc_attn_kernel<32, true>), reinterpret_cast<const void*>(enc::enc_attn_kernel<64, true>)})
+        MI_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     enc::init_attn_seq_attributes();
 }
 
 void launch_enc_attn(const EncAttn& p, hipStream_t s) {
-    if (p.ntok < 1 || p.ntok > ENC_MAX_SEQ) throw Error("enc attention: 1 to 2048 tokens");
+    if (p.ntok < 1 || p.ntok > ENC_MAX_SEQ) throw Error("enc attention: 1 to 8192 tokens");
     if (!enc_attn_supported(p.head_dim)) throw Error("enc attention: head_dim 32 or 64");
     if (p.n_head < 1 || p.kv_stride % 8 || !p.q || !p.k || !p.v || !p.out) throw Error("enc attention: unsupported shape");
-    if (p.ntok > ENC_MAX_TOK) {   // no [32][n] score matrix fits: the long kernel, the call as one sequence
-        launch_enc_attn_long(EncAttnSeq{p.q, p.k, p.v, p.q_stride, p.kv_stride, p.out_stride, p.n_head, p.head_dim, p.ntok, p.scale,
-                                        p.out, nullptr, nullptr, 1},
-                             (p.ntok + 31) / 32, s);
+    if (p.ntok > ENC_MAX_TOK) {   // no [32][n] score matrix fits: the long kernels, the call as one sequence
+        const EncAttnSeq l{p.q, p.k, p.v, p.q_stride, p.kv_stride, p.out_stride, p.n_head, p.head_dim, p.ntok, p.scale,
+                           p.out, nullptr, nullptr, 1, p.slopes};
+        if (p.ntok > ENC_MAX_LONG) launch_enc_attn_xlong(l, (p.ntok + ENC_XL_Q - 1) / ENC_XL_Q, s);
+        else launch_enc_attn_long(l, (p.ntok + 31) / 32, s);
         return;
     }
     const dim3 grid(p.n_head, (p.ntok + 31) / 32), block(64 * enc::AW);
     const size_t lds = enc::attn_lds(p.ntok, p.head_dim);
-    if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_kernel<32>, grid, block, lds, s, p);
-    else hipLaunchKernelGGL(enc::enc_attn_kernel<64>, grid, block, lds, s, p);
+    if (p.slopes) {
+        if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_kernel<32, true>), grid, block, lds, s, p);
+        else hipLaunchKernelGGL((enc::enc_attn_kernel<64, true>), grid, block, lds, s, p);
+    } else {
+        if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_kernel<32, false>), grid, block, lds, s, p);
+        else hipLaunchKernelGGL((enc::enc_attn_kernel<64, false>), grid, block, lds, s, p);
+    }
     MI_HIP(hipGetLastError());
 }
 

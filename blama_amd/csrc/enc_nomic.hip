@@ -54,47 +54,7 @@ __global__ void enc_rope_table_kernel(const int* pos, int ntok, int n_rot, float
 }
 
 // ----------------------------------------------------------------------- GEMMs ---
-constexpr int NW = 4;          // waves per workgroup
-constexpr int NKC = 512;       // activation columns per LDS chunk
-constexpr int NXS = NKC + 8;   // halves per LDS row
-
-// wrow[a]: row (tile a's first row + lane & 31) of the weights, at column 16 (lane >> 5)
-template <int NA>
-__device__ __forceinline__ void gemm_tiles(const __half* const (&wrow)[NA], bool act, const float* x, int x_stride, int K,
-                                           int ntok, int t0, _Float16* xs, f32x16 (&acc)[NA]) {
-    const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][r] = 0.0f;
-    for (int k0 = 0; k0 < K; k0 += NKC) {
-        const int kc = min(NKC, K - k0);
-        const int n4 = kc >> 2;
-        if (k0) __syncthreads();   // the previous chunk is read
-        for (int i = tid; i < 32 * n4; i += 64 * NW) {
-            const int t = i / n4, c = i - t * n4;
-            float4 v = float4{0.0f, 0.0f, 0.0f, 0.0f};   // tokens past ntok: zero columns, never stored
-            if (t0 + t < ntok) v = *reinterpret_cast<const float4*>(x + (long long)(t0 + t) * x_stride + k0 + 4 * c);
-            *reinterpret_cast<u32x2*>(xs + t * NXS + 4 * c) = u32x2{pack2(v.x, v.y), pack2(v.z, v.w)};
-        }
-        __syncthreads();
-        if (act) {
-            const _Float16* xrow = xs + col * NXS + 16 * h;
-            for (int kk = 0; kk < kc; kk += 32) {
-                const u32x4 b0 = *reinterpret_cast<const u32x4*>(xrow + kk);
-                const u32x4 b1 = *reinterpret_cast<const u32x4*>(xrow + kk + 8);
-#pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    const u32x4 a0 = *reinterpret_cast<const u32x4*>(wrow[a] + k0 + kk);
-                    const u32x4 a1 = *reinterpret_cast<const u32x4*>(wrow[a] + k0 + kk + 8);
-                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(a0), as_h8(b0), acc[a], 0, 0, 0);
-                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(a1), as_h8(b1), acc[a], 0, 0, 0);
-                }
-            }
-        }
-    }
-}
-
+// (gemm_tiles<NA>, NW, NKC, NXS: enc_common.h, shared with enc_jina.hip)
 template <int HD>
 __global__ __launch_bounds__(64 * NW) void enc_gemm_rope_kernel(const EncGemmRope P) {
     constexpr int NA = HD / 32;    // accumulator sets: the head's 32-row tiles
@@ -191,7 +151,9 @@ struct LongLds {
     static constexpr int bytes = pv_end > red_end ? pv_end : red_end;
 };
 
-template <int HD>
+// ALIBI (jina-bert-v2; enc_jina.hip states the arithmetic): every recomputed score takes slopes[head] *
+// -(float)|query - key| after the scale, from the D layout's indices.
+template <int HD, bool ALIBI>
 __global__ __launch_bounds__(64 * LW) void enc_attn_long_kernel(const EncAttnSeq P) {
     using L = LongLds<HD>;
     constexpr int QS = L::QS, RS = L::RS, NJ = HD / 16, NH = HD / 32;
@@ -238,6 +200,11 @@ __global__ __launch_bounds__(64 * LW) void enc_attn_long_kernel(const EncAttnSeq
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = acc[r] * P.scale;
+        if (ALIBI) {
+            const float m = P.slopes[head];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = acc[r] + m * alibi_dist(off + col, kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
+        }
         return acc;
     };
     auto key_of = [&](int kb, int r) { return kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -377,10 +344,15 @@ void launch_enc_attn_long(const EncAttnSeq& p, int n_tiles, hipStream_t s) {
     if (!enc_attn_supported(p.head_dim)) throw Error("enc attention: head_dim 32 or 64");
     if (p.n_head < 1 || n_tiles < 1 || !p.q || !p.k || !p.v || !p.out) throw Error("enc attention: unsupported shape");
     if (p.kv_stride % 8 || p.q_stride % 4 || p.out_stride % 4) throw Error("enc attention: kv_stride % 8, q_stride % 4, out_stride % 4");
-    if (!p.tiles && (p.ntok < 1 || p.ntok > ENC_MAX_SEQ || n_tiles != (p.ntok + 31) / 32)) throw Error("enc attention: 1 to 2048 tokens");
+    if (!p.tiles && (p.ntok < 1 || p.ntok > ENC_MAX_LONG || n_tiles != (p.ntok + 31) / 32)) throw Error("enc attention: 1 to 2048 tokens");
     const dim3 grid(p.n_head, n_tiles), block(64 * enc::LW);
-    if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_long_kernel<32>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(enc::enc_attn_long_kernel<64>, grid, block, 0, s, p);
+    if (p.slopes) {
+        if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_long_kernel<32, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((enc::enc_attn_long_kernel<64, true>), grid, block, 0, s, p);
+    } else {
+        if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_long_kernel<32, false>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((enc::enc_attn_long_kernel<64, false>), grid, block, 0, s, p);
+    }
     MI_HIP(hipGetLastError());
 }
 

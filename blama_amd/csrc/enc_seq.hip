@@ -32,6 +32,13 @@
 //    addition above is a function of (len, tile offset, HD) alone -- never of start, of the number
 //    of sequences or of another sequence's contents.  A sequence's output rows therefore have the
 //    same bits alone and in any batch.
+//    ALIBI (jina-bert-v2; enc_jina.hip states the arithmetic): the scaled score takes slopes[head] *
+//    -(float)|query - key| from the D layout's indices before it goes to LDS.  ALiBi makes the softmax
+//    of a short sequence peaked, and the f16 rounding of a large p is then the pass's largest error
+//    (2^-12 of p on average, straight into the output), so this variant carries the rounding's residual:
+//    the softmax leaves p as f32 in the score row beside its f16 value, and PV runs a second MFMA on
+//    lo = f16(p - (float)f16(p)) read from there.  The LDS layout is the same; the score rows are read
+//    until the end of PV, so one barrier more stands before the partial tiles go over them.
 //    LDS at len 512, HD 64: 66048 (scores) + 33280 (p) + 4608 (q) + 17408 (V chunk) = 121344 bytes
 //    of the CU's 160 KiB.  The launch is sized by its longest sequence.
 //  * enc_pool_seq_kernel: a workgroup per (sequence, 64 columns); embd_pool_kernel's arithmetic.
@@ -59,7 +66,7 @@ static size_t attn_seq_lds(int len, int hd) {
     return (size_t)seq_sc_floats(npad) * 4 + 32 * (size_t)(npad + 8) * 2 + 32 * (size_t)(hd + 8) * 2 + (size_t)hd * VS * 2;
 }
 
-template <int HD>
+template <int HD, bool ALIBI>
 __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq P) {
     constexpr int QS = HD + 8;           // halves per staged q row
     constexpr int NJ = HD / 16;          // MFMAs per 32-key block of QK^T
@@ -101,9 +108,18 @@ __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq 
         }
         float* srow = sc + col * SP + kb * 32 + 4 * h;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<float4*>(srow + 8 * q) =
-                float4{acc[4 * q] * P.scale, acc[4 * q + 1] * P.scale, acc[4 * q + 2] * P.scale, acc[4 * q + 3] * P.scale};
+        for (int q = 0; q < 4; ++q) {
+            float4 v = float4{acc[4 * q] * P.scale, acc[4 * q + 1] * P.scale, acc[4 * q + 2] * P.scale, acc[4 * q + 3] * P.scale};
+            if (ALIBI) {   // register 4 q + e of the lane's query off + col is key 32 kb + 8 q + 4 h + e
+                const float m = P.slopes[head];
+                const int qi = off + col, k0 = kb * 32 + 8 * q + 4 * h;
+                v.x = v.x + m * alibi_dist(qi, k0);
+                v.y = v.y + m * alibi_dist(qi, k0 + 1);
+                v.z = v.z + m * alibi_dist(qi, k0 + 2);
+                v.w = v.w + m * alibi_dist(qi, k0 + 3);
+            }
+            *reinterpret_cast<float4*>(srow + 8 * q) = v;
+        }
     }
     __syncthreads();
 
@@ -113,7 +129,10 @@ __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq 
         float* row = sc + r * SP;
         _Float16* prow = ph + r * PS;
         if (r >= live) {
-            for (int c = lane; c < npad; c += 64) prow[c] = (_Float16)0.0f;
+            for (int c = lane; c < npad; c += 64) {
+                prow[c] = (_Float16)0.0f;
+                if (ALIBI) row[c] = 0.0f;
+            }
             continue;
         }
         float mx = -INFINITY;
@@ -128,7 +147,11 @@ __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq 
         }
         sum = wave_sum_d(sum);
         const float inv = (float)(1.0 / sum);
-        for (int c = lane; c < npad; c += 64) prow[c] = c < len ? (_Float16)(row[c] * inv) : (_Float16)0.0f;
+        for (int c = lane; c < npad; c += 64) {
+            const float p = c < len ? row[c] * inv : 0.0f;
+            prow[c] = (_Float16)p;
+            if (ALIBI) row[c] = p;   // the f32 value, for the residual of the rounding
+        }
     }
 
     // ---- PV: D lane = query, registers = head dimensions of this wave's 32-column half ----
@@ -160,6 +183,14 @@ __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq 
                 const u32x4 a = *reinterpret_cast<const u32x4*>(vt + (32 * dh + col) * VS + 32 * kbl + 16 * j + 8 * h);
                 const u32x4 b = *reinterpret_cast<const u32x4*>(ph + col * PS + c0 + 32 * kbl + 16 * j + 8 * h);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(a), as_h8(b), acc, 0, 0, 0);
+                if (ALIBI) {   // + V (p - f16(p)): the same 8 keys of the lane's query, from the f32 row
+                    const float* pf = sc + col * SP + c0 + 32 * kbl + 16 * j + 8 * h;
+                    const float4 x = *reinterpret_cast<const float4*>(pf), y = *reinterpret_cast<const float4*>(pf + 4);
+                    const half8 hi = as_h8(b);
+                    const u32x4 lo = u32x4{pack2(x.x - (float)hi[0], x.y - (float)hi[1]), pack2(x.z - (float)hi[2], x.w - (float)hi[3]),
+                                           pack2(y.x - (float)hi[4], y.y - (float)hi[5]), pack2(y.z - (float)hi[6], y.w - (float)hi[7])};
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(a), as_h8(lo), acc, 0, 0, 0);
+                }
             }
         };
         if (HD == 32) {
@@ -170,6 +201,7 @@ __global__ __launch_bounds__(64 * SW) void enc_attn_seq_kernel(const EncAttnSeq 
         }
     }
     // every wave passed a barrier since its last read of the scores: the partial tiles go there
+    if (ALIBI) __syncthreads();   // (this variant read them in PV)
     float* red = sc;   // [SW][32][RS]
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -213,19 +245,24 @@ __global__ __launch_bounds__(64) void enc_pool_seq_kernel(const EncPoolSeq P) {
 
 void init_attn_seq_attributes() {
     const int lds = (int)attn_seq_lds(ENC_MAX_TOK, 64);
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_seq_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_seq_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    for (const void* f : {reinterpret_cast<const void*>(enc_attn_seq_kernel<32, false>), reinterpret_cast<const void*>(enc_attn_seq_kernel<64, false>),
+                          reinterpret_cast<const void*>(enc_attn_seq_kernel<32, true>), reinterpret_cast<const void*>(enc_attn_seq_kernel<64, true>)})
+        MI_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
 }
 
 }  // namespace enc
 
-int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long) {
-    int start = 0, n_short = 0, nl = 0;
+// the launch group of a sequence by its own length alone: 0 short, 1 long, 2 past ENC_MAX_LONG
+static int seq_group(int len) { return len > ENC_MAX_LONG ? 2 : len > ENC_MAX_TOK ? 1 : 0; }
+
+int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long, int* n_xlong) {
+    int start = 0, cnt[3] = {0, 0, 0};
     for (int s = 0; s < n_seq; ++s) {
         const int len = seq_len[s];
         if (len < 1 || len > ENC_MAX_SEQ)
-            throw Error("encoder sequences: sequence " + std::to_string(s) + " has " + std::to_string(len) + " tokens (1 to 2048)");
-        (len > ENC_MAX_TOK ? nl : n_short) += (len + 31) / 32;
+            throw Error("encoder sequences: sequence " + std::to_string(s) + " has " + std::to_string(len) + " tokens (1 to 8192)");
+        const int g = seq_group(len), step = g == 2 ? ENC_XL_Q : 32;
+        cnt[g] += (len + step - 1) / step;
         const float inv = 1.0f / (float)len;
         int bits;
         std::memcpy(&bits, &inv, sizeof bits);
@@ -235,21 +272,24 @@ int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_l
         }
         start += len;
     }
-    if (n_long) *n_long = nl;
-    if (!tiles) return n_short + nl;
-    // the short sequences' tiles from 0, the long sequences' from n_short, each group in sequence order
-    int at[2] = {0, n_short};
+    if (n_long) *n_long = cnt[1];
+    if (n_xlong) *n_xlong = cnt[2];
+    const int total = cnt[0] + cnt[1] + cnt[2];
+    if (!tiles) return total;
+    // the short sequences' tiles from 0, then the long sequences', then the 128-query groups of the
+    // sequences past ENC_MAX_LONG; each group in sequence order
+    int at[3] = {0, cnt[0], cnt[0] + cnt[1]};
     start = 0;
     for (int s = 0; s < n_seq; ++s) {
-        const int len = seq_len[s];
-        int& nt = at[len > ENC_MAX_TOK];
-        for (int off = 0; off < len; off += 32, ++nt) {
+        const int len = seq_len[s], g = seq_group(len);
+        int& nt = at[g];
+        for (int off = 0; off < len; off += g == 2 ? ENC_XL_Q : 32, ++nt) {
             int* t = tiles + 4 * nt;
             t[0] = start, t[1] = len, t[2] = off, t[3] = s;
         }
         start += len;
     }
-    return n_short + nl;
+    return total;
 }
 
 void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s) {
@@ -257,8 +297,8 @@ void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s) {
     if (p.n_head < 1 || p.n_seq < 1 || !p.seq_len || !p.tiles || !p.q || !p.k || !p.v || !p.out)
         throw Error("enc attention: unsupported shape");
     if (p.kv_stride % 8 || p.q_stride % 4 || p.out_stride % 4) throw Error("enc attention: kv_stride % 8, q_stride % 4, out_stride % 4");
-    int n_long = 0;
-    const int n_tiles = enc_seq_lists(p.seq_len, p.n_seq, nullptr, nullptr, &n_long);   // throws on a length outside 1 .. 2048
+    int n_long = 0, n_xlong = 0;
+    const int n_tiles = enc_seq_lists(p.seq_len, p.n_seq, nullptr, nullptr, &n_long, &n_xlong);   // throws on a length outside 1 .. 8192
     long long total = 0;
     int longest = 0;   // of the sequences this file's kernel takes
     for (int i = 0; i < p.n_seq; ++i) {
@@ -266,18 +306,28 @@ void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s) {
         if (p.seq_len[i] <= ENC_MAX_TOK) longest = std::max(longest, p.seq_len[i]);
     }
     if (total != p.ntok) throw Error("enc attention: the sequence lengths do not sum to ntok");
-    const int n_short = n_tiles - n_long;
+    const int n_short = n_tiles - n_long - n_xlong;
     if (n_short) {
         const dim3 grid(p.n_head, n_short), block(64 * enc::SW);
         const size_t lds = enc::attn_seq_lds(longest, p.head_dim);
-        if (p.head_dim == 32) hipLaunchKernelGGL(enc::enc_attn_seq_kernel<32>, grid, block, lds, s, p);
-        else hipLaunchKernelGGL(enc::enc_attn_seq_kernel<64>, grid, block, lds, s, p);
+        if (p.slopes) {
+            if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_seq_kernel<32, true>), grid, block, lds, s, p);
+            else hipLaunchKernelGGL((enc::enc_attn_seq_kernel<64, true>), grid, block, lds, s, p);
+        } else {
+            if (p.head_dim == 32) hipLaunchKernelGGL((enc::enc_attn_seq_kernel<32, false>), grid, block, lds, s, p);
+            else hipLaunchKernelGGL((enc::enc_attn_seq_kernel<64, false>), grid, block, lds, s, p);
+        }
         MI_HIP(hipGetLastError());
     }
     if (n_long) {   // the long sequences' tiles follow the short ones' in the list
         EncAttnSeq l = p;
         l.tiles = p.tiles + 4 * n_short;
         launch_enc_attn_long(l, n_long, s);
+    }
+    if (n_xlong) {  // and the groups of the sequences past ENC_MAX_LONG follow those
+        EncAttnSeq l = p;
+        l.tiles = p.tiles + 4 * (n_short + n_long);
+        launch_enc_attn_xlong(l, n_xlong, s);
     }
 }
 

@@ -65,6 +65,7 @@ struct HParams {
     int arch = 0;                       // ARCH_LLAMA (llm_build_llama), ARCH_GPT2 (llm_build_gpt2) or ARCH_BERT (llm_build_bert)
     int pooling_type = -1;              // {arch}.pooling_type (llama_pooling_type), -1: the GGUF has none
     bool nomic = false;                 // ARCH_BERT from general.architecture "nomic-bert": NEOX RoPE, gated FFN, no biases
+    bool jina = false;                  // ARCH_BERT from "jina-bert-v2": ALiBi (max bias 8), GELU-gated FFN, BERT's biases but ffn_up's
 };
 enum { ARCH_LLAMA = 0, ARCH_GPT2 = 1, ARCH_BERT = 2 };
 
@@ -92,13 +93,18 @@ struct EncLayer {
     const float *attn_out_norm = nullptr, *attn_out_norm_b = nullptr;     // attn_output_norm
     const float *layer_out_norm = nullptr, *layer_out_norm_b = nullptr;   // layer_output_norm
     // nomic-bert: the fused attn_qkv [3 n_embd][n_embd] (Q rows, K rows, V rows) instead of wq / wk /
-    // wv, ffn_gate beside ffn_up, and no bias
+    // wv, ffn_gate beside ffn_up, and no bias.  jina-bert-v2: BERT's matrices and biases, ffn_gate
+    // beside ffn_up, neither of the two with a bias
     const __half *wqkv = nullptr, *gate = nullptr;
 };
 // The two launches only a nomic-bert layer has, as enc_pass and the op entry points build them
 EncGemmRope enc_rope_gemm_of(const __half* wqkv, const float* x, int ntok, int K, int n_head, int head_dim, int n_rot,
                              const float2* rope, float* q, __half* k, __half* v);
 EncGemmPair enc_swiglu_gemm_of(const __half* gate, const __half* up, int rows, int K, const float* x, int ntok, float* out);
+// The pair launch of a jina-bert-v2 layer: the same with the GELU table
+EncGemmPair enc_geglu_gemm_of(const __half* gate, const __half* up, int rows, int K, const float* x, int ntok, float* out,
+                              const unsigned short* gelu_tab);
+constexpr float kJinaMaxAlibiBias = 8.0f;   // hparams.f_max_alibi_bias of LLM_ARCH_JINA_BERT_V2
 
 struct Model {
     HParams hp;
@@ -127,6 +133,10 @@ struct Model {
     // matrices per layer present, F16 and of the graph's shapes (a missing ffn_gate named as such), no
     // projection bias, no position_embd.weight.  Refused with the tensor's name and the reason.
     void check_nomic() const;
+    // A jina-bert-v2 file's tensor table, the header only as check_nomic: the six matrices and ffn_gate
+    // per layer present, F16 and of the graph's shapes, the five biases present; no position_embd.weight,
+    // no attn_q_norm / attn_k_norm / attn_norm_2 (the -code, -de, -es, -zh files' graph).
+    void check_jina() const;
     // Q4_0 / Q5_0 matrices (32-weight blocks, f16 scale, Q8_0 activations as Q8_0's): served in a
     // dense LLaMA graph, alone (llama-quantize's Q4_0 / Q5_0 files, head Q6_K) or inside a k-quant
     // file.  check_types reads the header only: true when a matrix has one of the two types; refuses,
@@ -356,6 +366,7 @@ struct Ctx {
     float *enc_x = nullptr, *enc_a = nullptr, *enc_x1 = nullptr, *enc_q = nullptr, *enc_o = nullptr, *enc_h = nullptr;
     __half *enc_k = nullptr, *enc_v = nullptr;   // [enc_rows][n_embd] f16 K / V of the layer
     float2* enc_rope = nullptr;         // nomic-bert: [enc_rows][n_rot / 2] (cos, sin) of the call's rows
+    float* enc_slopes = nullptr;        // jina-bert-v2: [n_head] ALiBi slopes (alibi_slopes, computed on the host)
     float* enc_pool = nullptr;          // [enc_rows][n_embd] the pooled row of each sequence of mi_encode_seqs
     int enc_nseq = 0;                   // sequences of the last call when it was mi_encode_seqs, else 0
     void enc_init();

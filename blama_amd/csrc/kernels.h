@@ -622,7 +622,9 @@ void launch_embd_pool(const EmbdPool& p, hipStream_t s);
 
 // ---- encoder models (enc.hip): llm_build_bert, b5187 ----
 constexpr int ENC_MAX_TOK = 512;   // tokens of a sequence the short attention kernels take (a tile's scores stay in LDS)
-constexpr int ENC_MAX_SEQ = 2048;  // tokens of one sequence: past ENC_MAX_TOK on enc_attn_long_kernel (enc_nomic.hip)
+constexpr int ENC_MAX_LONG = 2048; // tokens of a sequence enc_attn_long_kernel (enc_nomic.hip) takes, past ENC_MAX_TOK
+constexpr int ENC_MAX_SEQ = 8192;  // tokens of one sequence: past ENC_MAX_LONG on enc_attn_xlong_kernel (enc_jina.hip)
+constexpr int ENC_XL_Q = 128;      // queries of a workgroup of enc_attn_xlong_kernel: four 32-query tiles
 constexpr int ENC_MAX_ROWS = 8192; // token rows of one call: the sequences of mi_encode_seqs laid end to end
 // out[t] = pos[p] + (tok[tokens[t]] + typ[0]), p = positions ? positions[t] : t: the tables F16
 // (*_f16) or F32 rows of n_embd.  pos == nullptr (nomic-bert: rotary positions): out[t] = tok[tokens[t]] + typ[0]
@@ -659,7 +661,9 @@ struct EncGemm {
 void launch_enc_gemm(const EncGemm& p, hipStream_t s);
 // Bidirectional attention of ntok tokens over themselves: q f32 [ntok][q_stride], k / v f16
 // [ntok][kv_stride], head h at columns h * head_dim; out f32 [ntok][out_stride].  head_dim 32 or 64.
-// 1 <= ntok <= ENC_MAX_SEQ: up to ENC_MAX_TOK on enc_attn_kernel, past it on enc_attn_long_kernel.
+// 1 <= ntok <= ENC_MAX_SEQ: up to ENC_MAX_TOK on enc_attn_kernel, up to ENC_MAX_LONG on
+// enc_attn_long_kernel, past it on enc_attn_xlong_kernel.  slopes (device, [n_head]; null: none): ALiBi,
+// the scaled score of (query i, key j) takes slopes[head] * -(float)|i - j|.
 struct EncAttn {
     const float* q;
     const __half *k, *v;
@@ -667,6 +671,7 @@ struct EncAttn {
     int n_head, head_dim, ntok;
     float scale;
     float* out;
+    const float* slopes = nullptr;
 };
 bool enc_attn_supported(int head_dim);
 void init_enc_attributes();      // once per device (the attention kernel's LDS limit)
@@ -680,12 +685,14 @@ void launch_enc_attn(const EncAttn& p, hipStream_t s);
 //   tiles [n_tiles] int4 {start, len, offset of the 32-query tile inside the sequence, s}
 // Tiles are counted per sequence (ceil(len / 32) each), so n_tiles <= the call's tokens.  The tiles
 // of the sequences of at most ENC_MAX_TOK tokens come first, in sequence order, then the *n_long
-// tiles of the longer ones: each group is one launch of its own kernel.
-// Returns n_tiles; throws when a length is outside 1 .. ENC_MAX_SEQ (naming the sequence).
-int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long = nullptr);
+// tiles of those of at most ENC_MAX_LONG tokens, then *n_xlong entries of the longer ones, one per
+// ENC_XL_Q queries (offset a multiple of ENC_XL_Q): each group is one launch of its own kernel.
+// Returns the entries of all three groups; throws when a length is outside 1 .. ENC_MAX_SEQ (naming the sequence).
+int enc_seq_lists(const int* seq_len, int n_seq, int* seqs, int* tiles, int* n_long = nullptr, int* n_xlong = nullptr);
 // Attention as EncAttn's, per sequence, on v_mfma_f32_32x32x16_f16; a workgroup per (head, tile):
-// enc_attn_seq_kernel for the sequences of at most ENC_MAX_TOK tokens, enc_attn_long_kernel for the
-// longer ones, chosen per sequence by its length alone.
+// enc_attn_seq_kernel for the sequences of at most ENC_MAX_TOK tokens, enc_attn_long_kernel up to
+// ENC_MAX_LONG, enc_attn_xlong_kernel past it, chosen per sequence by its length alone.  slopes as EncAttn's,
+// with i and j the positions inside the sequence.
 // A sequence's output rows have the same bits whatever else the call holds.
 struct EncAttnSeq {
     const float* q;        // [ntok][q_stride]
@@ -697,6 +704,7 @@ struct EncAttnSeq {
     const int* tiles;      // device, from enc_seq_lists
     const int* seq_len;    // host [n_seq]: read by the launcher's checks only
     int n_seq;
+    const float* slopes = nullptr;   // device [n_head], or null
 };
 void launch_enc_attn_seq(const EncAttnSeq& p, hipStream_t s);
 // Pooling of every sequence of a call, a workgroup per (sequence, 64 columns): CLS the first row,
@@ -738,10 +746,22 @@ struct EncGemmPair {
     int x_stride;
     float* out;            // [ntok][out_stride]
     int out_stride;
+    const unsigned short* gelu_tab = nullptr;   // launch_enc_gemm_geglu: ggml_table_gelu_f16
 };
 void launch_enc_gemm_swiglu(const EncGemmPair& p, hipStream_t s);
 // enc_attn_long_kernel over n_tiles entries of p.tiles (device), or, p.tiles null, over the
 // (p.ntok + 31) / 32 tiles of one sequence of p.ntok tokens.  p.seq_len / p.n_seq are not read.
 void launch_enc_attn_long(const EncAttnSeq& p, int n_tiles, hipStream_t s);
+
+// ---- jina-bert-v2 (enc_jina.hip): ALiBi, the GELU-gated FFN, sequences past ENC_MAX_LONG ----
+// ggml_compute_forward_soft_max_f32's per-head slopes for max_bias (host, f32): n2 = 2^floor(log2 n_head),
+// m0 = powf(2, -max_bias / n2), m1 = powf(2, -max_bias / 2 / n2); head h: h < n2 ? powf(m0, h + 1) :
+// powf(m1, 2 (h - n2) + 1).  Uploaded once per context; the device never calls powf.
+void alibi_slopes(int n_head, float max_bias, float* out);
+// out[t][r] = gelu(gate[r] . f16(x[t])) * (up[r] . f16(x[t])), gelu by p.gelu_tab as ENC_GELU's
+void launch_enc_gemm_geglu(const EncGemmPair& p, hipStream_t s);
+// enc_attn_xlong_kernel over n_groups entries of p.tiles (device; offsets multiples of ENC_XL_Q), or,
+// p.tiles null, over the ceil(p.ntok / ENC_XL_Q) groups of one sequence of p.ntok tokens (up to ENC_MAX_SEQ).
+void launch_enc_attn_xlong(const EncAttnSeq& p, int n_groups, hipStream_t s);
 
 }  // namespace mi

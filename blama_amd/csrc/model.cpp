@@ -237,6 +237,33 @@ void Model::check_nomic() const {
     }
 }
 
+void Model::check_jina() const {
+    if (gguf.tensor("position_embd.weight"))
+        throw Error("tensor position_embd.weight: a jina-bert-v2 model has no position table (its attention carries ALiBi)");
+    const long long E = hp.n_embd, F = hp.n_ff;
+    const struct { const char* name; long long rows, K; bool bias; } mats[7] = {
+        {"attn_q", E, E, true}, {"attn_k", E, E, true}, {"attn_v", E, E, true}, {"attn_output", E, E, true},
+        {"ffn_up", F, E, false}, {"ffn_gate", F, E, false}, {"ffn_down", E, F, true}};
+    for (int l = 0; l < hp.n_layer; ++l) {
+        const std::string b = "blk." + std::to_string(l) + ".";
+        for (const char* n : {"attn_q_norm", "attn_k_norm", "attn_norm_2"})
+            if (gguf.tensor(b + n + ".weight"))
+                throw Error("tensor " + b + n + ".weight: the jina-bert-v2 variants with q/k norms or a second attention norm are not served");
+        for (const auto& m : mats) {
+            const std::string n = b + m.name + ".weight";
+            const GgufTensor* t = gguf.tensor(n);
+            if (!t)
+                throw Error("GGUF: missing tensor " + n + (std::string(m.name) == "ffn_gate"
+                            ? " (jina-bert-v2's FFN is gated: gelu(gate x) * (up x))" : ""));
+            if (t->type != T_F16)
+                throw Error("tensor " + n + ": a jina-bert-v2 matrix must be F16 (ggml type " + std::to_string(t->type) + " is not served)");
+            if (t->n_dims != 2 || t->ne[0] != m.K || t->ne[1] != m.rows)
+                throw Error("tensor " + n + ": expected " + std::to_string(m.rows) + " x " + std::to_string(m.K) + " (rows x K)");
+            if (m.bias && !gguf.tensor(b + m.name + ".bias")) throw Error("GGUF: missing tensor " + b + m.name + ".bias");
+        }
+    }
+}
+
 bool Model::check_types() const {
     bool any = false;
     // (a MoE model: its expert tensors first, so that the message names one of them)
@@ -375,11 +402,12 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     vocab_only = p.vocab_only != 0;
     gguf.parse(data, size);
     const std::string arch = gguf.get_str("general.architecture", "");
-    if (arch != "llama" && arch != "gpt2" && arch != "bert" && arch != "nomic-bert")
-        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama, gpt2, bert and nomic-bert graphs)");
+    if (arch != "llama" && arch != "gpt2" && arch != "bert" && arch != "nomic-bert" && arch != "jina-bert-v2")
+        throw Error("unsupported architecture '" + arch + "' (this backend serves the llama, gpt2, bert, nomic-bert and jina-bert-v2 graphs)");
     hp.nomic = arch == "nomic-bert";   // llm_build_bert's nomic branch: an encoder like BERT to every caller
-    hp.arch = arch == "gpt2" ? ARCH_GPT2 : arch == "bert" || hp.nomic ? ARCH_BERT : ARCH_LLAMA;
-    const bool bert = hp.arch == ARCH_BERT, nomic = hp.nomic;
+    hp.jina = arch == "jina-bert-v2";  // and its jina branch
+    hp.arch = arch == "gpt2" ? ARCH_GPT2 : arch == "bert" || hp.nomic || hp.jina ? ARCH_BERT : ARCH_LLAMA;
+    const bool bert = hp.arch == ARCH_BERT, nomic = hp.nomic, jina = hp.jina;
     auto key = [&](const char* k) { return arch + "." + k; };
     hp.n_embd = (int)gguf.get_int(key("embedding_length"), 0);
     hp.n_layer = (int)gguf.get_int(key("block_count"), 0);
@@ -425,6 +453,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             throw Error("nomic-bert: " + key("rope.dimension_count") + " " + std::to_string(hp.n_rot) +
                         " is not served (the fused Q|K|V launch rotates a multiple of 16 dimensions)");
         if (nomic) check_nomic();
+        if (jina) check_jina();
     }
 
     if (const GgufValue* tv = gguf.get("tokenizer.ggml.tokens")) tokens = tv->arr_s;
@@ -525,7 +554,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
     };
     const bool gpt2 = hp.arch == ARCH_GPT2;
     const int i_te = add("token_embd.weight", true, 1);
-    const int i_pe = gpt2 || (bert && !nomic) ? add("position_embd.weight", true, 1) : -1;
+    const int i_pe = gpt2 || (bert && !nomic && !jina) ? add("position_embd.weight", true, 1) : -1;
     const int i_on = bert ? -1 : add("output_norm.weight", true, 1);
     const int i_onb = gpt2 ? add("output_norm.bias", true, 1) : -1;
     int i_out = bert ? -1 : add("output.weight", false, 1);
@@ -562,7 +591,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             if (t->ne[0] != hp.n_embd || t->ne[1] < rows_min) throw Error("tensor " + t->name + ": unexpected shape");
         };
         table(i_te, 1);
-        if (!nomic) {
+        if (i_pe >= 0) {
             table(i_pe, 1);
             hp.n_ctx_train = (int)std::min<long long>(hp.n_ctx_train, plan[i_pe].t->ne[1]);   // the position table ends here
         }
@@ -584,8 +613,12 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
             }
             for (int k = 0; k < 6 && !nomic; ++k) {
                 x.w[k] = bert_mat(b + mats[k] + ".weight", mrows[k], mK[k]);
-                x.b[k] = bert_vec(b + mats[k] + ".bias", mrows[k]);
+                x.b[k] = jina && k == 4 ? -1 : bert_vec(b + mats[k] + ".bias", mrows[k]);   // jina-bert-v2: ffn_up has no bias
                 weight_bytes += (long long)plan[x.w[k]].t->nbytes;
+            }
+            if (jina) {
+                x.gate = bert_mat(b + "ffn_gate.weight", F, E_);
+                weight_bytes += (long long)plan[x.gate].t->nbytes;
             }
             x.an = bert_vec(b + "attn_output_norm.weight", E_);
             x.anb = bert_vec(b + "attn_output_norm.bias", E_);
@@ -721,6 +754,7 @@ void Model::load(const uint8_t* data, size_t size, const mi_model_params& p) {
                 L.wq = f16p(x.w[0]); L.wk = f16p(x.w[1]); L.wv = f16p(x.w[2]);
                 L.bq = f32p(x.b[0]); L.bk = f32p(x.b[1]); L.bv = f32p(x.b[2]);
                 L.bo = f32p(x.b[3]); L.bup = f32p(x.b[4]); L.bdown = f32p(x.b[5]);
+                if (jina) L.gate = f16p(x.gate);
             }
             L.attn_out_norm = f32p(x.an); L.attn_out_norm_b = f32p(x.anb);
             L.layer_out_norm = f32p(x.on); L.layer_out_norm_b = f32p(x.onb);

@@ -1097,14 +1097,14 @@ int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int3
 }
 
 // Bidirectional attention of ntok tokens over themselves (enc.hip enc_attn_kernel; past 512 tokens
-// enc_nomic.hip enc_attn_long_kernel): q f32 [ntok][n_head * head_dim], k / v f16 of the same shape -> out
+// enc_nomic.hip enc_attn_long_kernel, past 2048 enc_jina.hip enc_attn_xlong_kernel): q f32 [ntok][n_head * head_dim], k / v f16 of the same shape -> out
 // f32; scale 1 / sqrtf(head_dim).
 int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok, const float* q,
                             const uint16_t* k_f16, const uint16_t* v_f16, float* out) {
     try {
         if (!q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc: null argument");
         if (n_head < 1 || ntok < 1 || ntok > ENC_MAX_SEQ || !enc_attn_supported(head_dim))
-            throw Error("op_attention_enc: head_dim 32 or 64, 1 <= ntok <= 2048");
+            throw Error("op_attention_enc: head_dim 32 or 64, 1 <= ntok <= 8192");
         MI_HIP(hipSetDevice(device));
         init_enc_attributes();
         const int ne = n_head * head_dim;
@@ -1127,7 +1127,7 @@ int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_di
     try {
         if (!seq_len || !q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc_seqs: null argument");
         if (n_head < 1 || n_seq < 1 || !enc_attn_supported(head_dim)) throw Error("op_attention_enc_seqs: head_dim 32 or 64, n_seq >= 1");
-        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 2048
+        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 8192
         enc_seq_lists(seq_len, n_seq, nullptr, tiles.data());
         long long ntok = 0;
         for (int s = 0; s < n_seq; ++s) ntok += seq_len[s];
@@ -1141,6 +1141,38 @@ int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_di
         Dev<int> dt(tiles.size(), tiles.data());
         launch_enc_attn_seq(EncAttnSeq{dq.p, dk.p, dv.p, ne, ne, ne, n_head, head_dim, (int)ntok, 1.0f / std::sqrt((float)head_dim),
                                        dout.p, dt.p, seq_len, n_seq},
+                            nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dout.download(out);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// mi_op_attention_enc_seqs with the ALiBi slopes of max_bias (alibi_slopes, computed on the host) on every
+// score; max_bias 0: a null slope pointer, the kernels without the bias.
+int32_t mi_op_attention_enc_alibi(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
+                                  float max_bias, const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out) {
+    try {
+        if (!seq_len || !q || !k_f16 || !v_f16 || !out) throw Error("op_attention_enc_alibi: null argument");
+        if (n_head < 1 || n_seq < 1 || !enc_attn_supported(head_dim)) throw Error("op_attention_enc_alibi: head_dim 32 or 64, n_seq >= 1");
+        if (!(max_bias >= 0.0f)) throw Error("op_attention_enc_alibi: max_bias must be 0 (no bias) or positive");
+        std::vector<int> tiles(4 * (size_t)enc_seq_lists(seq_len, n_seq, nullptr, nullptr));   // throws on a length outside 1 .. 8192
+        enc_seq_lists(seq_len, n_seq, nullptr, tiles.data());
+        long long ntok = 0;
+        for (int s = 0; s < n_seq; ++s) ntok += seq_len[s];
+        if (ntok > ENC_MAX_ROWS) throw Error("op_attention_enc_alibi: at most 8192 tokens");
+        MI_HIP(hipSetDevice(device));
+        init_enc_attributes();
+        const int ne = n_head * head_dim;
+        const size_t n = (size_t)ntok * ne;
+        std::vector<float> sl((size_t)n_head);
+        alibi_slopes(n_head, max_bias, sl.data());
+        Dev<float> dq(n, q), dout(n), dsl(sl.size(), sl.data());
+        Dev<__half> dk(n, f16(k_f16)), dv(n, f16(v_f16));
+        Dev<int> dt(tiles.size(), tiles.data());
+        launch_enc_attn_seq(EncAttnSeq{dq.p, dk.p, dv.p, ne, ne, ne, n_head, head_dim, (int)ntok, 1.0f / std::sqrt((float)head_dim),
+                                       dout.p, dt.p, seq_len, n_seq, max_bias > 0.0f ? dsl.p : nullptr},
                             nullptr);
         MI_HIP(hipDeviceSynchronize());
         dout.download(out);
@@ -1190,6 +1222,26 @@ int32_t mi_op_gemm_f16_swiglu(int32_t device, const uint16_t* gate_f16, const ui
         Dev<__half> dg((size_t)rows * K, f16(gate_f16)), du((size_t)rows * K, f16(up_f16));
         Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows);
         launch_enc_gemm_swiglu(enc_swiglu_gemm_of(dg.p, du.p, rows, K, dx.p, ntok, dy.p), nullptr);
+        MI_HIP(hipDeviceSynchronize());
+        dy.download(y);
+        return 0;
+    }
+    MI_TRY(-1)
+}
+
+// The gate/up pair launch of a jina-bert-v2 layer (enc_jina.hip enc_gemm_geglu_kernel):
+// y[t][r] = gelu(gate[r] . f16(x[t])) * (up[r] . f16(x[t])), gelu by ggml's f16 table.
+int32_t mi_op_gemm_f16_geglu(int32_t device, const uint16_t* gate_f16, const uint16_t* up_f16, int32_t rows, int32_t K,
+                             int32_t ntok, const float* x, float* y) {
+    try {
+        if (!gate_f16 || !up_f16 || !x || !y) throw Error("op_gemm_f16_geglu: null argument");
+        if (rows < 32 || rows % 32 || K < 32 || K % 32 || ntok < 1 || ntok > ENC_MAX_ROWS)
+            throw Error("op_gemm_f16_geglu: rows % 32, K % 32, 1 <= ntok <= 8192");
+        MI_HIP(hipSetDevice(device));
+        Dev<__half> dg((size_t)rows * K, f16(gate_f16)), du((size_t)rows * K, f16(up_f16));
+        Dev<float> dx((size_t)ntok * K, x), dy((size_t)ntok * rows);
+        Dev<unsigned short> dt(65536, gelu_table_host().data());   // ggml_table_gelu_f16
+        launch_enc_gemm_geglu(enc_geglu_gemm_of(dg.p, du.p, rows, K, dx.p, ntok, dy.p, dt.p), nullptr);
         MI_HIP(hipDeviceSynchronize());
         dy.download(y);
         return 0;

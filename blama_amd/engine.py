@@ -148,6 +148,8 @@ _SIGS = {
     "mi_op_gemm_f16_rope": (C.c_int32, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                         C.c_float, C.c_float, _P, _P, _P]),
     "mi_op_gemm_f16_swiglu": (C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mi_op_attention_enc_alibi": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
+    "mi_op_gemm_f16_geglu": (C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mi_op_quant_act": (C.c_int32, [C.c_int32] * 3 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P, C.c_int32,
                                     C.c_int32, _P, C.c_int32] + [_P] * 6),
     "mi_op_dgemv_norm": (C.c_int32, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
@@ -944,6 +946,37 @@ def op_gemm_f16_swiglu(gate16: np.ndarray, up16: np.ndarray, x: np.ndarray, devi
     y = np.empty((x.shape[0], rows), np.float32)
     _check(lib().mi_op_gemm_f16_swiglu(device, _ptr(gate16), _ptr(up16), rows, K, x.shape[0], _ptr(x), _ptr(y)),
            "op_gemm_f16_swiglu")
+    return y
+
+
+def op_attention_enc_alibi(q: np.ndarray, k16: np.ndarray, v16: np.ndarray, seq_len, max_bias: float = 8.0,
+                           device: int = 0) -> np.ndarray:
+    """mi_op_attention_enc_alibi: op_attention_enc_seqs with the ALiBi slopes of max_bias on every score
+    (0: no bias); sequences of up to 8192 tokens."""
+    q = np.ascontiguousarray(q, np.float32)
+    ntok, n_head, hd = q.shape
+    k16 = np.ascontiguousarray(k16, np.float16)
+    v16 = np.ascontiguousarray(v16, np.float16)
+    lens = np.ascontiguousarray(seq_len, np.int32)
+    if int(lens.sum()) != ntok:
+        raise EngineError(f"op_attention_enc_alibi: the lengths sum to {int(lens.sum())}, q has {ntok} rows")
+    out = np.empty((ntok, n_head, hd), np.float32)
+    _check(lib().mi_op_attention_enc_alibi(device, n_head, hd, lens.size, _ptr(lens), max_bias, _ptr(q), _ptr(k16), _ptr(v16),
+                                           _ptr(out)), "op_attention_enc_alibi")
+    return out
+
+
+def op_gemm_f16_geglu(gate16: np.ndarray, up16: np.ndarray, x: np.ndarray, device: int = 0) -> np.ndarray:
+    """mi_op_gemm_f16_geglu: gate16 / up16 (rows, K) float16, x (ntok, K) f32 -> gelu(gate x) * (up x), (ntok, rows) f32."""
+    gate16 = np.ascontiguousarray(gate16, np.float16)
+    up16 = np.ascontiguousarray(up16, np.float16)
+    x = np.ascontiguousarray(x, np.float32)
+    rows, K = gate16.shape
+    if up16.shape != (rows, K) or x.shape[1] != K:
+        raise EngineError("op_gemm_f16_geglu: gate16, up16 and x do not fit")
+    y = np.empty((x.shape[0], rows), np.float32)
+    _check(lib().mi_op_gemm_f16_geglu(device, _ptr(gate16), _ptr(up16), rows, K, x.shape[0], _ptr(x), _ptr(y)),
+           "op_gemm_f16_geglu")
     return y
 
 

@@ -1149,3 +1149,90 @@ def build_nomic_gguf(cfg: NomicConfig, seed: int = 0, header_only: bool = False,
         view[:] = v.astype(np.float16 if t == F16 else np.float32).view(np.uint8)
 
     return w.to_bytes(fill=fill)
+
+
+# ---- jina-bert-v2 encoder models (llm_build_bert's jina branch: jina-embeddings-v2's shape, F16) ----
+
+@dataclass(frozen=True)
+class JinaConfig(BertConfig):
+    pass
+
+
+JINA_CONFIGS = {
+    # jina-embeddings-v2's head geometry (head_dim 64, MEAN pooling, 8192 trained positions) at 2 layers and
+    # small widths; n_ff no multiple of 128 (a partial workgroup of row tiles)
+    "jina-s": JinaConfig("jina-s", 300, 128, 2, 2, 320, 8192, pooling_type=1),
+    # head_dim 32, three heads: head 2 takes its ALiBi slope from the m1 branch
+    "jina-h3": JinaConfig("jina-h3", 300, 96, 2, 3, 256, 8192),
+}
+
+
+def jina_tensor_shapes(cfg: JinaConfig) -> dict:
+    d, f = cfg.n_embd, cfg.n_ff
+    s = {"token_embd.weight": (d, cfg.n_vocab), "token_types.weight": (d, cfg.n_token_types),
+         "token_embd_norm.weight": (d,), "token_embd_norm.bias": (d,)}
+    for i in range(cfg.n_layer):
+        p = f"blk.{i}."
+        for n in ("attn_q", "attn_k", "attn_v", "attn_output"):
+            s[p + n + ".weight"] = (d, d)
+            s[p + n + ".bias"] = (d,)
+        s[p + "attn_output_norm.weight"] = (d,)
+        s[p + "attn_output_norm.bias"] = (d,)
+        s[p + "ffn_up.weight"] = (d, f)
+        s[p + "ffn_gate.weight"] = (d, f)
+        s[p + "ffn_down.weight"] = (f, d)
+        s[p + "ffn_down.bias"] = (d,)
+        s[p + "layer_output_norm.weight"] = (d,)
+        s[p + "layer_output_norm.bias"] = (d,)
+    return s
+
+
+def build_jina_gguf(cfg: JinaConfig, seed: int = 0, header_only: bool = False, types: dict | None = None, drop=(),
+                    extra: dict | None = None, causal: bool = False) -> np.ndarray:
+    """A synthetic jina-bert-v2 GGUF (general.architecture "jina-bert-v2", llama.cpp b5187's keys and tensor
+    names): BERT's biased attn_q / attn_k / attn_v / attn_output and ffn_down, ffn_gate beside ffn_up without
+    biases, no position table.  types / drop / extra as build_nomic_gguf; causal: jina-bert-v2.attention.causal."""
+    vocab = bert_vocab(cfg.n_vocab)
+    a = "jina-bert-v2."
+    w = gguf.GGUFWriter()
+    w.add_str("general.architecture", "jina-bert-v2")
+    w.add_str("general.name", f"synthetic {cfg.name} F16")
+    w.add_u32("general.file_type", 1)
+    w.add_u32(a + "context_length", cfg.n_ctx_train)
+    w.add_u32(a + "embedding_length", cfg.n_embd)
+    w.add_u32(a + "block_count", cfg.n_layer)
+    w.add_u32(a + "feed_forward_length", cfg.n_ff)
+    w.add_u32(a + "attention.head_count", cfg.n_head)
+    w.add_f32(a + "attention.layer_norm_epsilon", cfg.eps)
+    w.add_bool(a + "attention.causal", causal)
+    if cfg.pooling_type >= 0:
+        w.add_u32(a + "pooling_type", cfg.pooling_type)
+    w.add_str("tokenizer.ggml.model", "bert")
+    w.add_array("tokenizer.ggml.tokens", gguf.T_STRING, vocab["tokens"])
+    w.add_array("tokenizer.ggml.token_type", gguf.T_INT32, vocab["types"])
+    w.add_u32("tokenizer.ggml.token_type_count", cfg.n_token_types)
+    w.add_u32("tokenizer.ggml.cls_token_id", vocab["cls"])
+    w.add_u32("tokenizer.ggml.seperator_token_id", vocab["sep"])
+    w.add_u32("tokenizer.ggml.unknown_token_id", vocab["unk"])
+    w.add_u32("tokenizer.ggml.padding_token_id", vocab["pad"])
+    shapes = {**jina_tensor_shapes(cfg), **(extra or {})}
+    ttypes = {n: (F16 if len(s) == 2 else F32) for n, s in shapes.items()}
+    ttypes.update(types or {})
+    for name, shape in shapes.items():
+        if name not in drop:
+            w.add_tensor(name, ttypes[name], shape)
+    if header_only:
+        return np.frombuffer(w.header_bytes()[0], np.uint8).copy()
+
+    def fill(name, t, shape, view):
+        rng = _rng(seed, name)
+        n = int(np.prod(shape))
+        if name.endswith("norm.weight"):
+            v = rng.uniform(0.8, 1.2, n)
+        elif name.endswith(".bias"):
+            v = rng.standard_normal(n) * 0.05
+        else:   # ffn_gate at ffn_up's scale (unit-variance g, as BERT's GELU input): the f16 table's fine bins
+            v = rng.standard_normal(n) * _bert_std(cfg, name)
+        view[:] = v.astype(np.float16 if t == F16 else np.float32).view(np.uint8)
+
+    return w.to_bytes(fill=fill)

@@ -224,7 +224,7 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * head_dim 32 or 64; llm_build_bert).  A context on one holds no KV cache and is ALWAYS in
  * embeddings mode, created with the model's pooling type (NONE when the key is absent).  Every
  * mi_decode call is one stateless bidirectional pass: its n tokens take positions 0 .. n - 1, use
- * token type 0 and attend to each other only; n <= min(n_batch, 2048, n_ctx_train), more is refused
+ * token type 0 and attend to each other only; n <= min(n_batch, 8192, n_ctx_train), more is refused
  * (< 0, with a message), as are token ids outside the vocabulary.  out_mode, pooling and the rows of
  * mi_embeddings are as above.  On such a context: mi_ctx_set_embeddings(ctx, 0, ..) < 0 (no output
  * head); mi_kv_pos_max is -1 and mi_kv_n_cells 0 always; mi_kv_clear is a no-op; mi_kv_seq_* and
@@ -238,8 +238,21 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * matrices and neither a projection bias nor position_embd.weight; anything else is refused at load
  * (vocab-only too) with the tensor's name.  A sequence of more than 512 tokens (either architecture)
  * runs its attention on the long-sequence kernel of enc_nomic.hip; shorter ones run the code and
- * give the bits they always did.  Not served: quantised or F32 encoder matrices, the jina variants
- * (ALiBi, GELU-PAR), nomic-bert-moe, dynamic NTK scaling, RANK pooling, token types other than 0.
+ * give the bits they always did.
+ * general.architecture "jina-bert-v2" (jina-embeddings-v2-small-en / -base-en; llm_build_bert's jina
+ * branch) is served as such an encoder too: no position table -- every attention score of (query i, key
+ * j) takes slope_h * -(float)|i - j| (ALiBi, max bias 8: the slopes of ggml_soft_max_ext, computed on the
+ * host) after the scale --, a gated FFN gelu(gate x) * (up x) in one pair launch (ggml's f16 GELU table),
+ * BERT's projection biases except on ffn_up / ffn_gate (neither has one), and 8192 trained positions.  Its files must hold F16
+ * attn_q / attn_k / attn_v / attn_output / ffn_up / ffn_gate / ffn_down matrices with the five biases and
+ * neither position_embd.weight nor attn_q_norm / attn_k_norm / attn_norm_2 (the -code, -de, -es and -zh
+ * files); anything else is refused at load (vocab-only too) with the tensor's name.  A sequence of more
+ * than 2048 tokens (any encoder architecture whose n_ctx_train allows it) runs its attention on the
+ * 128-query kernel of enc_jina.hip; a sequence of at most 2048 tokens keeps its kernel and its bits.
+ * With ALiBi a sequence of at most 512 tokens keeps the residual of p's f16 rounding, so
+ * it is rounded more finely than a longer sequence of the same model and than llama.cpp (f16 p in both).
+ * Not served: quantised or F32 encoder matrices, the jina variants with q/k norms or attn_norm_2 and
+ * BPE-tokenised jina files, nomic-bert-moe, dynamic NTK scaling, RANK pooling, token types other than 0.
  *
  * Several sequences in one call (an encoder context only): mi_encode_seqs runs ONE pass over n_seq
  * sequences laid end to end in tokens -- sequence s has seq_len[s] tokens at positions 0 ..
@@ -248,7 +261,7 @@ void mi_ctx_clear_lora(mi_ctx* ctx);
  * n_seq is.  A sequence's rows have the same bits alone and in any batch of sequences.  Refused (< 0,
  * with a message naming the sequence; n_batch is truncated to n_ctx as for every context, so create the
  * context with n_ctx >= the rows a call should hold): a context that is no encoder, n_seq < 1, a length < 1 or >
- * min(n_batch, 2048, n_ctx_train), a total above min(n_batch, 8192), a token id outside the vocabulary.
+ * min(n_batch, 8192, n_ctx_train), a total above min(n_batch, 8192), a token id outside the vocabulary.
  * Pooled context: mi_embeddings_seq(ctx, s) is sequence s's row (MEAN = sum_t row_t * (1.0f / len_s)
  * in token order, CLS the first row, LAST the last), and mi_embeddings is refused until the next
  * mi_decode.  Pooling NONE: mi_embeddings(ctx, row) is the row of token `row` of the concatenation
@@ -518,17 +531,24 @@ int32_t mi_op_moe_decode(int32_t device, int32_t type, const void* gate, const v
 int32_t mi_op_gemm_f16(int32_t device, const uint16_t* w_f16, int32_t rows, int32_t K, int32_t ntok,
                        const float* x, const float* bias, const float* resid, int32_t epilogue, float* y);
 /* The encoder pass's bidirectional attention (enc.hip; past 512 tokens the long-sequence MFMA kernel
- * of enc_nomic.hip): every token over all ntok <= 2048 tokens, no mask, scale 1 / sqrtf(head_dim);
+ * of enc_nomic.hip, past 2048 that of enc_jina.hip): every token over all ntok <= 8192 tokens, no mask, scale 1 / sqrtf(head_dim);
  * q / out: f32 [ntok][n_head * head_dim], k / v: f16 bits of the same shape; head_dim 32 or 64. */
 int32_t mi_op_attention_enc(int32_t device, int32_t n_head, int32_t head_dim, int32_t ntok,
                             const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
 /* The segmented attention of mi_encode_seqs (enc_seq.hip, v_mfma_f32_32x32x16_f16): n_seq sequences laid
- * end to end, sequence s of 1 <= seq_len[s] <= 2048 tokens, every token over the tokens of its own
+ * end to end, sequence s of 1 <= seq_len[s] <= 8192 tokens, every token over the tokens of its own
  * sequence only; shapes and scale as mi_op_attention_enc with ntok = the sum of the lengths (<= 8192).
- * A sequence of more than 512 tokens runs on the long-sequence kernel (enc_nomic.hip) in the same call;
- * the kernel is chosen by the sequence's own length alone. */
+ * A sequence of more than 512 tokens runs on the long-sequence kernel (enc_nomic.hip), one of more than 2048
+ * on the 128-query kernel (enc_jina.hip), in the same call; the kernel is chosen by the sequence's own length alone. */
 int32_t mi_op_attention_enc_seqs(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
                                  const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
+/* mi_op_attention_enc_seqs with ALiBi: the scaled score of (query i, key j) of a sequence of head h takes
+ * slope_h * -(float)|i - j| (a separate f32 product and add), slope_h from ggml_soft_max_ext's rule for
+ * max_bias: n2 = 2^floor(log2(n_head)), m0 = powf(2, -max_bias / n2), m1 = powf(2, -max_bias / 2 / n2),
+ * slope_h = h < n2 ? powf(m0, h + 1) : powf(m1, 2 (h - n2) + 1), computed on the host.  max_bias 0: no
+ * bias, the bits of mi_op_attention_enc_seqs. */
+int32_t mi_op_attention_enc_alibi(int32_t device, int32_t n_head, int32_t head_dim, int32_t n_seq, const int32_t* seq_len,
+                                  float max_bias, const float* q, const uint16_t* k_f16, const uint16_t* v_f16, float* out);
 /* The fused Q|K|V launch of a nomic-bert layer (enc_nomic.hip): the F16 GEMM of mi_op_gemm_f16 over w
  * [3 n_embd][K] f16 bits (Q rows, K rows, V rows; n_embd = n_head * head_dim) with ggml_rope_ext in
  * mode NEOX in its epilogue: in every Q and K head, for ic < n_rot / 2, out[ic] = y[ic] cos - y[ic +
@@ -544,6 +564,10 @@ int32_t mi_op_gemm_f16_rope(int32_t device, const uint16_t* w_f16, int32_t n_hea
  * silu(g) = g / (1 + expf(-g)); y: [ntok][rows]; rows % 32 == 0, K % 32 == 0, 1 <= ntok <= 8192. */
 int32_t mi_op_gemm_f16_swiglu(int32_t device, const uint16_t* gate_f16, const uint16_t* up_f16, int32_t rows, int32_t K,
                               int32_t ntok, const float* x, float* y);
+/* The gate/up pair launch of a jina-bert-v2 layer (enc_jina.hip): as mi_op_gemm_f16_swiglu with
+ * y[t][r] = gelu(g) * u, gelu by ggml's f16 table as epilogue 2 of mi_op_gemm_f16 (without a bias). */
+int32_t mi_op_gemm_f16_geglu(int32_t device, const uint16_t* gate_f16, const uint16_t* up_f16, int32_t rows, int32_t K,
+                             int32_t ntok, const float* x, float* y);
 /* Median device time (us) of `iters` launches of mi_op_gemv's GEMV (micro-benchmark). */
 int32_t mi_op_gemv_bench(int32_t device, int32_t type, const void* raw_blocks, int32_t rows, int32_t K,
                          int32_t iters, float* median_us);
